@@ -1,32 +1,39 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mvoxels/s of (voxelize + JFA) at n = 512 on the 1,348,128-face bunny.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n {512,1024,2048}]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n {512,1024,2048}] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = tiled voxelization of the resident mesh into a bit-packed n^3 grid followed by the full JFA
 (border mask, first pass from the mask, sparse / dense tile passes, last pass fused with the id -> sdf
 conversion) into a float sdf -- both through the C ABI of libvphip.so, inputs already in HBM.
+A plain run sets up, warms up, times K steps, writes the outputs of the last one (--dump-outputs) and prints the line;
+every block marked [full] below takes runs of its own and is measured only with --full.
 Rank 0 prints ONE JSON line (DESIGN.md "Measurement"):
 
   value / ms_per_step   whole job, wall clock between barriers, max over ranks
   roofline              the DOMINANT kernel only: the dense tile pass (jfa_dense), its own algorithmic bytes
                         (2 * S * n^3) / its own mean launch time from hipEvents on the kernel's stream
-  kernels               every kernel of the step: launches per step, mean ms, algorithmic bytes, GB/s, fraction of peak
-  n1024                 (N = 1, default size only) the same JFA at n = 1024, where the north star puts its roofline target
-  cpu_baseline          the oracle (C restatement of the reference's sequential path) on the box's host cores:
+  kernels               the dominant kernel from the timed region; [full] every other kernel of the step from TABLE_STEPS further
+                        steps: launches per step, mean ms, algorithmic bytes, GB/s, fraction of peak
+  n1024                 [full] (N = 1, default size only) the same JFA at n = 1024, where the north star puts its roofline target
+  cpu_baseline          [full] the oracle (C restatement of the reference's sequential path) on the box's host cores:
                         1-thread voxelize + OpenMP JFA with ALL passes -- measured, not extrapolated
-  copy_peak             (N = 1) vp_stream_copy over 1 GiB on this box: roofline.measured_copy_GBs / frac_of_measured
-  config3               (N = 1, default size) BASELINE config 3 as a pipeline: bimba + bunny voxelize, CSG union, JFA at n = 512,
+  copy_peak             [full] (N = 1) vp_stream_copy over 1 GiB on this box: roofline.measured_copy_GBs / frac_of_measured
+  config3               [full] (N = 1, default size) BASELINE config 3 as a pipeline: bimba + bunny voxelize, CSG union, JFA at n = 512,
                         device-resident; kernels.csg_words against 3 n^3/8 bytes; checked against the reference's golden row
-  vox_large_triangles   (N = 1, default size) the LDS tile rasteriser on a mesh of large triangles (vox_scan / vox_scatter / vox_tile per step),
+  vox_large_triangles   [full] (N = 1, default size) the LDS tile rasteriser on a mesh of large triangles (vox_scan / vox_scatter / vox_tile per step),
                         checked against the naive voxelizer
-  totals_incl_transfers (N = 1, default size) one host-in / host-out round (vp_voxelize_host + vp_jfa_host) = what the
+  totals_incl_transfers [full] (N = 1, default size) one host-in / host-out round (vp_voxelize_host + vp_jfa_host) = what the
                         reference's Compute() calls time as Memory + Processing (38.6 + 829.6 ms)
+
+--dump-outputs DIR (N = 1): after the timed region, what the last timed step handed its caller -- the bit-packed grid and the sdf --
+as float arrays in DIR (dump_outputs: a fixed, seeded sample of the voxels plus the set-voxel count of every z plane, 32 MiB at most).
+The inputs are generated without randomness, so two builds given the same arguments can be compared output for output.
 
 N > 1: strong scaling of the same n^3 job over N Z-slabs, one process per GPU (cuda_mesh_voxelization_amd/slab.py).  After the
 timed region every rank runs the ONE-GPU path on its own device and compares its slab of the bitmask and of the sdf bit for
-bit (`parity_ok`; a mismatch on any rank makes the run exit non-zero), then times the OTHER pipelines over shorter regions, checked
+bit (`parity_ok`; a mismatch on any rank makes the run exit non-zero); [full] then it times the OTHER pipelines over shorter regions, checked
 the same way: `multi_alt` = the transposed pipeline (cyclic planes, ONE RCCL all-to-all), `multi_alt_halo` = RCCL point-to-point halos
 before every pass, `multi_alt_transpose_p2p` = the transposed pipeline with its planes sent point to point and placed directly -- under a
 watchdog (VP_BENCH_ALT_TIMEOUT, default 180 s each): if a transport hangs, rank 0 prints the line of the timed pipeline as it stands, with the time-out recorded in that object,
@@ -59,11 +66,16 @@ def parse_args(argv=None):
                     help="grid side; 512 = the headline configuration, 1024 / 2048 = the sizes the north star shards.  Under "
                          "torch.distributed.run spell it --grid-n: the launcher's own parser rejects a bare --n as an ambiguous "
                          "abbreviation of its --nnodes / --nproc-per-node")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-n1024", action="store_true", help="skip the extra n = 1024 JFA block of the default run")
-    ap.add_argument("--no-config3", action="store_true", help="skip the BASELINE config 3 block (bimba + bunny, CSG union, JFA at n = 512)")
-    ap.add_argument("--no-host-totals", action="store_true", help="skip the host-in / host-out round (reference-style totals)")
-    ap.add_argument("--no-copy-peak", action="store_true", help="skip the 1-GiB stream-copy measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything the headline figure does not need: the per-kernel table, the HBM copy peak, the n = 1024 "
+                         "JFA, config 3, large triangles, host-in / host-out totals, the CPU baseline; N > 1: the other pipelines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, seeded sample; one GPU only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-n1024", action="store_true", help="with --full: skip the extra n = 1024 JFA block")
+    ap.add_argument("--no-config3", action="store_true", help="with --full: skip the BASELINE config 3 block (bimba + bunny, CSG union, JFA at n = 512)")
+    ap.add_argument("--no-host-totals", action="store_true", help="with --full: skip the host-in / host-out round (reference-style totals)")
+    ap.add_argument("--no-copy-peak", action="store_true", help="with --full: skip the 1-GiB stream-copy measurement")
     ap.add_argument("--multi", choices=["ghost", "halo", "hybrid", "transpose", "transpose-p2p"], default="ghost",
                     help="N > 1: 'ghost' = Z-slabs with recomputed ghost planes, no data-path exchange (default: the one pipeline that needs no "
                          "transport the build could never try on hardware); 'transpose' = planes dealt cyclically for every pass whose step is a "
@@ -71,7 +83,12 @@ def parse_args(argv=None):
                          "planes as one batch of point-to-point messages placed directly: no send / staging buffer, no weave); 'halo' = Z-slabs "
                          "with RCCL point-to-point halo planes before every pass; 'hybrid' = ghost planes for the wide passes (k > nz/2), halos of "
                          "the adjacent ranks -- sent a pass ahead, under the interior planes -- for the narrow ones")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
 
 
 def launch_ranks(args):
@@ -81,7 +98,7 @@ def launch_ranks(args):
     returns the child's exit code.  The reference hard-wires device 0 (apps/cli/main.cpp:22-23); this is what replaces it for N > 1."""
     import subprocess
     argv = ["--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--grid-n", str(args.n), "--multi", args.multi]
-    for flag in ("no_cpu_baseline", "no_n1024", "no_config3", "no_host_totals", "no_copy_peak"):
+    for flag in ("full", "no_cpu_baseline", "no_n1024", "no_config3", "no_host_totals", "no_copy_peak"):
         if getattr(args, flag):
             argv.append("--" + flag.replace("_", "-"))
     # --standalone: the launcher's own rendezvous on a port IT picks and keeps (binding one here and closing it again could lose it to another
@@ -344,8 +361,7 @@ TABLE_STEPS = 5
 
 def measure(eng, step, steps, warmup, barrier):
     """The timed region: `steps` steps between barriers, hipEvents only around the dominant kernel (an event pair costs ~3 us of
-    stream time; bracketing all 18 launches of a step cost 0.11 ms = 3 % of it, tools/prof_overhead.py).  The per-kernel table
-    of the other kernels comes from TABLE_STEPS further steps with every launch bracketed, outside the timed region."""
+    stream time; bracketing all 18 launches of a step cost 0.11 ms = 3 % of it, tools/prof_overhead.py)."""
     for _ in range(warmup):
         step()
     barrier()
@@ -359,6 +375,11 @@ def measure(eng, step, steps, warmup, barrier):
     elapsed = time.perf_counter() - t0
     eng.ctx.prof_enable(False)
     live = eng.ctx.prof()
+    return elapsed, live
+
+
+def table_steps(eng, step, barrier):
+    """The per-kernel table of the other kernels: TABLE_STEPS further steps with every launch bracketed, outside the timed region."""
     eng.ctx.prof_reset()
     eng.ctx.prof_select(None)
     eng.ctx.prof_enable(True)
@@ -366,8 +387,7 @@ def measure(eng, step, steps, warmup, barrier):
         step()
     barrier()
     eng.ctx.prof_enable(False)
-    table = eng.ctx.prof()
-    return elapsed, live, table
+    return eng.ctx.prof()
 
 
 def merge_tables(live, steps, table, bytes_per):
@@ -377,7 +397,8 @@ def merge_tables(live, steps, table, bytes_per):
     return kernels
 
 
-def run_single(eng, frame, d_xyz, d_tri, steps, warmup, algo):
+def single_step(eng, frame, d_xyz, d_tri, algo):
+    """the one-GPU step and the two arrays it hands its caller: the bit-packed grid and the sdf"""
     grid = eng.new_grid(frame)
     sdf = torch.empty(frame.voxels, dtype=torch.float32, device=eng.device)
 
@@ -385,7 +406,32 @@ def run_single(eng, frame, d_xyz, d_tri, steps, warmup, algo):
         eng.voxelize(frame, d_xyz, d_tri, out=grid, algo=algo)
         eng.jfa(frame, grid, out=sdf, algo=algo)
 
-    return measure(eng, step, steps, warmup, torch.cuda.synchronize)
+    return step, grid, sdf
+
+
+DUMP_SAMPLES = 1 << 21           # voxels written by --dump-outputs: 8 + 8 + 16 MiB, under the 64 MiB a dump may hold
+DUMP_SEED = 512
+
+
+def dump_outputs(path, frame, grid, sdf):
+    """--dump-outputs: the grid and the sdf of the last timed step as float arrays.  The sdf has n^3 floats (512 MiB at n = 512), so
+    both are sampled at the same DUMP_SAMPLES voxels, drawn without replacement by a generator of fixed seed (sample_index: linear
+    voxel index, x fastest); the whole grid enters as the number of set voxels of every z plane."""
+    n = frame.n
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(frame.voxels, size=min(DUMP_SAMPLES, frame.voxels), replace=False))
+    di = torch.from_numpy(idx).to(grid.device)
+    solid = (grid[di >> 5] >> (di & 31).to(torch.int32)) & 1          # bit i & 31 of word i >> 5 (the reference's layout)
+    ones = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int32, device=grid.device)
+    planes = grid.view(torch.uint8).view(n, -1)
+    per_plane = torch.cat([ones[planes[z:z + 64].long()].sum(1) for z in range(0, n, 64)])
+    out = {"sdf_sample": sdf[di].cpu().numpy().astype(np.float32),
+           "solid_sample": solid.cpu().numpy().astype(np.float32),
+           "sample_index": idx.astype(np.float64),
+           "solid_per_plane": per_plane.cpu().numpy().astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
 
 
 def main():
@@ -453,14 +499,20 @@ def main():
     pipe_report, pipe_desc, parity, multi_alt, alts_ok = None, None, None, None, True
     if world == 1:
         barrier()
-        elapsed, live, table = run_single(eng, frame, d_xyz, d_tri, args.steps, args.warmup, ALGO_TILED)
+        step, grid, sdf = single_step(eng, frame, d_xyz, d_tri, ALGO_TILED)
+        elapsed, live = measure(eng, step, args.steps, args.warmup, torch.cuda.synchronize)
+        if args.dump_outputs is not None:
+            names = dump_outputs(args.dump_outputs, frame, grid, sdf)
+            sys.stderr.write("bench.py: wrote %s to %s\n" % (", ".join(n_ + ".npy" for n_ in names), args.dump_outputs))
+        table = table_steps(eng, step, torch.cuda.synchronize) if args.full else {}
+        del step, grid, sdf
         planes = n
     else:
         from cuda_mesh_voxelization_amd.slab import HostStagedDist, make_pipeline
         p2p = HostStagedDist(dist) if dist.get_backend() == "gloo" else dist        # gloo (the shared-GPU test rig) moves CPU tensors only
         pw, pv = n * n // 32, n * n
 
-        def run_pipeline(kind, steps, warmup):
+        def run_pipeline(kind, steps, warmup, table=True):
             """time `steps` steps of one slab pipeline; returns (elapsed max over ranks, timers, report, this rank's slab of the
             bitmask and of the sdf as copies) and frees the pipeline's buffers (n = 2048: two id volumes are 128 GiB)"""
             pipe = make_pipeline(kind, eng, frame, rank, world, p2p)
@@ -469,7 +521,8 @@ def main():
                 pipe.voxelize(d_xyz, d_tri, algo=ALGO_TILED)
                 pipe.jfa()
 
-            el, lv, tb = measure(eng, step, steps, warmup, barrier)
+            el, lv = measure(eng, step, steps, warmup, barrier)
+            tb = table_steps(eng, step, barrier) if table else {}
             t = torch.tensor([el], dtype=torch.float64, device=eng.device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             w = pipe.words if pipe.words.numel() == pipe.frame.words else pipe.words[pipe.z0 * pw:pipe.z1 * pw]
@@ -484,7 +537,7 @@ def main():
             return [bool(torch.equal(w, ref_words[z0 * pw:z1 * pw])),
                     bool(torch.equal(s_.view(torch.int32), ref_sdf[z0 * pv:z1 * pv].view(torch.int32)))]
 
-        elapsed, live, table, pipe_report, got = run_pipeline(args.multi, args.steps, args.warmup)
+        elapsed, live, table, pipe_report, got = run_pipeline(args.multi, args.steps, args.warmup, table=args.full)
         pipe_desc = pipe_report.pop("describe")
         planes = n // world
         regs = pipe_report.pop("regions")
@@ -550,7 +603,8 @@ def main():
                     "report_rank0": a_rep,
                     "kernels_ms_per_step_rank0": {k: round(v["ms"] / TABLE_STEPS, 4) for k, v in a_table.items()}}
 
-    peak = copy_peak(eng) if (world == 1 and not args.no_copy_peak) else None
+    peak = copy_peak(eng) if (world == 1 and args.full and not args.no_copy_peak) else None
+    extra = world == 1 and n == N_GRID and args.full          # the [full] blocks of the default size
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = n ** 3 / (elapsed / args.steps) / 1e6
@@ -593,8 +647,8 @@ def main():
                          "formulation_floor_source": fl.get("source") if fl.get("n%d" % n) else None,
                          # which round's files the quoted (not live) figures of this object come from
                          "quoted_from": {"profiles/formulation_floor.json": "round %s" % fl.get("round", "?"), "profiles/jfa_dense_traffic.json": "round %s" % tj.get("round", "?")},
-                         "timing": "hipEvents on the kernel's stream around each of its launches inside the timed region; the other "
-                                   "kernels of `kernels` are timed over %d further steps outside it" % TABLE_STEPS,
+                         "timing": "hipEvents on the kernel's stream around each of its launches inside the timed region" + (
+                                   "; the other kernels of `kernels` are timed over %d further steps outside it" % TABLE_STEPS if table else ""),
                          "note": "bytes = 2*S*n^2*planes (SURVEY.md 8(d)); 27 exact candidate evaluations per voxel (DESIGN.md section 4)"},
             "kernels": kernels,
             "kernels_ms_per_step": {k: v["ms_per_step"] for k, v in kernels.items()},
@@ -605,12 +659,15 @@ def main():
             out["multi"] = pipe_report
             out["parity_ok"] = parity["parity_ok"]
             out["parity"] = parity
-        if world == 1 and n == N_GRID and not args.no_n1024:
+        if extra and not args.no_n1024:
             # the north star's roofline target lives at n = 1024: same mesh, JFA only is what differs in cost per voxel
             n2 = 1024
             o2, v2 = M.frame([xyz], n2)
             f2 = Frame.make(n2, v2, o2)
-            e2, l2, t2 = run_single(eng, f2, d_xyz, d_tri, 3, 1, ALGO_TILED)
+            s2 = single_step(eng, f2, d_xyz, d_tri, ALGO_TILED)[0]
+            e2, l2 = measure(eng, s2, 3, 1, torch.cuda.synchronize)
+            t2 = table_steps(eng, s2, torch.cuda.synchronize)
+            del s2
             k2 = merge_tables(l2, 3, t2, kernel_bytes(n2, n2, eng.ctx.jfa_state_bytes(f2, ALGO_TILED), int(tri.shape[0]), int(xyz.shape[0])))
             jfa_ms = sum(v["ms_per_step"] for k, v in k2.items() if k.startswith("jfa_") or k == "surface")
             jfa_bytes = sum(v["bytes"] * v["launches_per_step"] for k, v in k2.items() if k.startswith("jfa_") or k == "surface")
@@ -637,18 +694,18 @@ def main():
             out["roofline"]["n1024"] = {"achieved": kd2.get("GB/s"), "avg_launch_ms": kd2.get("avg_ms"), "bytes_per_launch": kd2.get("bytes"),
                                         "jfa_all_passes_frac": out["n1024"]["jfa_frac_of_peak"], "target_frac": 0.70,
                                         "formulation_floor_frac": (fl.get("n1024") or {}).get("formulation_floor_frac")}
-        if world == 1 and n == N_GRID and not args.no_config3:
+        if extra and not args.no_config3:
             out["config3"] = run_config3(eng)
             if "csg_words" in out["config3"]["kernels"]:
                 out["kernels"]["csg_words"] = dict(out["config3"]["kernels"]["csg_words"], measured_in="config3 (the headline step has no CSG)")
-        if world == 1 and n == N_GRID and not args.no_config3:
+        if extra and not args.no_config3:
             out["vox_large_triangles"] = run_large_triangles(eng)
-        if world == 1 and n == N_GRID and not args.no_host_totals:
+        if extra and not args.no_host_totals:
             out["totals_incl_transfers"] = host_totals(eng, frame, xyz, tri, ALGO_TILED)
             out["totals_incl_transfers_ms"] = out["totals_incl_transfers"]["total_ms"]
-        if world == 1 and not args.no_cpu_baseline and n == N_GRID:
+        if extra and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(xyz, tri, origin, vs, n)
-    if world > 1:
+    if world > 1 and args.full:
         # The other pipelines run under a watchdog: a transport that HANGS on hardware the build never saw (a collective that never completes
         # cannot be cancelled) must not take the timed pipeline's line with it.  After VP_BENCH_ALT_TIMEOUT seconds (default 180, per
         # pipeline) rank 0 prints the line it already has, with the time-out recorded in that pipeline's object, and every rank leaves.
@@ -702,8 +759,12 @@ def main():
             finished[0] = True
         timer.cancel()
         dist.destroy_process_group()
-    elif rank == 0:
-        emit(out)
+    else:
+        if rank == 0:
+            emit(out)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
 
     bad = parity is not None and not (parity["parity_ok"] and alts_ok)
     if bad:

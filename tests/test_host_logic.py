@@ -120,3 +120,11 @@ def test_bench_argument_surface():
     a = mod.parse_args(["--gpus", "4", "--steps", "7", "--warmup", "2", "--grid-n", "1024"])
     assert (a.gpus, a.steps, a.warmup, a.n, a.multi) == (4, 7, 2, 1024, "ghost")
     assert mod.parse_args([]).gpus == 1 and mod.parse_args(["--n", "2048"]).n == 2048
+    # a plain run measures the headline only; --full adds the rest, --dump-outputs (one GPU) the last step's outputs
+    d = mod.parse_args([])
+    assert d.full is False and d.dump_outputs is None
+    a = mod.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "out"]):
+        with pytest.raises(SystemExit):
+            mod.parse_args(bad)

@@ -490,7 +490,7 @@ def test_bench_multi_process_launch_on_shared_gpu(world, multi):
         port = s.getsockname()[1]
     env = dict(os.environ, VP_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--grid-n", "256", "--multi", multi]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--grid-n", "256", "--multi", multi, "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -534,7 +534,7 @@ def test_bench_bare_invocation_launches_its_own_ranks(world):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["VP_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--grid-n", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--grid-n", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -547,6 +547,43 @@ def test_bench_bare_invocation_launches_its_own_ranks(world):
         assert out["multi_alt_halo"]["parity_ok"] is True and out["multi_alt_transpose_p2p"]["parity_ok"] is True
 
 
+def test_bench_plain_run_dumps_the_outputs_of_its_last_step(engine, tmp_path):
+    """`bench.py --gpus 1` without --full times the step and measures nothing else; --dump-outputs writes what the last timed step handed
+    its caller as float arrays (sdf and occupancy at a seeded sample of voxels, set voxels per z plane), 64 MiB at most -- equal to the
+    same step run in this process."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, d = 256, tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--grid-n", str(n), "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith('{"metric"'), r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0 and out["unit"] == "Mvoxels/s" and out["dtype"] == "f32"
+    assert not {"copy_peak", "n1024", "config3", "vox_large_triangles", "totals_incl_transfers", "cpu_baseline"} & set(out)
+    assert set(out["kernels"]) == {"jfa_dense"} and out["roofline"]["launches"] > 0
+    names = sorted(os.listdir(d))
+    assert names == ["sample_index.npy", "sdf_sample.npy", "solid_per_plane.npy", "solid_sample.npy"]
+    assert sum(os.path.getsize(d / f) for f in names) <= 64 << 20
+    got = {f[:-4]: np.load(d / f) for f in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    idx = got["sample_index"].astype(np.int64)
+    assert idx.size == 1 << 21 and np.all(np.diff(idx) > 0) and idx[-1] < n ** 3
+    xyz, tri = M.bunny(24)
+    origin, vs = M.frame([xyz], n)
+    fr = Frame.make(n, vs, origin)
+    dx, dt = engine.mesh_to_device(xyz, tri)
+    g = engine.voxelize(fr, dx, dt, algo=ALGO_TILED)
+    sdf = engine.jfa(fr, g, algo=ALGO_TILED)
+    engine.sync()
+    occ = np.unpackbits(engine.words_to_numpy(g).view(np.uint8), bitorder="little")
+    assert np.array_equal(got["solid_sample"], occ[idx].astype(np.float32))
+    assert np.array_equal(got["solid_per_plane"], occ.reshape(n, -1).sum(1).astype(np.float64))
+    assert np.array_equal(got["sdf_sample"].view(np.uint32), sdf.cpu().numpy()[idx].view(np.uint32))
+    del g, sdf, dx, dt
+
+
 def test_bench_other_transport_hang_does_not_take_the_line_with_it():
     """bench.py runs the second transport of an N > 1 job under a watchdog: a transport that never returns (first contact with
     hardware the build never saw) must leave the timed pipeline's line and parity intact.  A limit of 1 ms stands in for the hang."""
@@ -557,7 +594,7 @@ def test_bench_other_transport_hang_does_not_take_the_line_with_it():
         port = s.getsockname()[1]
     env = dict(os.environ, VP_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1", VP_BENCH_ALT_TIMEOUT="0.001")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--grid-n", "256"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--grid-n", "256", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     # exit code 2: the timed pipeline's line stands, but a status check must see that a transport never came back
     assert r.returncode != 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -9,7 +9,7 @@ timeout 600 python tools/ab_step.py --n 512 --libs $libs 2>&1 | grep -v amdgpu.i
 timeout 900 python tools/ab_step.py --n 1024 --rounds 5 --libs $libs 2>&1 | grep -v amdgpu.ids > $O/ab_1024.txt
 if [ "$3" = "2048" ]; then
   for v in $(echo $2 | tr ',' ' '); do
-    VPHIP_LIB=$R/tools/exp/libvphip_$v.so timeout 900 python bench.py --grid-n 2048 --steps 4 --warmup 1 --no-cpu-baseline > $O/n2048_$v.json 2> $O/n2048_$v.err
+    VPHIP_LIB=$R/tools/exp/libvphip_$v.so timeout 900 python bench.py --full --grid-n 2048 --steps 4 --warmup 1 --no-cpu-baseline > $O/n2048_$v.json 2> $O/n2048_$v.err
   done
 fi
 cat $O/ab_512.txt $O/ab_1024.txt

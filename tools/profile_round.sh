@@ -9,10 +9,10 @@ O=$R/gpurun_out/$round
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. kernel trace of the bench command itself (n = 512 headline + its n = 1024 block), then the same command un-profiled
-timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
+timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
 grep '^{"metric"' $O/bench_under_rocprof.log > $O/bench_under_rocprof.json
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv 2>/dev/null
-python3 $R/bench.py > $O/bench_unprofiled.json 2> $O/bench_unprofiled.err
+python3 $R/bench.py --full > $O/bench_unprofiled.json 2> $O/bench_unprofiled.err
 pmc() {  # size, name, counters...
   local n=$1 name=$2; shift 2
   timeout -k 5 250 rocprofv3 --pmc "$@" --output-format csv -d $O/pmc_${name}_n$n -- python3 $R/tools/run_passes.py $n 1 > $O/pmc_${name}_n$n.log 2>&1
@@ -30,8 +30,8 @@ python3 $R/tools/traffic_json.py $O > $O/jfa_dense_traffic.json 2> $O/traffic_js
 rm -rf $O/stats $O/pmc_*/ $O/*.log
 ls $O
 # round 4: the other two sizes, the n = 2048 byte counters, the probes
-python3 $R/bench.py --grid-n 1024 --no-cpu-baseline > $O/bench_n1024.json 2> $O/bench_n1024.err
-python3 $R/bench.py --grid-n 2048 --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_n2048.json 2> $O/bench_n2048.err
+python3 $R/bench.py --full --grid-n 1024 --no-cpu-baseline > $O/bench_n1024.json 2> $O/bench_n1024.err
+python3 $R/bench.py --full --grid-n 2048 --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_n2048.json 2> $O/bench_n2048.err
 pmc 2048 fetch FETCH_SIZE
 pmc 2048 write WRITE_SIZE
 pmc 2048 sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY
