@@ -18,6 +18,10 @@
 //                            apps/cli/main.cpp:22-23); --multi ghost|halo|hybrid|transpose picks the JFA variant (vphip.h, vp_multi_jfa)
 //         --verify           (extension, with -g G > 1) run the job once more on device 0 alone and compare grid and sdf bit for
 //                            bit; prints "# multi-gpu ..." lines (parity, device-to-device bytes of the JFA), exit code 3 on a mismatch
+//         --conservative     (extension) replace the voxelization of every input mesh by the conservative SURFACE voxelization:
+//                            a voxel is set iff its closed box overlaps a triangle (include/vphip.h, vp_voxelize_conservative) -- a
+//                            correct grid for open meshes and triangle soups, where the solid rule streaks; -p, -e, --surface-only,
+//                            -s, -m and -d work on it unchanged.  One device only (-g > 1 is refused)
 //     -h, --help
 #include <cmath>
 #include <cstdint>
@@ -62,6 +66,7 @@ struct Options {
     std::string multi = "ghost";
     bool verify = false;
     bool surfaceOnly = false;
+    bool conservative = false;
     bool help = false;
 };
 
@@ -90,6 +95,9 @@ const char* kUsage =
     "                        (default: the reference's mesh -- every face of every set voxel once, interior faces included)\n"
     "      --verify          With -g > 1: run the job again on device 0 alone, compare grid and sdf bit for bit, print\n"
     "                        '# multi-gpu' lines (parity, bytes moved between devices); exit code 3 on a mismatch (extension)\n"
+    "      --conservative    Surface voxelization: a voxel is set iff its closed box overlaps a triangle (any mesh, open or\n"
+    "                        closed; the default solid rule needs closed meshes); CSG, export, sdf and dumps work on it unchanged.\n"
+    "                        One device only: not with -g > 1 (extension)\n"
     "  -h, --help            Print usage\n";
 
 // Minimal getopt-style parser: -x V, -xV, --long V, --long=V, boolean switches, positionals.
@@ -97,7 +105,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -118,10 +126,10 @@ Options Parse(int argc, char** argv)
             o.filenames.push_back(a);
             continue;
         }
-        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S';
+        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C';
         if (isSwitch) {
             const bool v = !hasValue || value == "true" || value == "1";
-            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else o.help = v;
+            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else o.help = v;
             continue;
         }
         if (!hasValue) {
@@ -150,6 +158,12 @@ void Voxelize(unsigned blockSize, HostVoxelsGrid<gridType>& grid, const Mesh& me
 {
     if constexpr (T == Types::TILED) VOX::Compute<Types::TILED>(blockSize, grid, mesh);
     else VOX::Compute<T>(grid, mesh);
+}
+
+template <Types T>
+void VoxelizeConservative(unsigned blockSize, HostVoxelsGrid<gridType>& grid, const Mesh& mesh)
+{
+    VOX::ComputeConservative<T>(blockSize, grid, mesh);
 }
 
 template <Types T>
@@ -202,6 +216,7 @@ int main(int argc, char** argv)
     const bool EXPORT = !BENCHMARK && opt.doExport;
     const bool GPU = TYPE == Types::NAIVE || TYPE == Types::TILED;      // exports: the walk over the grid runs on the device too
     cpuAssert(opt.gpus >= 1 && opt.gpus <= 64, "Number of GPUs must be 1..64");
+    cpuAssert(!(opt.conservative && opt.gpus > 1), "--conservative runs on one device: -g must be 1\n");
     cpuAssert(opt.multi == "ghost" || opt.multi == "halo" || opt.multi == "hybrid" || opt.multi == "transpose", "--multi must be ghost, halo, hybrid or transpose");
     if (GPU && opt.gpus > 1) {
         // Z-slabs over devices 0 .. G-1.  VPLIB_SHARE_GPU=1 (test rigs with fewer devices than slabs): the slabs share the devices
@@ -244,11 +259,20 @@ int main(int argc, char** argv)
             HostVoxelsGrid<gridType>& grid = grids[i];
             grid = HostVoxelsGrid<gridType>(N, voxelSize);
             grid.View().SetOrigin(originX, originY, originZ);
-            switch (TYPE) {
-                case Types::SEQUENTIAL:
-                case Types::OPENMP: Voxelize<Types::SEQUENTIAL>(opt.blockSize, grid, meshes[i]); break;   // main.cpp:99-103
-                case Types::NAIVE:  Voxelize<Types::NAIVE>(opt.blockSize, grid, meshes[i]); break;
-                case Types::TILED:  Voxelize<Types::TILED>(opt.blockSize, grid, meshes[i]); break;
+            if (opt.conservative) {
+                switch (TYPE) {
+                    case Types::SEQUENTIAL: VoxelizeConservative<Types::SEQUENTIAL>(opt.blockSize, grid, meshes[i]); break;
+                    case Types::OPENMP:     VoxelizeConservative<Types::OPENMP>(opt.blockSize, grid, meshes[i]); break;
+                    case Types::NAIVE:      VoxelizeConservative<Types::NAIVE>(opt.blockSize, grid, meshes[i]); break;
+                    case Types::TILED:      VoxelizeConservative<Types::TILED>(opt.blockSize, grid, meshes[i]); break;
+                }
+            } else {
+                switch (TYPE) {
+                    case Types::SEQUENTIAL:
+                    case Types::OPENMP: Voxelize<Types::SEQUENTIAL>(opt.blockSize, grid, meshes[i]); break;   // main.cpp:99-103
+                    case Types::NAIVE:  Voxelize<Types::NAIVE>(opt.blockSize, grid, meshes[i]); break;
+                    case Types::TILED:  Voxelize<Types::TILED>(opt.blockSize, grid, meshes[i]); break;
+                }
             }
             if (EXPORT) {                                                                               // main.cpp:118-124
                 Mesh outMesh;

@@ -17,7 +17,8 @@ EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
 MULTI_HALO, MULTI_GHOST, MULTI_HYBRID, MULTI_TRANSPOSE = 0, 1, 2, 3
 
 KERNELS = ["vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
-           "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal"]
+           "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
+           "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive"]
 JFA_PASS_KEYS = ("jfa_pass", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last")
 
 # every symbol include/vphip.h declares (tests check the library exports all of them)
@@ -34,6 +35,7 @@ SYMBOLS = [
     "vp_prof_enable", "vp_prof_select", "vp_prof_reset", "vp_prof_get", "vp_prof_name",
     "vp_multi_create", "vp_multi_destroy", "vp_multi_count", "vp_multi_ctx", "vp_multi_sync", "vp_multi_set_mesh", "vp_multi_voxelize",
     "vp_multi_set_grid", "vp_multi_get_grid", "vp_multi_csg", "vp_multi_jfa", "vp_multi_get_sdf", "vp_multi_bytes_moved", "vp_multi_window",
+    "vp_voxelize_conservative", "vp_voxelize_conservative_host",
 ]
 
 
@@ -130,6 +132,8 @@ def lib():
         "vp_grid_words": (_sz, [fp]),
         "vp_grid_voxels": (_sz, [fp]),
         "vp_voxelize": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int]),
+        "vp_voxelize_conservative": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int]),
+        "vp_voxelize_conservative_host": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -243,6 +247,12 @@ class Context:
                  algo: int = ALGO_TILED, accumulate: bool = False):
         check(lib().vp_voxelize(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_xyz), nverts, _vp(d_tri), ntris,
                                 algo, 1 if accumulate else 0))
+
+    def voxelize_conservative(self, frame: Frame, d_words: int, d_xyz: int, nverts: int, d_tri: int, ntris: int,
+                              algo: int = ALGO_TILED, accumulate: bool = False):
+        """Conservative surface voxelization (closed voxel box overlaps closed triangle); accumulate ORs into d_words."""
+        check(lib().vp_voxelize_conservative(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_xyz), nverts, _vp(d_tri), ntris,
+                                             algo, 1 if accumulate else 0))
 
     def csg(self, d_a: int, d_b: int, nwords: int, op: int):
         check(lib().vp_csg(self._h, _vp(d_a), _vp(d_b), nwords, op))
@@ -369,6 +379,11 @@ class Context:
         check(lib().vp_voxelize_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp),
                                      h_xyz.ctypes.data_as(_vp), h_xyz.shape[0], h_tri.ctypes.data_as(_vp),
                                      h_tri.shape[0], algo))
+
+    def voxelize_conservative_host(self, frame: Frame, h_words, h_xyz, h_tri, algo: int = ALGO_TILED):
+        check(lib().vp_voxelize_conservative_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp),
+                                                  h_xyz.ctypes.data_as(_vp), h_xyz.shape[0], h_tri.ctypes.data_as(_vp),
+                                                  h_tri.shape[0], algo))
 
     def csg_host(self, h_a, h_b, op: int):
         check(lib().vp_csg_host(self._h, h_a.ctypes.data_as(_vp), h_b.ctypes.data_as(_vp), h_a.size, op))

@@ -129,7 +129,8 @@ static void grid_written(vp_ctx* ctx, const void* d_ptr, size_t bytes)
 
 static const char* kNames[VP_K_COUNT] = {
     "vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
-    "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal"
+    "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
+    "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive"
 };
 
 }  // namespace vp
@@ -176,13 +177,15 @@ int vp_ctx_destroy(vp_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
-                       &ctx->ext_cnt, &ctx->ext_off };
+                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : ctx->prof_pool) (void)hipEventDestroy(e);
     if (ctx->vox_total_event) (void)hipEventDestroy(ctx->vox_total_event);
     if (ctx->vox_total_host) (void)hipHostFree(ctx->vox_total_host);
+    if (ctx->cvox_event) (void)hipEventDestroy(ctx->cvox_event);
+    if (ctx->cvox_host) (void)hipHostFree(ctx->cvox_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -308,6 +311,21 @@ int vp_voxelize(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, const float* 
     if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "vp_voxelize: too many triangles");
     grid_written(ctx, d_words, vp_grid_words(f) * 4);
     return launch_voxelize(ctx, make_frame(f), d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate ? 1 : 0);
+}
+
+int vp_voxelize_conservative(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, const float* d_xyz, size_t nverts,
+                             const uint32_t* d_tri, size_t ntris, int algo, int accumulate)
+{
+    const char* who = "vp_voxelize_conservative";
+    if (!ctx || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_aligned(who, {d_words}));
+    if (ntris && (!d_xyz || !d_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
+    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: algo %d", who, algo);
+    if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "%s: too many triangles", who);
+    grid_written(ctx, d_words, vp_grid_words(f) * 4);
+    return launch_voxelize_conservative(ctx, make_frame(f), d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate ? 1 : 0);
 }
 
 int vp_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op)
@@ -754,6 +772,22 @@ int vp_voxelize_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words, const fl
     VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
     VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
     VP_TRY(vp_voxelize(ctx, f, (uint32_t*)dw, (const float*)dx, nverts, (const uint32_t*)dt, ntris, algo, 0));
+    return vp_download(ctx, h_words, dw, wb);
+}
+
+int vp_voxelize_conservative_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words, const float* h_xyz, size_t nverts,
+                                  const uint32_t* h_tri, size_t ntris, int algo)
+{
+    if (!ctx || !h_words) return set_error(VP_ERR_INVALID, "vp_voxelize_conservative_host: null argument");
+    VP_TRY(check_frame(f, "vp_voxelize_conservative_host", true));
+    void *dw = nullptr, *dx = nullptr, *dt = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nverts * 12, &dx));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
+    VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
+    VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
+    VP_TRY(vp_voxelize_conservative(ctx, f, (uint32_t*)dw, (const float*)dx, nverts, (const uint32_t*)dt, ntris, algo, 0));
     return vp_download(ctx, h_words, dw, wb);
 }
 

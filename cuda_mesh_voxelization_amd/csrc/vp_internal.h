@@ -79,6 +79,12 @@ struct vp_ctx {
     struct VoxJob { const void* tri = nullptr; size_t ntris = 0; uint32_t n = 0, z0 = 0, z1 = 0;
                     bool operator==(const VoxJob& o) const { return tri == o.tri && ntris == o.ntris && n == o.n && z0 == o.z0 && z1 == o.z1; } };
     VoxJob vox_pending_job, vox_nolist_job;
+    // conservative voxelizer (cvox.hip): its own large-triangle counter, record list and row scan, and its own lazily copied count
+    vp::Buffer cvox_cnt, cvox_rec, cvox_base;
+    uint32_t* cvox_host = nullptr;
+    hipEvent_t cvox_event = nullptr;
+    bool cvox_pending = false;
+    uint64_t cvox_nbig_seen = 0;
     // profiling
     bool prof_on = false;
     uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
@@ -140,6 +146,9 @@ inline char* win_bytes_plane(const IdWin& w, uint32_t n, int64_t plane)
 // ---- stage launchers (each enqueues on ctx->stream) ----
 int launch_voxelize(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float* d_xyz, size_t nverts,
                     const uint32_t* d_tri, size_t ntris, int algo, int accumulate);
+// cvox.hip: conservative (26-separating) surface voxelization, OR into d_words (accumulate) or overwrite
+int launch_voxelize_conservative(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float* d_xyz, size_t nverts,
+                                 const uint32_t* d_tri, size_t ntris, int algo, int accumulate);
 int launch_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op);
 int launch_stream_copy(vp_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);   // 16 B per lane: the measured HBM copy rate
 // jfa_seed.hip

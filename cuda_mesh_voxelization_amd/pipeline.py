@@ -53,6 +53,16 @@ class Engine:
                           algo, accumulate)
         return out
 
+    def voxelize_conservative(self, frame: Frame, d_xyz, d_tri, out=None, algo=ALGO_TILED, accumulate=False):
+        """Surface grid: every voxel whose closed box overlaps a triangle (any mesh, open or closed).  accumulate ORs into `out`."""
+        if out is None:
+            out = self.new_grid(frame)
+            if accumulate:
+                out.zero_()
+        self.ctx.voxelize_conservative(frame, out.data_ptr(), d_xyz.data_ptr(), d_xyz.shape[0], d_tri.data_ptr(), d_tri.shape[0],
+                                       algo, accumulate)
+        return out
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

@@ -31,6 +31,9 @@ namespace detail {
 // grid words viewed as uint32 (see voxels_grid.h on why this is layout-neutral)
 void Sequential(uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh);
 void Device(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh);
+// conservative surface voxelization (cvox.cpp): host restatement (ORs into `words`; parallel over z when `parallel`) and the GPU marshalling
+void ConservativeHost(bool parallel, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh);
+void ConservativeDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh);
 }  // namespace detail
 
 template <Types type, VGType T>
@@ -53,6 +56,33 @@ template <Types type, VGType T>
 void Compute(const size_t /*blockSize*/, HostVoxelsGrid<T>& grid, const Mesh& mesh)
 {
     Compute<type, T>(grid, mesh);
+}
+
+// ComputeConservative: the SURFACE grid of any mesh, open or closed -- voxel set iff its closed box overlaps a closed triangle (the
+// 26-separating test of Schwarz & Seidel 2010; the float32 predicate of include/vphip.h, vp_voxelize_conservative).  No reference
+// counterpart: the reference promises surface grids but has only the solid rule above.
+//   SEQUENTIAL / OPENMP   host restatement, ORs into `grid` (OPENMP: parallel over z planes)
+//   NAIVE / TILED         vp_voxelize_conservative_host: replace the grid contents, like the GPU Compute variants
+// Every variant produces the same bits.
+template <Types type, VGType T>
+void ComputeConservative(HostVoxelsGrid<T>& grid, const Mesh& mesh)
+{
+    auto& v = grid.View();
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    uint32_t* words = reinterpret_cast<uint32_t*>(v.Data());
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        detail::ConservativeHost(type == Types::OPENMP, words, v.VoxelsPerSide(), v.VoxelSize(), origin, mesh);
+    else if constexpr (type == Types::NAIVE)
+        detail::ConservativeDevice(VP_ALGO_NAIVE, "NaiveConservativeVox", words, v.VoxelsPerSide(), v.VoxelSize(), origin, mesh);
+    else
+        detail::ConservativeDevice(VP_ALGO_TILED, "TiledConservativeVox", words, v.VoxelsPerSide(), v.VoxelSize(), origin, mesh);
+}
+
+// blockSize: as for Compute, accepted and ignored
+template <Types type, VGType T>
+void ComputeConservative(const size_t /*blockSize*/, HostVoxelsGrid<T>& grid, const Mesh& mesh)
+{
+    ComputeConservative<type, T>(grid, mesh);
 }
 
 }  // namespace VOX

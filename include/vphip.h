@@ -117,6 +117,31 @@ int vp_voxelize(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words,
                 const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,
                 int algo, int accumulate);
 
+/* ---- conservative surface voxelization (no reference counterpart) ---------------------------
+ * The reference promises "solid or surface voxel grids" (README) but has only the solid parity rule above, which needs a closed,
+ * consistently crossed mesh; on an open mesh or a triangle soup its columns streak to the grid edge.  This voxelizer sets voxel
+ * (i, j, k) iff its CLOSED box overlaps the CLOSED triangle (Schwarz & Seidel 2010, section 3.1: the 26-separating test).  In float32,
+ * in this association, without FMA contraction (the contract):
+ *   corner      p.a = o.a + (float)idx * vs
+ *   setup       e0 = v1 - v0, e1 = v2 - v1, e2 = v0 - v2;  nrm = Cross(e0, e1).  A triangle contributes NOTHING if an index is >= nverts,
+ *               a vertex coordinate is not finite, or nrm == (0, 0, 0).
+ *   box         p.a <= max.a && p.a + vs >= min.a on every axis (min / max of the three vertices)
+ *   plane       c.a = nrm.a > 0 ? vs : 0;  d1 = Dot(nrm, c - v0), d2 = Dot(nrm, (vs - c) - v0), Dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ *               t = Dot(nrm, p), s1 = t + d1, s2 = t + d2; the voxel fails if (s1 > 0 && s2 > 0) || (s1 < 0 && s2 < 0)
+ *   projections (u, v) = (x, y), (y, z), (z, x) with sigma = (nrm.z, nrm.x, nrm.y) >= 0 ? 1 : -1; for each edge e_i starting at v_i:
+ *               ne = (-e_i.v * sigma, e_i.u * sigma), de = ((-(ne.u v_i.u + ne.v v_i.v)) + max(0, vs ne.u)) + max(0, vs ne.v)
+ *               (max(0, x) = x > 0 ? x : 0); the voxel passes iff (ne.u p.u + ne.v p.v) + de >= 0 for all nine
+ * accumulate = 0: d_words is overwritten (zero-fill, then OR); 1: OR into the existing words (a union -- not the XOR of vp_voxelize).
+ * Slab frames are served: a slab's words are those planes of the whole-grid result.  Argument checks as vp_voxelize.
+ * VP_ALGO_NAIVE: one thread per triangle, one atomicOr per set voxel.  VP_ALGO_TILED: small triangles rasterised by their setup
+ * thread (one atomicOr per touched word), the rows of large ones dealt to lanes over the whole device.  Same bits.
+ * Asynchronous in steady state; the first call, and any call that needs a larger large-triangle list than the context has (grow-only,
+ * 64 Ki records of 176 B or what earlier calls counted + 25 %, a large triangle that finds it full is walked in place), synchronises
+ * and allocates. */
+int vp_voxelize_conservative(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words,
+                             const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,
+                             int algo, int accumulate);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
@@ -343,6 +368,9 @@ int vp_voxelize_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words,
 int vp_csg_host(vp_ctx* ctx, uint32_t* h_a, const uint32_t* h_b, size_t nwords, int op);
 int vp_jfa_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, float fill_unset,
                 float* h_sdf, int algo);
+/* vp_voxelize_conservative with the convention above (whole-grid frame, overwrite) */
+int vp_voxelize_conservative_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words,
+                                  const float* h_xyz, size_t nverts, const uint32_t* h_tri, size_t ntris, int algo);
 
 /* ---- per-kernel timing (PROFILING_SCOPE equivalent for device time, vplib/src/profiling.h:8-33)
  * When enabled, every kernel launch is bracketed by hipEvents on the context's stream. */
@@ -359,6 +387,12 @@ enum {
     VP_K_EXTRACT,       /* vp_extract_count / vp_extract: 2 n^3/8 + records */
     VP_K_VOX_ZERO,      /* the voxelizer's zero-fill of the toggle grid (+ the tile histogram): n^3/8 */
     VP_K_JFA_REDEAL,    /* vp_jfa_window_interleave: 2 S x the planes woven */
+    /* vp_voxelize_conservative: */
+    VP_K_CVOX_ZERO,     /* zero-fill of the grid (overwrite) and of the large-triangle counter: n^3/8 */
+    VP_K_CVOX_SETUP,    /* TILED: triangle setup, small triangles rasterised */
+    VP_K_CVOX_SCAN,     /* TILED: row scan of the large-triangle list */
+    VP_K_CVOX_ROWS,     /* TILED: the rows of the large triangles */
+    VP_K_CVOX_NAIVE,    /* NAIVE: one thread per triangle */
     VP_K_COUNT
 };
 int vp_prof_enable(vp_ctx* ctx, int on);
