@@ -274,3 +274,46 @@ def test_open_mesh_does_not_streak():
     whole = to_bits(cvox_numpy(xyz, tri, n, vs, origin), n)
     part = to_bits(cvox_numpy(xyz, open_sphere()[1], n, vs, origin), n)
     assert part.any() and not (part & ~whole).any()
+
+
+# ---- the restatement against an exact reference (tests/cvox_exact.py) ------------------------------------------------------
+EXACT_FRAMES = [(1.0, (0.0, 0.0, 0.0)), (2.0 ** -3, (-2.5, 0.75, 3.0)), (2.0 ** -6, (1.5, -0.25, 0.125))]
+
+
+@pytest.mark.parametrize("n,E", [(32, 5), (48, 7), (64, 6), (64, 12)])
+@pytest.mark.parametrize("frame", range(len(EXACT_FRAMES)))
+def test_restatement_equals_the_exact_reference(n, E, frame):
+    """Every exact family (tests/cvox_exact.py), one triangle per cell with >= 2 empty voxels between candidate boxes, border cells
+    touching or crossing the grid's outer planes: where float32 is exact (checked first), the contract's formula IS the closed-box
+    test, bit for bit"""
+    import cvox_exact as X
+    vs, origin = EXACT_FRAMES[frame]
+    cells = X.cells_per_call(n, E)
+    for seed in range(3):
+        local, _ = X.families(1000 * n + 10 * E + seed, max(4, cells // len(X.FAMILIES) + 1), E)
+        H = X.pack(local[np.random.default_rng(seed).permutation(len(local))], n, E, seed=seed)
+        X.exact_budget(H, vs, origin, n)
+        exp = X.sat_overlap(H, n)
+        xyz = X.world(H, vs, origin).reshape(-1, 3)
+        got = to_bits(cvox_numpy(xyz, np.arange(len(xyz)).reshape(-1, 3), n, vs, origin), n)
+        assert exp.any()
+        assert np.array_equal(got, exp), X.describe(H, exp, got, n)
+
+
+def test_exact_families_touch_boxes_only_on_their_boundary():
+    """the families are made of closed contacts: the closed-box grid differs from the open-box one (boxes shrunk by 1e-6), and on
+    every family; the float64 test agrees with _tri_box_overlap voxel by voxel"""
+    import cvox_exact as X
+    n, E = 48, 7
+    for name in X.FAMILIES:
+        local, _ = X.families(5, 40, E, names=[name])
+        H = X.pack(local, n, E, seed=1, border=False)
+        closed = X.sat_overlap(H, n)
+        assert np.array_equal(closed, X.overlap_f64(H.astype(np.float64) / 2, 1.0, (0, 0, 0), n, 0.0)), name
+        opened = X.overlap_f64(H.astype(np.float64) / 2, 1.0, (0, 0, 0), n, -1e-6)
+        assert (opened & ~closed).sum() == 0 and (closed & ~opened).sum() > 0, name
+    v = H.astype(np.float64) / 2
+    rng = np.random.default_rng(2)
+    for z, y, x in np.argwhere(np.ones((n, n, n), bool))[rng.choice(n ** 3, 3000, replace=False)]:
+        c = np.array([x, y, z], np.float64) + 0.5
+        assert bool(closed[z, y, x]) == bool(_tri_box_overlap(v, c, 0.5).any()), (x, y, z)
