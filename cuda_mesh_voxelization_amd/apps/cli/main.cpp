@@ -22,6 +22,10 @@
 //                            a voxel is set iff its closed box overlaps a triangle (include/vphip.h, vp_voxelize_conservative) -- a
 //                            correct grid for open meshes and triangle soups, where the solid rule streaks; -p, -e, --surface-only,
 //                            -s, -m and -d work on it unchanged.  One device only (-g > 1 is refused)
+//         --fill             (extension) after each mesh's voxelization (solid or --conservative), fill its interior: every empty voxel
+//                            that no 6-connected path of empty voxels joins to the grid boundary is set (include/vphip.h,
+//                            vp_fill_interior).  Runs before export, CSG and sdf, so --conservative --fill gives the solid of an open
+//                            mesh or soup whose holes are smaller than a voxel.  One device only (-g > 1 is refused)
 //     -h, --help
 #include <cmath>
 #include <cstdint>
@@ -67,6 +71,7 @@ struct Options {
     bool verify = false;
     bool surfaceOnly = false;
     bool conservative = false;
+    bool fill = false;
     bool help = false;
 };
 
@@ -98,6 +103,9 @@ const char* kUsage =
     "      --conservative    Surface voxelization: a voxel is set iff its closed box overlaps a triangle (any mesh, open or\n"
     "                        closed; the default solid rule needs closed meshes); CSG, export, sdf and dumps work on it unchanged.\n"
     "                        One device only: not with -g > 1 (extension)\n"
+    "      --fill            After each voxelization, set every empty voxel the grid boundary cannot reach through face-adjacent\n"
+    "                        empty voxels (interior fill: a solid from a --conservative grid); before export, CSG and sdf.\n"
+    "                        One device only: not with -g > 1 (extension)\n"
     "  -h, --help            Print usage\n";
 
 // Minimal getopt-style parser: -x V, -xV, --long V, --long=V, boolean switches, positionals.
@@ -105,7 +113,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -126,10 +134,10 @@ Options Parse(int argc, char** argv)
             o.filenames.push_back(a);
             continue;
         }
-        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C';
+        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F';
         if (isSwitch) {
             const bool v = !hasValue || value == "true" || value == "1";
-            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else o.help = v;
+            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else o.help = v;
             continue;
         }
         if (!hasValue) {
@@ -217,6 +225,7 @@ int main(int argc, char** argv)
     const bool GPU = TYPE == Types::NAIVE || TYPE == Types::TILED;      // exports: the walk over the grid runs on the device too
     cpuAssert(opt.gpus >= 1 && opt.gpus <= 64, "Number of GPUs must be 1..64");
     cpuAssert(!(opt.conservative && opt.gpus > 1), "--conservative runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
     cpuAssert(opt.multi == "ghost" || opt.multi == "halo" || opt.multi == "hybrid" || opt.multi == "transpose", "--multi must be ghost, halo, hybrid or transpose");
     if (GPU && opt.gpus > 1) {
         // Z-slabs over devices 0 .. G-1.  VPLIB_SHARE_GPU=1 (test rigs with fewer devices than slabs): the slabs share the devices
@@ -272,6 +281,14 @@ int main(int argc, char** argv)
                     case Types::OPENMP: Voxelize<Types::SEQUENTIAL>(opt.blockSize, grid, meshes[i]); break;   // main.cpp:99-103
                     case Types::NAIVE:  Voxelize<Types::NAIVE>(opt.blockSize, grid, meshes[i]); break;
                     case Types::TILED:  Voxelize<Types::TILED>(opt.blockSize, grid, meshes[i]); break;
+                }
+            }
+            if (opt.fill) {
+                switch (TYPE) {
+                    case Types::SEQUENTIAL: VOX::FillInterior<Types::SEQUENTIAL>(grid); break;
+                    case Types::OPENMP:     VOX::FillInterior<Types::OPENMP>(grid); break;
+                    case Types::NAIVE:      VOX::FillInterior<Types::NAIVE>(grid); break;
+                    case Types::TILED:      VOX::FillInterior<Types::TILED>(grid); break;
                 }
             }
             if (EXPORT) {                                                                               // main.cpp:118-124

@@ -18,7 +18,8 @@ MULTI_HALO, MULTI_GHOST, MULTI_HYBRID, MULTI_TRANSPOSE = 0, 1, 2, 3
 
 KERNELS = ["vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
            "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
-           "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive"]
+           "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
+           "fill_x", "fill_y", "fill_z", "fill_final"]
 JFA_PASS_KEYS = ("jfa_pass", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last")
 
 # every symbol include/vphip.h declares (tests check the library exports all of them)
@@ -36,6 +37,7 @@ SYMBOLS = [
     "vp_multi_create", "vp_multi_destroy", "vp_multi_count", "vp_multi_ctx", "vp_multi_sync", "vp_multi_set_mesh", "vp_multi_voxelize",
     "vp_multi_set_grid", "vp_multi_get_grid", "vp_multi_csg", "vp_multi_jfa", "vp_multi_get_sdf", "vp_multi_bytes_moved", "vp_multi_window",
     "vp_voxelize_conservative", "vp_voxelize_conservative_host",
+    "vp_fill_interior", "vp_fill_interior_host",
 ]
 
 
@@ -134,6 +136,8 @@ def lib():
         "vp_voxelize": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int]),
         "vp_voxelize_conservative": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int]),
         "vp_voxelize_conservative_host": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int]),
+        "vp_fill_interior": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_fill_interior_host": (ctypes.c_int, [_vp, fp, _vp, _vp]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -253,6 +257,13 @@ class Context:
         """Conservative surface voxelization (closed voxel box overlaps closed triangle); accumulate ORs into d_words."""
         check(lib().vp_voxelize_conservative(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_xyz), nverts, _vp(d_tri), ntris,
                                              algo, 1 if accumulate else 0))
+
+    def fill_interior(self, frame: Frame, d_words: int, d_out: int) -> int:
+        """Interior fill (6-connected exterior flood from the grid boundary): d_out = d_words plus every enclosed empty voxel.
+        Blocking; returns the number of propagation rounds that ran."""
+        rounds = ctypes.c_uint32(0)
+        check(lib().vp_fill_interior(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), ctypes.byref(rounds)))
+        return rounds.value
 
     def csg(self, d_a: int, d_b: int, nwords: int, op: int):
         check(lib().vp_csg(self._h, _vp(d_a), _vp(d_b), nwords, op))
@@ -384,6 +395,9 @@ class Context:
         check(lib().vp_voxelize_conservative_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp),
                                                   h_xyz.ctypes.data_as(_vp), h_xyz.shape[0], h_tri.ctypes.data_as(_vp),
                                                   h_tri.shape[0], algo))
+
+    def fill_interior_host(self, frame: Frame, h_words, h_out):
+        check(lib().vp_fill_interior_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp)))
 
     def csg_host(self, h_a, h_b, op: int):
         check(lib().vp_csg_host(self._h, h_a.ctypes.data_as(_vp), h_b.ctypes.data_as(_vp), h_a.size, op))

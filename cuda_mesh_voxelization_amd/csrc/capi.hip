@@ -130,7 +130,8 @@ static void grid_written(vp_ctx* ctx, const void* d_ptr, size_t bytes)
 static const char* kNames[VP_K_COUNT] = {
     "vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
     "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
-    "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive"
+    "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
+    "fill_x", "fill_y", "fill_z", "fill_final"
 };
 
 }  // namespace vp
@@ -177,7 +178,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
-                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base };
+                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -186,6 +187,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->vox_total_host) (void)hipHostFree(ctx->vox_total_host);
     if (ctx->cvox_event) (void)hipEventDestroy(ctx->cvox_event);
     if (ctx->cvox_host) (void)hipHostFree(ctx->cvox_host);
+    if (ctx->fill_host) (void)hipHostFree(ctx->fill_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -326,6 +328,20 @@ int vp_voxelize_conservative(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, 
     if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "%s: too many triangles", who);
     grid_written(ctx, d_words, vp_grid_words(f) * 4);
     return launch_voxelize_conservative(ctx, make_frame(f), d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate ? 1 : 0);
+}
+
+int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds)
+{
+    const char* who = "vp_fill_interior";
+    if (!ctx || !d_words || !d_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_frame(f, who, false));
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    VP_TRY(check_aligned(who, {d_words, d_out}));
+    const size_t bytes = vp_grid_words(f) * 4;
+    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    grid_written(ctx, d_out, bytes);
+    return launch_fill_interior(ctx, f->n, d_words, d_out, h_rounds);
 }
 
 int vp_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op)
@@ -789,6 +805,21 @@ int vp_voxelize_conservative_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_wo
     VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
     VP_TRY(vp_voxelize_conservative(ctx, f, (uint32_t*)dw, (const float*)dx, nverts, (const uint32_t*)dt, ntris, algo, 0));
     return vp_download(ctx, h_words, dw, wb);
+}
+
+int vp_fill_interior_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out)
+{
+    const char* who = "vp_fill_interior_host";
+    if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_frame(f, who, false));
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    void *da = nullptr, *db = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
+    VP_TRY(vp_upload(ctx, da, h_words, wb));
+    VP_TRY(vp_fill_interior(ctx, f, (const uint32_t*)da, (uint32_t*)db, nullptr));
+    return vp_download(ctx, h_out, db, wb);
 }
 
 int vp_csg_host(vp_ctx* ctx, uint32_t* h_a, const uint32_t* h_b, size_t nwords, int op)

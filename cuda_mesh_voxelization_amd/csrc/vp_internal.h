@@ -85,6 +85,9 @@ struct vp_ctx {
     hipEvent_t cvox_event = nullptr;
     bool cvox_pending = false;
     uint64_t cvox_nbig_seen = 0;
+    // interior fill (fill.hip): the ring of round flags (two batches) and its pinned host copy of one batch
+    vp::Buffer fill_flags;
+    uint32_t* fill_host = nullptr;
     // profiling
     bool prof_on = false;
     uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
@@ -149,6 +152,8 @@ int launch_voxelize(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float*
 // cvox.hip: conservative (26-separating) surface voxelization, OR into d_words (accumulate) or overwrite
 int launch_voxelize_conservative(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float* d_xyz, size_t nverts,
                                  const uint32_t* d_tri, size_t ntris, int algo, int accumulate);
+// fill.hip: interior fill of a whole grid, d_out = NOT exterior(d_words); blocking (reads the round flags back once per batch)
+int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds);
 int launch_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op);
 int launch_stream_copy(vp_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);   // 16 B per lane: the measured HBM copy rate
 // jfa_seed.hip

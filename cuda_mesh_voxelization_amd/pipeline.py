@@ -63,6 +63,14 @@ class Engine:
                                        algo, accumulate)
         return out
 
+    def fill_interior(self, frame: Frame, words, out=None):
+        """Solid from any grid: `words` plus every empty voxel that no 6-connected path of empty voxels joins to the grid boundary.
+        Blocking; returns (out, rounds)."""
+        if out is None:
+            out = self.new_grid(frame)
+        rounds = self.ctx.fill_interior(frame, words.data_ptr(), out.data_ptr())
+        return out, rounds
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

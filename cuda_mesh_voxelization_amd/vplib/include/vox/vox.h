@@ -34,6 +34,9 @@ void Device(int algo, const char* label, uint32_t* words, size_t n, float voxelS
 // conservative surface voxelization (cvox.cpp): host restatement (ORs into `words`; parallel over z when `parallel`) and the GPU marshalling
 void ConservativeHost(bool parallel, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh);
 void ConservativeDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh);
+// interior fill (fill.cpp): host breadth-first flood from the boundary, and the GPU marshalling; both fill `words` in place
+void FillHost(uint32_t* words, size_t n);
+void FillDevice(const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3]);
 }  // namespace detail
 
 template <Types type, VGType T>
@@ -83,6 +86,24 @@ template <Types type, VGType T>
 void ComputeConservative(const size_t /*blockSize*/, HostVoxelsGrid<T>& grid, const Mesh& mesh)
 {
     ComputeConservative<type, T>(grid, mesh);
+}
+
+// FillInterior: the SOLID of a grid -- every empty voxel that no 6-connected path of empty voxels joins to the grid boundary is set
+// (include/vphip.h, vp_fill_interior; scipy.ndimage.binary_fill_holes).  Run on a ComputeConservative grid it gives the solid of a mesh
+// whose holes are smaller than a voxel, or of a soup that covers a closed surface.  No reference counterpart.
+//   SEQUENTIAL / OPENMP   host flood: an explicit-stack search from every empty boundary voxel over a visited bit grid (one thread)
+//   NAIVE / TILED         vp_fill_interior_host (one GPU path, like CSG)
+// Every variant produces the same bits.
+template <Types type, VGType T>
+void FillInterior(HostVoxelsGrid<T>& grid)
+{
+    auto& v = grid.View();
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    uint32_t* words = reinterpret_cast<uint32_t*>(v.Data());
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        detail::FillHost(words, v.VoxelsPerSide());
+    else
+        detail::FillDevice(type == Types::NAIVE ? "NaiveFill" : "TiledFill", words, v.VoxelsPerSide(), v.VoxelSize(), origin);
 }
 
 }  // namespace VOX

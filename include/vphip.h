@@ -142,6 +142,21 @@ int vp_voxelize_conservative(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words,
                              const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,
                              int algo, int accumulate);
 
+/* ---- interior fill (no reference counterpart) -----------------------------------------------
+ * Turns a grid into a solid by filling every enclosed empty region.  A voxel is EXTERIOR if it is not set in d_words and either lies
+ * on the grid boundary (x, y or z in {0, n-1}) or is face-adjacent (6-connectivity) to an exterior voxel; d_out = NOT exterior, i.e.
+ * d_words plus every empty voxel the boundary cannot reach (scipy.ndimage.binary_fill_holes with its default structure).  The
+ * conservative grid above is 26-separating, so a 6-connected flood cannot cross a surface that is closed at voxel scale: filling it
+ * gives the solid of an open mesh whose holes are smaller than a voxel, or of a soup that covers a closed surface (DESIGN.md
+ * section 10).  No connectivity option.
+ *   Whole-grid frames only: a slab frame (z0 != 0 || z1 != n) returns VP_ERR_UNSUPPORTED.  d_out must not overlap d_words
+ *   (VP_ERR_INVALID); both 16-byte aligned.  Every refusal leaves d_out untouched.
+ *   h_rounds (may be NULL) receives the number of propagation rounds that ran -- one round sweeps x, y and z -- including the final
+ *   round that changed nothing.
+ * BLOCKING: rounds are enqueued in batches and their convergence flags read back once per batch; when the call returns, d_out is
+ * complete and the stream is idle.  It cannot be captured in a graph.  The flags (a few words, grow-only) belong to the context. */
+int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
@@ -371,6 +386,8 @@ int vp_jfa_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, float f
 /* vp_voxelize_conservative with the convention above (whole-grid frame, overwrite) */
 int vp_voxelize_conservative_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words,
                                   const float* h_xyz, size_t nverts, const uint32_t* h_tri, size_t ntris, int algo);
+/* vp_fill_interior with the convention above (whole-grid frame); staged through workspace slots, so h_out may equal h_words */
+int vp_fill_interior_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out);
 
 /* ---- per-kernel timing (PROFILING_SCOPE equivalent for device time, vplib/src/profiling.h:8-33)
  * When enabled, every kernel launch is bracketed by hipEvents on the context's stream. */
@@ -393,6 +410,11 @@ enum {
     VP_K_CVOX_SCAN,     /* TILED: row scan of the large-triangle list */
     VP_K_CVOX_ROWS,     /* TILED: the rows of the large triangles */
     VP_K_CVOX_NAIVE,    /* NAIVE: one thread per triangle */
+    /* vp_fill_interior (per round; rounds after convergence return at once): */
+    VP_K_FILL_X,        /* x sweep (round 0: seeds the six faces): 2 n^3/8 read + n^3/8 written */
+    VP_K_FILL_Y,        /* y sweep: three walks over each column segment, 6 n^3/8 read + up to 2 n^3/8 written */
+    VP_K_FILL_Z,        /* z sweep: as y */
+    VP_K_FILL_FINAL,    /* out = NOT exterior: 2 n^3/8 */
     VP_K_COUNT
 };
 int vp_prof_enable(vp_ctx* ctx, int on);
