@@ -26,6 +26,13 @@
 //                            that no 6-connected path of empty voxels joins to the grid boundary is set (include/vphip.h,
 //                            vp_fill_interior).  Runs before export, CSG and sdf, so --conservative --fill gives the solid of an open
 //                            mesh or soup whose holes are smaller than a voxel.  One device only (-g > 1 is refused)
+//         --morph LIST       (extension) ball morphology on each mesh's grid, after its voxelization (solid or --conservative) and before
+//                            --fill, export, CSG and sdf.  LIST = comma-separated steps, applied in order: dilate:R, erode:R, open:R,
+//                            close:R (integer ball radius R = 0 .. 32; include/vphip.h, vp_morph) and fill (the interior fill of --fill).
+//                            --conservative --morph dilate:3,fill,erode:3 repairs a shell with holes up to about 5 voxels wide;
+//                            close:3 followed by a fill does not (the erosion inside close re-opens the plug).  --fill always runs
+//                            after the whole list, wherever it stands on the command line: a fill at any other place is written as
+//                            a step of the list (--morph fill,erode:1 is erode(fill(W))).  One device only (-g > 1 is refused)
 //     -h, --help
 #include <cmath>
 #include <cstdint>
@@ -73,7 +80,38 @@ struct Options {
     bool conservative = false;
     bool fill = false;
     bool help = false;
+    struct MorphStep { int op; unsigned radius; };          // op = VOX::MorphOp, or -1: the interior fill
+    std::vector<MorphStep> morph;
 };
+
+// --morph LIST: dilate:R,erode:R,open:R,close:R,fill with R = 0 .. 32; anything else is a usage error
+std::vector<Options::MorphStep> ParseMorph(const std::string& list)
+{
+    static const char* names[] = {"dilate", "erode", "open", "close"};
+    std::vector<Options::MorphStep> steps;
+    size_t pos = 0;
+    while (true) {
+        const size_t comma = list.find(',', pos);
+        const std::string item = list.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+        if (item == "fill") {
+            steps.push_back({-1, 0u});
+        } else {
+            const size_t colon = item.find(':');
+            int op = -1;
+            if (colon != std::string::npos)
+                for (int k = 0; k < 4; ++k) if (item.substr(0, colon) == names[k]) op = k;
+            const std::string num = colon == std::string::npos ? "" : item.substr(colon + 1);
+            const bool digits = !num.empty() && num.size() <= 2 && num.find_first_not_of("0123456789") == std::string::npos;
+            cpuAssert(op >= 0 && digits, "--morph: bad step '" + item + "' (dilate:R, erode:R, open:R, close:R or fill)\n");
+            const unsigned radius = static_cast<unsigned>(std::stoul(num));
+            cpuAssert(radius <= 32, "--morph: radius " + num + " outside 0..32\n");
+            steps.push_back({op, radius});
+        }
+        if (comma == std::string::npos) break;
+        pos = comma + 1;
+    }
+    return steps;
+}
 
 const char* kUsage =
     "CLI apps to test csg voxelization\nUsage:\n  cli [OPTION...] filenames...\n\n"
@@ -106,6 +144,12 @@ const char* kUsage =
     "      --fill            After each voxelization, set every empty voxel the grid boundary cannot reach through face-adjacent\n"
     "                        empty voxels (interior fill: a solid from a --conservative grid); before export, CSG and sdf.\n"
     "                        One device only: not with -g > 1 (extension)\n"
+    "      --morph arg       Ball morphology after each voxelization, before --fill, export, CSG and sdf: comma-separated steps\n"
+    "                        dilate:R, erode:R, open:R, close:R (integer radius R = 0..32) and fill, applied in order, e.g.\n"
+    "                        --conservative --morph dilate:3,fill,erode:3 (solid of a shell with holes up to about 5 voxels wide).\n"
+    "                        --fill always runs after the whole list, wherever it stands on the command line; to fill earlier,\n"
+    "                        write fill inside the list (--morph fill,erode:1 is erode(fill(W)), not fill(erode(W))).\n"
+    "                        One device only: not with -g > 1 (extension)\n"
     "  -h, --help            Print usage\n";
 
 // Minimal getopt-style parser: -x V, -xV, --long V, --long=V, boolean switches, positionals.
@@ -113,7 +157,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -155,6 +199,7 @@ Options Parse(int argc, char** argv)
             case 'd': o.dump = value; break;
             case 'g': o.gpus = static_cast<unsigned>(std::stoul(value)); break;
             case 'M': o.multi = value; break;
+            case 'R': o.morph = ParseMorph(value); cpuAssert(!o.morph.empty(), "--morph needs a list\n"); break;
             default: cpuAssert(false, std::string("Unknown option -") + key + "\n");
         }
     }
@@ -172,6 +217,15 @@ template <Types T>
 void VoxelizeConservative(unsigned blockSize, HostVoxelsGrid<gridType>& grid, const Mesh& mesh)
 {
     VOX::ComputeConservative<T>(blockSize, grid, mesh);
+}
+
+template <Types T>
+void MorphSteps(const std::vector<Options::MorphStep>& steps, HostVoxelsGrid<gridType>& grid)
+{
+    for (const auto& st : steps) {
+        if (st.op < 0) VOX::FillInterior<T>(grid);
+        else VOX::Morph<T>(grid, static_cast<VOX::MorphOp>(st.op), st.radius);
+    }
 }
 
 template <Types T>
@@ -226,6 +280,7 @@ int main(int argc, char** argv)
     cpuAssert(opt.gpus >= 1 && opt.gpus <= 64, "Number of GPUs must be 1..64");
     cpuAssert(!(opt.conservative && opt.gpus > 1), "--conservative runs on one device: -g must be 1\n");
     cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
+    cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
     cpuAssert(opt.multi == "ghost" || opt.multi == "halo" || opt.multi == "hybrid" || opt.multi == "transpose", "--multi must be ghost, halo, hybrid or transpose");
     if (GPU && opt.gpus > 1) {
         // Z-slabs over devices 0 .. G-1.  VPLIB_SHARE_GPU=1 (test rigs with fewer devices than slabs): the slabs share the devices
@@ -281,6 +336,14 @@ int main(int argc, char** argv)
                     case Types::OPENMP: Voxelize<Types::SEQUENTIAL>(opt.blockSize, grid, meshes[i]); break;   // main.cpp:99-103
                     case Types::NAIVE:  Voxelize<Types::NAIVE>(opt.blockSize, grid, meshes[i]); break;
                     case Types::TILED:  Voxelize<Types::TILED>(opt.blockSize, grid, meshes[i]); break;
+                }
+            }
+            if (!opt.morph.empty()) {
+                switch (TYPE) {
+                    case Types::SEQUENTIAL: MorphSteps<Types::SEQUENTIAL>(opt.morph, grid); break;
+                    case Types::OPENMP:     MorphSteps<Types::OPENMP>(opt.morph, grid); break;
+                    case Types::NAIVE:      MorphSteps<Types::NAIVE>(opt.morph, grid); break;
+                    case Types::TILED:      MorphSteps<Types::TILED>(opt.morph, grid); break;
                 }
             }
             if (opt.fill) {

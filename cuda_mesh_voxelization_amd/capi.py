@@ -13,13 +13,15 @@ HOOKS_LIB_PATH = os.path.join(PKG, "libvphip_hooks.so")
 
 ALGO_NAIVE, ALGO_TILED = 1, 2
 OP_VOID, OP_UNION, OP_INTERSECTION, OP_DIFFERENCE = 0, 1, 2, 3
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3     # vp_morph: ball morphology
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
 MULTI_HALO, MULTI_GHOST, MULTI_HYBRID, MULTI_TRANSPOSE = 0, 1, 2, 3
 
 KERNELS = ["vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
            "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
            "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
-           "fill_x", "fill_y", "fill_z", "fill_final"]
+           "fill_x", "fill_y", "fill_z", "fill_final",
+           "morph", "morph_naive"]
 JFA_PASS_KEYS = ("jfa_pass", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last")
 
 # every symbol include/vphip.h declares (tests check the library exports all of them)
@@ -38,6 +40,7 @@ SYMBOLS = [
     "vp_multi_set_grid", "vp_multi_get_grid", "vp_multi_csg", "vp_multi_jfa", "vp_multi_get_sdf", "vp_multi_bytes_moved", "vp_multi_window",
     "vp_voxelize_conservative", "vp_voxelize_conservative_host",
     "vp_fill_interior", "vp_fill_interior_host",
+    "vp_morph", "vp_morph_host",
 ]
 
 
@@ -138,6 +141,8 @@ def lib():
         "vp_voxelize_conservative_host": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int]),
         "vp_fill_interior": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.POINTER(ctypes.c_uint32)]),
         "vp_fill_interior_host": (ctypes.c_int, [_vp, fp, _vp, _vp]),
+        "vp_morph": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
+        "vp_morph_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -264,6 +269,10 @@ class Context:
         rounds = ctypes.c_uint32(0)
         check(lib().vp_fill_interior(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), ctypes.byref(rounds)))
         return rounds.value
+
+    def morph(self, frame: Frame, d_words: int, d_out: int, op: int, radius: int, algo: int = ALGO_TILED):
+        """Ball morphology (MORPH_DILATE / ERODE / OPEN / CLOSE, integer radius 0 .. 32): d_out = op(d_words).  Enqueues only."""
+        check(lib().vp_morph(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), op, radius, algo))
 
     def csg(self, d_a: int, d_b: int, nwords: int, op: int):
         check(lib().vp_csg(self._h, _vp(d_a), _vp(d_b), nwords, op))
@@ -398,6 +407,9 @@ class Context:
 
     def fill_interior_host(self, frame: Frame, h_words, h_out):
         check(lib().vp_fill_interior_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp)))
+
+    def morph_host(self, frame: Frame, h_words, h_out, op: int, radius: int, algo: int = ALGO_TILED):
+        check(lib().vp_morph_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp), op, radius, algo))
 
     def csg_host(self, h_a, h_b, op: int):
         check(lib().vp_csg_host(self._h, h_a.ctypes.data_as(_vp), h_b.ctypes.data_as(_vp), h_a.size, op))

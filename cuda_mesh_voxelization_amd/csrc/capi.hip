@@ -131,7 +131,8 @@ static const char* kNames[VP_K_COUNT] = {
     "vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
     "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
     "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
-    "fill_x", "fill_y", "fill_z", "fill_final"
+    "fill_x", "fill_y", "fill_z", "fill_final",
+    "morph", "morph_naive"
 };
 
 }  // namespace vp
@@ -178,7 +179,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
-                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags };
+                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -342,6 +343,24 @@ int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, ui
     if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
     grid_written(ctx, d_out, bytes);
     return launch_fill_interior(ctx, f->n, d_words, d_out, h_rounds);
+}
+
+int vp_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo)
+{
+    const char* who = "vp_morph";
+    if (!ctx || !d_words || !d_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_frame(f, who, false));
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    if (op != VP_MORPH_DILATE && op != VP_MORPH_ERODE && op != VP_MORPH_OPEN && op != VP_MORPH_CLOSE)
+        return set_error(VP_ERR_INVALID, "%s: unknown op %d", who, op);
+    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    if (radius > 32) return set_error(VP_ERR_UNSUPPORTED, "%s: radius %u is not served (0 .. 32)", who, radius);
+    VP_TRY(check_aligned(who, {d_words, d_out}));
+    const size_t bytes = vp_grid_words(f) * 4;
+    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    grid_written(ctx, d_out, bytes);
+    return launch_morph(ctx, f->n, d_words, d_out, op, radius, algo);
 }
 
 int vp_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op)
@@ -819,6 +838,21 @@ int vp_fill_interior_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_word
     VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
     VP_TRY(vp_upload(ctx, da, h_words, wb));
     VP_TRY(vp_fill_interior(ctx, f, (const uint32_t*)da, (uint32_t*)db, nullptr));
+    return vp_download(ctx, h_out, db, wb);
+}
+
+int vp_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo)
+{
+    const char* who = "vp_morph_host";
+    if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_frame(f, who, false));
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    void *da = nullptr, *db = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
+    VP_TRY(vp_upload(ctx, da, h_words, wb));
+    VP_TRY(vp_morph(ctx, f, (const uint32_t*)da, (uint32_t*)db, op, radius, algo));
     return vp_download(ctx, h_out, db, wb);
 }
 

@@ -88,6 +88,8 @@ struct vp_ctx {
     // interior fill (fill.hip): the ring of round flags (two batches) and its pinned host copy of one batch
     vp::Buffer fill_flags;
     uint32_t* fill_host = nullptr;
+    // ball morphology (morph.hip): the row tables of every radius (uploaded by the first tiled call) and the intermediate grid of open / close
+    vp::Buffer morph_tab, morph_tmp;
     // profiling
     bool prof_on = false;
     uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
@@ -154,6 +156,8 @@ int launch_voxelize_conservative(vp_ctx* ctx, const Frame& f, uint32_t* d_words,
                                  const uint32_t* d_tri, size_t ntris, int algo, int accumulate);
 // fill.hip: interior fill of a whole grid, d_out = NOT exterior(d_words); blocking (reads the round flags back once per batch)
 int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds);
+// morph.hip: ball dilate / erode / open / close of a whole grid (enqueues only, once the context's buffers have grown)
+int launch_morph(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
 int launch_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op);
 int launch_stream_copy(vp_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);   // 16 B per lane: the measured HBM copy rate
 // jfa_seed.hip

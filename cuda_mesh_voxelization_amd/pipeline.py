@@ -71,6 +71,14 @@ class Engine:
         rounds = self.ctx.fill_interior(frame, words.data_ptr(), out.data_ptr())
         return out, rounds
 
+    def morph(self, frame: Frame, words, op: int, radius: int, out=None, algo: int = ALGO_TILED):
+        """Ball morphology of a whole grid: out = dilate / erode / open / close (capi.MORPH_*) of `words` by the integer ball of `radius`
+        (0 .. 32).  `out` must not be `words`.  Enqueues only; returns out."""
+        if out is None:
+            out = self.new_grid(frame)
+        self.ctx.morph(frame, words.data_ptr(), out.data_ptr(), op, radius, algo)
+        return out
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

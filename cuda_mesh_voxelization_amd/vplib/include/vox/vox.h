@@ -37,6 +37,9 @@ void ConservativeDevice(int algo, const char* label, uint32_t* words, size_t n, 
 // interior fill (fill.cpp): host breadth-first flood from the boundary, and the GPU marshalling; both fill `words` in place
 void FillHost(uint32_t* words, size_t n);
 void FillDevice(const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3]);
+// ball morphology (morph.cpp): host restatement by separable capped squared distances, and the GPU marshalling; both work in place
+void MorphHost(bool parallel, uint32_t* words, size_t n, int op, uint32_t radius);
+void MorphDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], int op, uint32_t radius);
 }  // namespace detail
 
 template <Types type, VGType T>
@@ -104,6 +107,31 @@ void FillInterior(HostVoxelsGrid<T>& grid)
         detail::FillHost(words, v.VoxelsPerSide());
     else
         detail::FillDevice(type == Types::NAIVE ? "NaiveFill" : "TiledFill", words, v.VoxelsPerSide(), v.VoxelSize(), origin);
+}
+
+// Morph: ball morphology of a grid, in place (include/vphip.h, vp_morph).  B_r = {d in Z^3 : |d|^2 <= r^2}, r = 0 .. 32 (0 = identity).
+//   DILATE  set iff some set voxel lies within B_r (outside the grid reads as empty)   scipy binary_dilation(border_value=0)
+//   ERODE   NOT dilate(NOT grid) (outside the grid reads as set)                       scipy binary_erosion(border_value=1)
+//   OPEN = dilate(erode), CLOSE = erode(dilate): idempotent, open a subset and close a superset of the grid.
+// To repair a shell with holes up to about 2 r voxels wide: Morph(DILATE, r), FillInterior, Morph(ERODE, r) -- not CLOSE then fill,
+// which leaks (the erosion inside CLOSE re-opens the plug before the fill sees it).  No reference counterpart.
+//   SEQUENTIAL / OPENMP   host restatement in another formulation: the exact capped squared distance in three separable integer passes
+//                         (x, then y, then z), then <= r^2; OPENMP runs the planes in parallel
+//   NAIVE / TILED         vp_morph_host with VP_ALGO_NAIVE / VP_ALGO_TILED
+// Every variant produces the same bits.
+enum class MorphOp : int { DILATE = 0, ERODE = 1, OPEN = 2, CLOSE = 3 };     // = VP_MORPH_*
+
+template <Types type, VGType T>
+void Morph(HostVoxelsGrid<T>& grid, MorphOp op, uint32_t radius)
+{
+    auto& v = grid.View();
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    uint32_t* words = reinterpret_cast<uint32_t*>(v.Data());
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        detail::MorphHost(type == Types::OPENMP, words, v.VoxelsPerSide(), static_cast<int>(op), radius);
+    else
+        detail::MorphDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveMorph" : "TiledMorph", words, v.VoxelsPerSide(),
+                            v.VoxelSize(), origin, static_cast<int>(op), radius);
 }
 
 }  // namespace VOX

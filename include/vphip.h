@@ -157,6 +157,32 @@ int vp_voxelize_conservative(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words,
  * complete and the stream is idle.  It cannot be captured in a graph.  The flags (a few words, grow-only) belong to the context. */
 int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds);
 
+/* ---- ball morphology: dilate, erode, open, close (no reference counterpart) --------------------
+ * B_r = {(dx, dy, dz) in Z^3 : dx^2 + dy^2 + dz^2 <= r^2}, integer r; everything below is integer arithmetic.
+ *   VP_MORPH_DILATE  voxel p is set iff some d in B_r has p - d inside the grid and set: voxels outside the grid read as EMPTY, the
+ *                    result is clipped to the grid (scipy.ndimage.binary_dilation(W, structure=ball, border_value=0)).
+ *   VP_MORPH_ERODE   NOT dilate(NOT W, r): voxels outside the grid read as SET (scipy.ndimage.binary_erosion(W, structure=ball,
+ *                    border_value=1)).  The frame is the tight bounding box, so meshes touch the grid faces; a border of 0 would eat
+ *                    them.  With these two borders (dilate, erode) is an adjunction on the grid lattice, hence:
+ *   VP_MORPH_OPEN    dilate(erode(W)): idempotent, a subset of W (removes specks thinner than the ball).
+ *   VP_MORPH_CLOSE   erode(dilate(W)): idempotent, a superset of W.
+ *   radius 0 copies the grid; 1 .. 32 is served (the x reach stays inside the two neighbouring words); above 32: VP_ERR_UNSUPPORTED.
+ * REPAIRING AN OPEN SHELL: vp_fill_interior needs holes smaller than a voxel.  For holes up to about 2 R voxels wide:
+ *     dilate(conservative grid, R)  ->  vp_fill_interior  ->  erode(., R)
+ * The dilation plugs the hole, the fill makes the solid, the erosion puts the outer surface back where it was (a shallow dimple of at
+ * most about k^2 R voxels remains behind a k x k hole).  CLOSE IS NOT THAT RECIPE: fill(close(W, R)) still leaks, because the erosion
+ * inside close runs BEFORE the fill and re-opens the plug from the side -- the plug is thinner than the ball.
+ *   Whole-grid frames only: a slab frame (z0 != 0 || z1 != n) returns VP_ERR_UNSUPPORTED.  d_out must not overlap d_words
+ *   (VP_ERR_INVALID); both 16-byte aligned.  Null pointers, an unknown op, an unknown algo: VP_ERR_INVALID.  Every refusal leaves
+ *   d_out untouched.
+ *   algo: VP_ALGO_NAIVE -- one thread per output word, every row of the ball x-dilated by its own half-width; VP_ALGO_TILED -- the rows
+ *   folded in by Horner over the half-widths, tiles staged in LDS.  Same bits.
+ * Open and close run two passes through an intermediate grid of n^3/8 bytes, a grow-only buffer of the context.  ASYNCHRONOUS in steady
+ * state: the call only enqueues kernels on the context's stream; the call that first grows a buffer of the context may synchronise.
+ * Like every writer of a grid, it drops a pending vp_jfa_start whose words (or workspace) d_out overlaps. */
+enum { VP_MORPH_DILATE = 0, VP_MORPH_ERODE = 1, VP_MORPH_OPEN = 2, VP_MORPH_CLOSE = 3 };
+int vp_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
@@ -389,6 +415,9 @@ int vp_voxelize_conservative_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_wo
 /* vp_fill_interior with the convention above (whole-grid frame); staged through workspace slots, so h_out may equal h_words */
 int vp_fill_interior_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out);
 
+/* vp_morph with the convention above (whole-grid frame); staged through workspace slots, so h_out may equal h_words */
+int vp_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo);
+
 /* ---- per-kernel timing (PROFILING_SCOPE equivalent for device time, vplib/src/profiling.h:8-33)
  * When enabled, every kernel launch is bracketed by hipEvents on the context's stream. */
 enum {
@@ -415,6 +444,9 @@ enum {
     VP_K_FILL_Y,        /* y sweep: three walks over each column segment, 6 n^3/8 read + up to 2 n^3/8 written */
     VP_K_FILL_Z,        /* z sweep: as y */
     VP_K_FILL_FINAL,    /* out = NOT exterior: 2 n^3/8 */
+    /* vp_morph (open and close book two launches): */
+    VP_K_MORPH,         /* VP_ALGO_TILED, one dilate or erode pass: 2 n^3/8 algorithmic bytes */
+    VP_K_MORPH_NAIVE,   /* VP_ALGO_NAIVE, one pass */
     VP_K_COUNT
 };
 int vp_prof_enable(vp_ctx* ctx, int on);
