@@ -33,6 +33,11 @@
 //                            close:3 followed by a fill does not (the erosion inside close re-opens the plug).  --fill always runs
 //                            after the whole list, wherever it stands on the command line: a fill at any other place is written as
 //                            a step of the list (--morph fill,erode:1 is erode(fill(W))).  One device only (-g > 1 is refused)
+//                            Two more steps filter by connected component (include/vphip.h, vp_components_filter): largest[:C] keeps the
+//                            largest component, minsize:V[:C] the components of at least V voxels; C = 6 (face neighbours) or 26 (face,
+//                            edge and corner neighbours; the default: the fill floods the empty phase with 6, so the set phase takes 26).
+//                            Each prints "components: K, kept: M voxels".  --conservative --morph dilate:2,fill,erode:2,largest drops
+//                            the debris of a scan and leaves the object bit for bit (open:R would round its edges)
 //     -h, --help
 #include <cmath>
 #include <cstdint>
@@ -80,11 +85,13 @@ struct Options {
     bool conservative = false;
     bool fill = false;
     bool help = false;
-    struct MorphStep { int op; unsigned radius; };          // op = VOX::MorphOp, or -1: the interior fill
+    // op = VOX::MorphOp, or -1: the interior fill, -2: largest component, -3: minsize (value = V); conn = 6 / 26 for the last two
+    struct MorphStep { int op; unsigned radius; unsigned value = 0; int conn = 26; };
     std::vector<MorphStep> morph;
 };
 
-// --morph LIST: dilate:R,erode:R,open:R,close:R,fill with R = 0 .. 32; anything else is a usage error
+// --morph LIST: dilate:R,erode:R,open:R,close:R,fill with R = 0 .. 32, largest[:C] and minsize:V[:C] with C = 6 or 26; anything else is a
+// usage error
 std::vector<Options::MorphStep> ParseMorph(const std::string& list)
 {
     static const char* names[] = {"dilate", "erode", "open", "close"};
@@ -95,6 +102,24 @@ std::vector<Options::MorphStep> ParseMorph(const std::string& list)
         const std::string item = list.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
         if (item == "fill") {
             steps.push_back({-1, 0u});
+        } else if (item.rfind("largest", 0) == 0 || item.rfind("minsize", 0) == 0) {
+            // fields after the name, split at ':' (an empty field is a field: "minsize:" has one)
+            std::vector<std::string> fields;
+            for (size_t p = 7; p < item.size();) {
+                if (item[p] != ':') { fields.assign(3, ""); break; }              // "largestX": no such step
+                const size_t next = item.find(':', p + 1);
+                fields.push_back(item.substr(p + 1, next == std::string::npos ? std::string::npos : next - p - 1));
+                p = next == std::string::npos ? item.size() : next;
+            }
+            const bool largest = item[0] == 'l';
+            auto digits = [](const std::string& t) { return !t.empty() && t.size() <= 10 && t.find_first_not_of("0123456789") == std::string::npos; };
+            bool ok = fields.size() <= (largest ? 1u : 2u) && (largest || fields.size() >= 1);
+            unsigned long long value = 0;
+            if (ok && !largest) { ok = digits(fields[0]); if (ok) value = std::stoull(fields[0]); ok = ok && value <= 0xFFFFFFFFull; }
+            int conn = 26;
+            if (ok && fields.size() == (largest ? 1u : 2u)) { ok = fields.back() == "6" || fields.back() == "26"; if (ok) conn = std::stoi(fields.back()); }
+            cpuAssert(ok, "--morph: bad step '" + item + "' (largest[:C] or minsize:V[:C] with V a voxel count and C = 6 or 26)\n");
+            steps.push_back({largest ? -2 : -3, 0u, static_cast<unsigned>(value), conn});
         } else {
             const size_t colon = item.find(':');
             int op = -1;
@@ -102,7 +127,7 @@ std::vector<Options::MorphStep> ParseMorph(const std::string& list)
                 for (int k = 0; k < 4; ++k) if (item.substr(0, colon) == names[k]) op = k;
             const std::string num = colon == std::string::npos ? "" : item.substr(colon + 1);
             const bool digits = !num.empty() && num.size() <= 2 && num.find_first_not_of("0123456789") == std::string::npos;
-            cpuAssert(op >= 0 && digits, "--morph: bad step '" + item + "' (dilate:R, erode:R, open:R, close:R or fill)\n");
+            cpuAssert(op >= 0 && digits, "--morph: bad step '" + item + "' (dilate:R, erode:R, open:R, close:R, fill, largest[:C] or minsize:V[:C])\n");
             const unsigned radius = static_cast<unsigned>(std::stoul(num));
             cpuAssert(radius <= 32, "--morph: radius " + num + " outside 0..32\n");
             steps.push_back({op, radius});
@@ -149,6 +174,10 @@ const char* kUsage =
     "                        --conservative --morph dilate:3,fill,erode:3 (solid of a shell with holes up to about 5 voxels wide).\n"
     "                        --fill always runs after the whole list, wherever it stands on the command line; to fill earlier,\n"
     "                        write fill inside the list (--morph fill,erode:1 is erode(fill(W)), not fill(erode(W))).\n"
+    "                        Component filters are steps too: largest[:C] keeps the largest connected component, minsize:V[:C] the\n"
+    "                        components of at least V voxels; C = 6 (face neighbours) or 26 (face, edge and corner neighbours,\n"
+    "                        the default); each prints 'components: K, kept: M voxels'.  E.g. --conservative --morph\n"
+    "                        dilate:2,fill,erode:2,largest removes floating debris and leaves the object bit for bit.\n"
     "                        One device only: not with -g > 1 (extension)\n"
     "  -h, --help            Print usage\n";
 
@@ -223,8 +252,15 @@ template <Types T>
 void MorphSteps(const std::vector<Options::MorphStep>& steps, HostVoxelsGrid<gridType>& grid)
 {
     for (const auto& st : steps) {
-        if (st.op < 0) VOX::FillInterior<T>(grid);
-        else VOX::Morph<T>(grid, static_cast<VOX::MorphOp>(st.op), st.radius);
+        if (st.op == -1) {
+            VOX::FillInterior<T>(grid);
+        } else if (st.op < 0) {
+            const VOX::ComponentStats cs = st.op == -2 ? VOX::FilterComponents<T>(grid, VOX::ComponentFilter::KEEP_LARGEST, 1u, st.conn)
+                                                       : VOX::FilterComponents<T>(grid, VOX::ComponentFilter::MIN_VOXELS, st.value, st.conn);
+            std::printf("components: %u, kept: %llu voxels\n", cs.count, static_cast<unsigned long long>(cs.kept));
+        } else {
+            VOX::Morph<T>(grid, static_cast<VOX::MorphOp>(st.op), st.radius);
+        }
     }
 }
 

@@ -14,6 +14,8 @@ HOOKS_LIB_PATH = os.path.join(PKG, "libvphip_hooks.so")
 ALGO_NAIVE, ALGO_TILED = 1, 2
 OP_VOID, OP_UNION, OP_INTERSECTION, OP_DIFFERENCE = 0, 1, 2, 3
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3     # vp_morph: ball morphology
+CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
+COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
 MULTI_HALO, MULTI_GHOST, MULTI_HYBRID, MULTI_TRANSPOSE = 0, 1, 2, 3
 
@@ -22,6 +24,10 @@ KERNELS = ["vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox
            "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
            "fill_x", "fill_y", "fill_z", "fill_final",
            "morph", "morph_naive"]
+# the timing keys of vp_components_* follow those of KERNELS in the header's enum (PROF_KEYS is the whole enum, in its order)
+COMP_KERNELS = ["comp_init", "comp_merge", "comp_init_naive", "comp_merge_naive", "comp_flatten", "comp_rank", "comp_relabel", "comp_sizes",
+                "comp_select", "comp_write"]
+PROF_KEYS = KERNELS + COMP_KERNELS
 JFA_PASS_KEYS = ("jfa_pass", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last")
 
 # every symbol include/vphip.h declares (tests check the library exports all of them)
@@ -41,6 +47,7 @@ SYMBOLS = [
     "vp_voxelize_conservative", "vp_voxelize_conservative_host",
     "vp_fill_interior", "vp_fill_interior_host",
     "vp_morph", "vp_morph_host",
+    "vp_components_label", "vp_components_sizes", "vp_components_filter", "vp_components_label_host", "vp_components_filter_host",
 ]
 
 
@@ -143,6 +150,13 @@ def lib():
         "vp_fill_interior_host": (ctypes.c_int, [_vp, fp, _vp, _vp]),
         "vp_morph": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
         "vp_morph_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
+        "vp_components_label": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_components_sizes": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, _vp]),
+        "vp_components_filter": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_components_label_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_components_filter_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+                                                     ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -273,6 +287,25 @@ class Context:
     def morph(self, frame: Frame, d_words: int, d_out: int, op: int, radius: int, algo: int = ALGO_TILED):
         """Ball morphology (MORPH_DILATE / ERODE / OPEN / CLOSE, integer radius 0 .. 32): d_out = op(d_words).  Enqueues only."""
         check(lib().vp_morph(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), op, radius, algo))
+
+    def components_label(self, frame: Frame, d_words: int, d_labels: int, conn: int = CONN_26, algo: int = ALGO_TILED) -> int:
+        """Connected components of the set voxels (CONN_6 / CONN_26): d_labels takes one uint32 per voxel, 0 = background, components
+        1 .. K in the order of their lowest voxel index (= scipy.ndimage.label).  Blocking; returns K."""
+        count = ctypes.c_uint32()
+        check(lib().vp_components_label(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_labels), conn, algo, ctypes.byref(count)))
+        return count.value
+
+    def components_sizes(self, frame: Frame, d_labels: int, count: int, d_sizes: int):
+        """d_sizes[k - 1] = voxels of component k of a label volume with `count` components.  Blocking."""
+        check(lib().vp_components_sizes(self._h, ctypes.byref(frame), _vp(d_labels), count, _vp(d_sizes or None)))
+
+    def components_filter(self, frame: Frame, d_words: int, d_out: int, mode: int, param: int, conn: int = CONN_26, algo: int = ALGO_TILED):
+        """d_out = the components of d_words that pass COMP_KEEP_LARGEST (param = m largest, 1 .. 16) or COMP_MIN_VOXELS (param = least
+        size).  Blocking; returns (K, kept voxels)."""
+        count, kept = ctypes.c_uint32(), ctypes.c_uint64()
+        check(lib().vp_components_filter(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), conn, mode, param, algo,
+                                         ctypes.byref(count), ctypes.byref(kept)))
+        return count.value, kept.value
 
     def csg(self, d_a: int, d_b: int, nwords: int, op: int):
         check(lib().vp_csg(self._h, _vp(d_a), _vp(d_b), nwords, op))
@@ -411,6 +444,18 @@ class Context:
     def morph_host(self, frame: Frame, h_words, h_out, op: int, radius: int, algo: int = ALGO_TILED):
         check(lib().vp_morph_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp), op, radius, algo))
 
+    def components_label_host(self, frame: Frame, h_words, h_labels, conn: int = CONN_26, algo: int = ALGO_TILED) -> int:
+        count = ctypes.c_uint32()
+        check(lib().vp_components_label_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_labels.ctypes.data_as(_vp), conn, algo,
+                                             ctypes.byref(count)))
+        return count.value
+
+    def components_filter_host(self, frame: Frame, h_words, h_out, mode: int, param: int, conn: int = CONN_26, algo: int = ALGO_TILED):
+        count, kept = ctypes.c_uint32(), ctypes.c_uint64()
+        check(lib().vp_components_filter_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp), conn, mode,
+                                              param, algo, ctypes.byref(count), ctypes.byref(kept)))
+        return count.value, kept.value
+
     def csg_host(self, h_a, h_b, op: int):
         check(lib().vp_csg_host(self._h, h_a.ctypes.data_as(_vp), h_b.ctypes.data_as(_vp), h_a.size, op))
 
@@ -424,7 +469,7 @@ class Context:
 
     def prof_select(self, names=None):
         """Time only the kernels whose timing keys are named (None = all): every event pair costs stream time."""
-        mask = (1 << 64) - 1 if names is None else sum(1 << KERNELS.index(k) for k in names)
+        mask = (1 << 64) - 1 if names is None else sum(1 << PROF_KEYS.index(k) for k in names)
         check(lib().vp_prof_select(self._h, mask))
 
     def prof_reset(self):
@@ -432,7 +477,7 @@ class Context:
 
     def prof(self):
         out = {}
-        for i, name in enumerate(KERNELS):
+        for i, name in enumerate(PROF_KEYS):
             ms = ctypes.c_double()
             n = ctypes.c_uint64()
             check(lib().vp_prof_get(self._h, i, ctypes.byref(ms), ctypes.byref(n)))

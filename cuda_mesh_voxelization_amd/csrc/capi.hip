@@ -132,7 +132,9 @@ static const char* kNames[VP_K_COUNT] = {
     "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
     "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
     "fill_x", "fill_y", "fill_z", "fill_final",
-    "morph", "morph_naive"
+    "morph", "morph_naive",
+    "comp_init", "comp_merge", "comp_init_naive", "comp_merge_naive", "comp_flatten", "comp_rank", "comp_relabel", "comp_sizes", "comp_select",
+    "comp_write"
 };
 
 }  // namespace vp
@@ -179,7 +181,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
-                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp };
+                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp,
+                       &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -189,6 +192,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->cvox_event) (void)hipEventDestroy(ctx->cvox_event);
     if (ctx->cvox_host) (void)hipHostFree(ctx->cvox_host);
     if (ctx->fill_host) (void)hipHostFree(ctx->fill_host);
+    if (ctx->comp_host) (void)hipHostFree(ctx->comp_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -254,6 +258,7 @@ int vp_ctx_release(vp_ctx* ctx)
     VP_HIP(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     release(ctx->jfa_work);
+    release(ctx->comp_labels);                                     // vp_components_filter's label volume, 4 n^3 bytes
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     return 0;
@@ -361,6 +366,65 @@ int vp_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* 
     if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
     grid_written(ctx, d_out, bytes);
     return launch_morph(ctx, f->n, d_words, d_out, op, radius, algo);
+}
+
+// what the three vp_components_* entry points share: whole grids up to n = 1024, connectivity and algo
+static int check_components(const vp_frame* f, const char* who, int connectivity, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: voxel indices are 32-bit)", who, f->n);
+    if (connectivity != VP_CONN_6 && connectivity != VP_CONN_26) return set_error(VP_ERR_INVALID, "%s: unknown connectivity %d (6 or 26)", who, connectivity);
+    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    return 0;
+}
+
+static int check_filter_mode(const char* who, int mode, uint32_t param)
+{
+    if (mode != VP_COMP_KEEP_LARGEST && mode != VP_COMP_MIN_VOXELS) return set_error(VP_ERR_INVALID, "%s: unknown mode %d", who, mode);
+    if (mode == VP_COMP_KEEP_LARGEST && (param < 1 || param > 16)) return set_error(VP_ERR_INVALID, "%s: KEEP_LARGEST m=%u outside 1 .. 16", who, param);
+    return 0;
+}
+
+int vp_components_label(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_labels, int connectivity, int algo,
+                        uint32_t* h_count)
+{
+    const char* who = "vp_components_label";
+    if (!ctx || !d_words || !d_labels || !h_count) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_components(f, who, connectivity, algo));
+    VP_TRY(check_aligned(who, {d_words, d_labels}));
+    const size_t wb = vp_grid_words(f) * 4, lb = vp_grid_voxels(f) * 4;
+    if (overlaps(d_words, wb, d_labels, lb)) return set_error(VP_ERR_INVALID, "%s: d_labels overlaps d_words", who);
+    grid_written(ctx, d_labels, lb);
+    return launch_components_label(ctx, f->n, d_words, d_labels, connectivity, algo, h_count);
+}
+
+int vp_components_sizes(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_labels, uint32_t count, uint32_t* d_sizes)
+{
+    const char* who = "vp_components_sizes";
+    if (!ctx || !d_labels || (!d_sizes && count)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_components(f, who, VP_CONN_6, VP_ALGO_TILED));
+    VP_TRY(check_aligned(who, {d_labels, d_sizes}));
+    if (count && overlaps(d_labels, vp_grid_voxels(f) * 4, d_sizes, (size_t)count * 4)) return set_error(VP_ERR_INVALID, "%s: d_sizes overlaps d_labels", who);
+    if (count) grid_written(ctx, d_sizes, (size_t)count * 4);
+    return launch_components_sizes(ctx, f->n, d_labels, count, d_sizes);
+}
+
+int vp_components_filter(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int connectivity, int mode,
+                         uint32_t param, int algo, uint32_t* h_count, uint64_t* h_kept)
+{
+    const char* who = "vp_components_filter";
+    if (!ctx || !d_words || !d_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_components(f, who, connectivity, algo));
+    VP_TRY(check_filter_mode(who, mode, param));
+    VP_TRY(check_aligned(who, {d_words, d_out}));
+    const size_t bytes = vp_grid_words(f) * 4;
+    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    grid_written(ctx, d_out, bytes);
+    return launch_components_filter(ctx, f->n, d_words, d_out, connectivity, mode, param, algo, h_count, h_kept);
 }
 
 int vp_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op)
@@ -853,6 +917,37 @@ int vp_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint3
     VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
     VP_TRY(vp_upload(ctx, da, h_words, wb));
     VP_TRY(vp_morph(ctx, f, (const uint32_t*)da, (uint32_t*)db, op, radius, algo));
+    return vp_download(ctx, h_out, db, wb);
+}
+
+int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,
+                             uint32_t* h_count)
+{
+    const char* who = "vp_components_label_host";
+    if (!ctx || !h_words || !h_labels || !h_count) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_components(f, who, connectivity, algo));
+    void *dw = nullptr, *dl = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, lb = vp_grid_voxels(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, lb, &dl));              // one 32-bit value per voxel, like the sdf
+    VP_TRY(vp_upload(ctx, dw, h_words, wb));
+    VP_TRY(vp_components_label(ctx, f, (const uint32_t*)dw, (uint32_t*)dl, connectivity, algo, h_count));
+    return vp_download(ctx, h_labels, dl, lb);
+}
+
+int vp_components_filter_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int connectivity, int mode,
+                              uint32_t param, int algo, uint32_t* h_count, uint64_t* h_kept)
+{
+    const char* who = "vp_components_filter_host";
+    if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_components(f, who, connectivity, algo));
+    VP_TRY(check_filter_mode(who, mode, param));
+    void *da = nullptr, *db = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
+    VP_TRY(vp_upload(ctx, da, h_words, wb));
+    VP_TRY(vp_components_filter(ctx, f, (const uint32_t*)da, (uint32_t*)db, connectivity, mode, param, algo, h_count, h_kept));
     return vp_download(ctx, h_out, db, wb);
 }
 

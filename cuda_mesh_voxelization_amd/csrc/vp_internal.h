@@ -90,6 +90,11 @@ struct vp_ctx {
     uint32_t* fill_host = nullptr;
     // ball morphology (morph.hip): the row tables of every radius (uploaded by the first tiled call) and the intermediate grid of open / close
     vp::Buffer morph_tab, morph_tmp;
+    // connected components (components.hip): root counts per block of voxels and their scan; for vp_components_filter the label volume
+    // (4 n^3 bytes, freed by vp_ctx_release), the sizes and keep flags of the K components, the arg-max winners and the kept count;
+    // the pinned host words K and kept are read back through
+    vp::Buffer comp_cnt, comp_off, comp_labels, comp_sizes, comp_keep, comp_small;
+    uint64_t* comp_host = nullptr;
     // profiling
     bool prof_on = false;
     uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
@@ -158,6 +163,11 @@ int launch_voxelize_conservative(vp_ctx* ctx, const Frame& f, uint32_t* d_words,
 int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds);
 // morph.hip: ball dilate / erode / open / close of a whole grid (enqueues only, once the context's buffers have grown)
 int launch_morph(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
+// components.hip: labels, sizes and size filters of the connected components of a whole grid; all three are blocking (counts go to the host)
+int launch_components_label(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_labels, int conn, int algo, uint32_t* h_count);
+int launch_components_sizes(vp_ctx* ctx, uint32_t n, const uint32_t* d_labels, uint32_t count, uint32_t* d_sizes);
+int launch_components_filter(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, int conn, int mode, uint32_t param, int algo,
+                             uint32_t* h_count, uint64_t* h_kept);
 int launch_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op);
 int launch_stream_copy(vp_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);   // 16 B per lane: the measured HBM copy rate
 // jfa_seed.hip

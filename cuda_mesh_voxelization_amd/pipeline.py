@@ -79,6 +79,29 @@ class Engine:
         self.ctx.morph(frame, words.data_ptr(), out.data_ptr(), op, radius, algo)
         return out
 
+    def components_label(self, frame: Frame, words, conn: int = capi.CONN_26, algo: int = ALGO_TILED, out=None):
+        """Connected components of the set voxels of a whole grid (capi.CONN_6 / CONN_26).  Returns (labels, K): an int32 tensor of n^3
+        labels, x fastest, 0 = background, components 1 .. K in the order of their lowest voxel index -- scipy.ndimage.label's
+        numbering.  Blocking."""
+        if out is None:
+            out = torch.empty(frame.voxels, dtype=torch.int32, device=self.device)
+        count = self.ctx.components_label(frame, words.data_ptr(), out.data_ptr(), conn, algo)
+        return out, count
+
+    def components_sizes(self, frame: Frame, labels, count: int):
+        """Voxels per component: an int32 tensor of `count` sizes, sizes[k - 1] for label k.  Blocking."""
+        sizes = torch.empty(max(count, 1), dtype=torch.int32, device=self.device)[:count]
+        self.ctx.components_sizes(frame, labels.data_ptr(), count, sizes.data_ptr() if count else 0)
+        return sizes
+
+    def components_filter(self, frame: Frame, words, mode: int, param: int, conn: int = capi.CONN_26, out=None, algo: int = ALGO_TILED):
+        """Size filter: capi.COMP_KEEP_LARGEST keeps the `param` (1 .. 16) largest components (ties: the lower label), capi.COMP_MIN_VOXELS
+        those with at least `param` voxels.  `out` must not be `words`.  Blocking; returns (out, K, kept voxels)."""
+        if out is None:
+            out = self.new_grid(frame)
+        count, kept = self.ctx.components_filter(frame, words.data_ptr(), out.data_ptr(), mode, param, conn, algo)
+        return out, count, kept
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

@@ -40,6 +40,14 @@ void FillDevice(const char* label, uint32_t* words, size_t n, float voxelSize, c
 // ball morphology (morph.cpp): host restatement by separable capped squared distances, and the GPU marshalling; both work in place
 void MorphHost(bool parallel, uint32_t* words, size_t n, int op, uint32_t radius);
 void MorphDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], int op, uint32_t radius);
+// connected components (components.cpp): host restatement by a scan in index order with an explicit-stack flood per component, and the
+// GPU marshalling; the filters work in place
+struct ComponentStats { uint32_t count; uint64_t kept; };      // K components found, voxels kept
+uint32_t LabelHost(bool parallel, const uint32_t* words, size_t n, uint32_t* labels, int conn);
+ComponentStats FilterHost(bool parallel, uint32_t* words, size_t n, int mode, uint32_t param, int conn);
+uint32_t LabelDevice(int algo, const char* label, const uint32_t* words, size_t n, float voxelSize, const float origin[3], uint32_t* labels, int conn);
+ComponentStats FilterDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], int mode,
+                            uint32_t param, int conn);
 }  // namespace detail
 
 template <Types type, VGType T>
@@ -132,6 +140,46 @@ void Morph(HostVoxelsGrid<T>& grid, MorphOp op, uint32_t radius)
     else
         detail::MorphDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveMorph" : "TiledMorph", words, v.VoxelsPerSide(),
                             v.VoxelSize(), origin, static_cast<int>(op), radius);
+}
+
+// LabelComponents / FilterComponents: connected components of the set voxels (include/vphip.h, vp_components_*).  conn = 6 (face
+// neighbours) or 26 (face, edge and corner neighbours); voxels outside the grid are empty.  No reference counterpart.
+//   LabelComponents   labels(x, y, z) = 0 for an empty voxel, else 1 .. K, components numbered in increasing order of their lowest linear
+//                     voxel index (scipy.ndimage.label's numbering); `labels` is resized to the grid; returns K
+//   FilterComponents  in place: ComponentFilter::KEEP_LARGEST keeps the `param` (1 .. 16) largest components, ties to the lower label;
+//                     MIN_VOXELS those of at least `param` voxels; returns {K, voxels kept}
+//   SEQUENTIAL / OPENMP   host restatement in another formulation: one scan in index order, an explicit-stack flood per component
+//   NAIVE / TILED         vp_components_label_host / vp_components_filter_host with VP_ALGO_NAIVE / VP_ALGO_TILED (n % 32 == 0, n <= 1024)
+// Every variant produces the same labels and bits.
+enum class ComponentFilter : int { KEEP_LARGEST = 0, MIN_VOXELS = 1 };     // = VP_COMP_*
+using ComponentStats = detail::ComponentStats;
+
+template <Types type, VGType T>
+uint32_t LabelComponents(const HostVoxelsGrid<T>& grid, HostGrid<uint32_t>& labels, int conn = 26)
+{
+    const auto& v = grid.View();
+    const size_t n = v.VoxelsPerSide();
+    if (labels.View().SizeX() != n || labels.View().SizeY() != n || labels.View().SizeZ() != n) labels = HostGrid<uint32_t>(n, 0u);
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(v.Data());
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        return detail::LabelHost(type == Types::OPENMP, words, n, labels.View().Data(), conn);
+    else
+        return detail::LabelDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveComponents" : "TiledComponents", words, n,
+                                   v.VoxelSize(), origin, labels.View().Data(), conn);
+}
+
+template <Types type, VGType T>
+ComponentStats FilterComponents(HostVoxelsGrid<T>& grid, ComponentFilter mode, uint32_t param, int conn = 26)
+{
+    auto& v = grid.View();
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    uint32_t* words = reinterpret_cast<uint32_t*>(v.Data());
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        return detail::FilterHost(type == Types::OPENMP, words, v.VoxelsPerSide(), static_cast<int>(mode), param, conn);
+    else
+        return detail::FilterDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveComponents" : "TiledComponents", words,
+                                    v.VoxelsPerSide(), v.VoxelSize(), origin, static_cast<int>(mode), param, conn);
 }
 
 }  // namespace VOX

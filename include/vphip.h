@@ -183,6 +183,37 @@ int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, ui
 enum { VP_MORPH_DILATE = 0, VP_MORPH_ERODE = 1, VP_MORPH_OPEN = 2, VP_MORPH_CLOSE = 3 };
 int vp_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
 
+/* ---- connected components: labels, sizes, size filters (no reference counterpart) ----------------
+ * Set voxels are the foreground, voxels outside the grid are empty.  connectivity: VP_CONN_6 (face neighbours) or VP_CONN_26 (face, edge
+ * and corner neighbours) = scipy.ndimage.generate_binary_structure(3, 1) and (3, 3).  Integer arithmetic only.
+ *   vp_components_label   d_labels: one uint32 per voxel, x fastest like the sdf (4 n^3 bytes); 0 = background; components are numbered
+ *                         1 .. K in increasing order of their lowest linear voxel index x + n (y + n z), so the volume equals
+ *                         scipy.ndimage.label(vox_zyx, structure)[0] element for element.  *h_count = K.  Needs no second volume: d_labels is
+ *                         the parent array of a lock-free union-find while the call runs.
+ *   vp_components_sizes   d_sizes[k - 1] = voxels of component k, for the `count` = K components of a label volume (labels above count are
+ *                         ignored; count = 0 writes nothing).  d_sizes holds count uint32.
+ *   vp_components_filter  bit grid -> bit grid.  VP_COMP_KEEP_LARGEST, param = m in 1 .. 16: the m largest components stay (all if K <= m;
+ *                         ties go to the lower label).  VP_COMP_MIN_VOXELS, param = v: the components with at least v voxels stay (v = 0
+ *                         and v = 1 copy the grid).  *h_count = K, *h_kept = voxels set in d_out (either may be NULL).  An empty grid gives
+ *                         K = 0 and an empty d_out, not an error.  The label volume is a grow-only buffer of the context (4 n^3 bytes:
+ *                         4 GiB at n = 1024), which vp_ctx_release frees.
+ *   Whole-grid frames only: a slab frame returns VP_ERR_UNSUPPORTED; so does n > 1024 (voxel indices need 33 bits there and the label
+ *   volume would be 32 GiB).  d_labels / d_out must not overlap d_words, and every buffer is 16-byte aligned.  Null pointers, an unknown
+ *   connectivity, mode or algo, m outside 1 .. 16: VP_ERR_INVALID.  Every refusal leaves the outputs untouched.
+ *   algo: VP_ALGO_NAIVE -- one thread per voxel, one union per set backward neighbour; VP_ALGO_TILED -- trees start as whole x runs and
+ *   the merge makes one union per pair of adjacent runs.  Same labels: a component's root is its lowest voxel index whatever the order
+ *   of execution.
+ * BLOCKING: all three return when the work is complete and the stream is idle (K and the kept count come back through a pinned host
+ * word of the context; vp_components_filter also reads K once midway, to size its per-component arrays).  They cannot be captured in a
+ * graph.  Like every writer of a grid, they drop a pending vp_jfa_start or extract count whose bytes d_labels / d_sizes / d_out overlap. */
+enum { VP_CONN_6 = 6, VP_CONN_26 = 26 };
+enum { VP_COMP_KEEP_LARGEST = 0, VP_COMP_MIN_VOXELS = 1 };
+int vp_components_label(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_labels, int connectivity, int algo,
+                        uint32_t* h_count);
+int vp_components_sizes(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_labels, uint32_t count, uint32_t* d_sizes);
+int vp_components_filter(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int connectivity, int mode,
+                         uint32_t param, int algo, uint32_t* h_count, uint64_t* h_kept);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
@@ -418,6 +449,13 @@ int vp_fill_interior_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_word
 /* vp_morph with the convention above (whole-grid frame); staged through workspace slots, so h_out may equal h_words */
 int vp_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo);
 
+/* vp_components_label / vp_components_filter with the convention above (whole-grid frame); staged through workspace slots.  h_labels holds
+ * n^3 uint32; h_out may equal h_words. */
+int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,
+                             uint32_t* h_count);
+int vp_components_filter_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int connectivity, int mode,
+                              uint32_t param, int algo, uint32_t* h_count, uint64_t* h_kept);
+
 /* ---- per-kernel timing (PROFILING_SCOPE equivalent for device time, vplib/src/profiling.h:8-33)
  * When enabled, every kernel launch is bracketed by hipEvents on the context's stream. */
 enum {
@@ -447,6 +485,17 @@ enum {
     /* vp_morph (open and close book two launches): */
     VP_K_MORPH,         /* VP_ALGO_TILED, one dilate or erode pass: 2 n^3/8 algorithmic bytes */
     VP_K_MORPH_NAIVE,   /* VP_ALGO_NAIVE, one pass */
+    /* vp_components_label (the first seven) and vp_components_sizes / vp_components_filter: */
+    VP_K_COMP_INIT,         /* TILED: every set voxel points at the start of its x run: n^3/8 read + 4 n^3 written */
+    VP_K_COMP_MERGE,        /* TILED: one union per pair of adjacent runs: up to 5 n^3/8 read + the unions (data-dependent) */
+    VP_K_COMP_INIT_NAIVE,   /* NAIVE: P[v] = v: n^3/8 + 4 n^3 */
+    VP_K_COMP_MERGE_NAIVE,  /* NAIVE: one union per set voxel and set backward neighbour: n^3/8 + the unions */
+    VP_K_COMP_FLATTEN,      /* every set voxel takes its root, roots counted per 8192 voxels: 4 n^3 read + up to 4 n^3 written */
+    VP_K_COMP_RANK,         /* scan of the n^3/8192 counts + the roots take their rank: 4 n^3 read + 4 K written */
+    VP_K_COMP_RELABEL,      /* ranks -> labels: 4 n^3 read + 4 n^3 written + one gather per set voxel */
+    VP_K_COMP_SIZES,        /* 4 n^3 read + the adds */
+    VP_K_COMP_SELECT,       /* MIN_VOXELS: 5 K; KEEP_LARGEST m: min(m, K) rounds of 4 K */
+    VP_K_COMP_WRITE,        /* 4 n^3 read + n^3/8 written + one gather per set voxel */
     VP_K_COUNT
 };
 int vp_prof_enable(vp_ctx* ctx, int on);
