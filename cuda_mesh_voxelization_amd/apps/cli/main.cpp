@@ -38,6 +38,10 @@
 //                            edge and corner neighbours; the default: the fill floods the empty phase with 6, so the set phase takes 26).
 //                            Each prints "components: K, kept: M voxels".  --conservative --morph dilate:2,fill,erode:2,largest drops
 //                            the debris of a scan and leaves the object bit for bit (open:R would round its edges)
+//         --surface-nets I   (extension, with -e) the grid meshes -- the files --surface-only affects -- hold the surface-nets mesh of the grid
+//                            (include/vphip.h, vp_surfnets): one vertex per boundary cell, two triangles per exposed voxel face, closed,
+//                            after I = 0 .. 64 relaxation steps; a smooth mesh back from a repaired grid instead of cube faces.  Not with
+//                            --surface-only.  -t 0 / -t 3: host scan; -t 1 / -t 2: the device (n <= 1024), same bytes
 //     -h, --help
 #include <cmath>
 #include <cstdint>
@@ -82,6 +86,7 @@ struct Options {
     std::string multi = "ghost";
     bool verify = false;
     bool surfaceOnly = false;
+    int surfaceNets = -1;                                   // --surface-nets ITERS: relaxation steps, -1 = not asked for
     bool conservative = false;
     bool fill = false;
     bool help = false;
@@ -161,6 +166,9 @@ const char* kUsage =
     "                        one re-deal into slabs for the last log2 <gpus> passes (<gpus> a power of two, else ghost)\n"
     "      --surface-only    With -e: the grid meshes hold only the faces between a set voxel and an unset / outside neighbour\n"
     "                        (default: the reference's mesh -- every face of every set voxel once, interior faces included)\n"
+    "      --surface-nets arg With -e: the grid meshes hold the surface-nets mesh instead -- one vertex per boundary cell, two\n"
+    "                        triangles per exposed voxel face, closed -- after <arg> = 0..64 relaxation steps that smooth the stairs\n"
+    "                        while every vertex stays inside its cell.  Not together with --surface-only; the GPU types serve n <= 1024\n"
     "      --verify          With -g > 1: run the job again on device 0 alone, compare grid and sdf bit for bit, print\n"
     "                        '# multi-gpu' lines (parity, bytes moved between devices); exit code 3 on a mismatch (extension)\n"
     "      --conservative    Surface voxelization: a voxel is set iff its closed box overlaps a triangle (any mesh, open or\n"
@@ -186,7 +194,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -228,6 +236,12 @@ Options Parse(int argc, char** argv)
             case 'd': o.dump = value; break;
             case 'g': o.gpus = static_cast<unsigned>(std::stoul(value)); break;
             case 'M': o.multi = value; break;
+            case 'N': {
+                const bool digits = !value.empty() && value.size() <= 2 && value.find_first_not_of("0123456789") == std::string::npos;
+                cpuAssert(digits && std::stoi(value) <= 64, "--surface-nets: '" + value + "' is not a number of relaxation steps in 0..64\n");
+                o.surfaceNets = std::stoi(value);
+                break;
+            }
             case 'R': o.morph = ParseMorph(value); cpuAssert(!o.morph.empty(), "--morph needs a list\n"); break;
             default: cpuAssert(false, std::string("Unknown option -") + key + "\n");
         }
@@ -285,12 +299,13 @@ void WriteRaw(const std::string& path, const void* data, size_t bytes)
 
 }  // namespace
 
-// -e: the mesh of a grid (main.cpp:118-124,192-197): the reference's compressed mesh, or (--surface-only) the visible surface alone; the GPU
-// types leave the walk over the grid to vp_extract
+// -e: the mesh of a grid (main.cpp:118-124,192-197): the reference's compressed mesh, (--surface-only) the visible surface alone, or
+// (--surface-nets I) the surface-nets mesh after I relaxation steps; the GPU types leave the walk over the grid to vp_extract / vp_surfnets
 template <typename View>
-static void GridMesh(bool gpu, bool surfaceOnly, const View& grid, Mesh& out)
+static void GridMesh(bool gpu, bool surfaceOnly, int surfaceNets, const View& grid, Mesh& out)
 {
-    if (surfaceOnly) { if (gpu) VoxelsGridToSurfaceMeshDevice(grid, out); else VoxelsGridToSurfaceMesh(grid, out); }
+    if (surfaceNets >= 0) { if (gpu) VoxelsGridToSurfaceNetsDevice(grid, static_cast<uint32_t>(surfaceNets), out); else VoxelsGridToSurfaceNets(grid, static_cast<uint32_t>(surfaceNets), out); }
+    else if (surfaceOnly) { if (gpu) VoxelsGridToSurfaceMeshDevice(grid, out); else VoxelsGridToSurfaceMesh(grid, out); }
     else             { if (gpu) VoxelsGridToMeshCompressedDevice(grid, out); else VoxelsGridToMeshCompressed(grid, out); }
 }
 
@@ -317,6 +332,8 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.conservative && opt.gpus > 1), "--conservative runs on one device: -g must be 1\n");
     cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.surfaceNets >= 0 && opt.surfaceOnly), "--surface-nets and --surface-only exclude each other: one mesh per grid file\n");
+    cpuAssert(!(opt.surfaceNets >= 0 && opt.gpus > 1), "--surface-nets runs on one device: -g must be 1\n");
     cpuAssert(opt.multi == "ghost" || opt.multi == "halo" || opt.multi == "hybrid" || opt.multi == "transpose", "--multi must be ghost, halo, hybrid or transpose");
     if (GPU && opt.gpus > 1) {
         // Z-slabs over devices 0 .. G-1.  VPLIB_SHARE_GPU=1 (test rigs with fewer devices than slabs): the slabs share the devices
@@ -392,7 +409,7 @@ int main(int argc, char** argv)
             }
             if (EXPORT) {                                                                               // main.cpp:118-124
                 Mesh outMesh;
-                GridMesh(GPU, opt.surfaceOnly, grid.View(), outMesh);
+                GridMesh(GPU, opt.surfaceOnly, opt.surfaceNets, grid.View(), outMesh);
                 cpuAssert(ExportMesh("out/" + typeName + "_" + GetFilename(opt.filenames[i]), outMesh),
                           "Error in " + typeName + " " + opt.filenames[i] + " export");
             }
@@ -410,7 +427,7 @@ int main(int argc, char** argv)
 
         if (EXPORT && OPERATION != CSG::Op::VOID) {                                                     // main.cpp:192-197
             Mesh outMesh;
-            GridMesh(GPU, opt.surfaceOnly, grids[0].View(), outMesh);
+            GridMesh(GPU, opt.surfaceOnly, opt.surfaceNets, grids[0].View(), outMesh);
             cpuAssert(ExportMesh("out/csg_vox_" + typeName + "_" + opt.output, outMesh), "Error in " + opt.output + " export (csg)");
         }
 

@@ -28,6 +28,11 @@ KERNELS = ["vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox
 COMP_KERNELS = ["comp_init", "comp_merge", "comp_init_naive", "comp_merge_naive", "comp_flatten", "comp_rank", "comp_relabel", "comp_sizes",
                 "comp_select", "comp_write"]
 PROF_KEYS = KERNELS + COMP_KERNELS
+# the timing keys of vp_surfnets_* are a second enum of the header that starts where the first ends (= VP_K_COUNT): ALL_PROF_KEYS is
+# every key in its numbering, the list prof() and prof_select() look names up in
+SURFNETS_KERNELS = ["sn_cells", "sn_scan", "sn_verts", "sn_quads", "sn_relax", "sn_cells_naive", "sn_verts_naive", "sn_quads_naive",
+                    "sn_relax_naive"]
+ALL_PROF_KEYS = PROF_KEYS + SURFNETS_KERNELS
 JFA_PASS_KEYS = ("jfa_pass", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last")
 
 # every symbol include/vphip.h declares (tests check the library exports all of them)
@@ -48,6 +53,7 @@ SYMBOLS = [
     "vp_fill_interior", "vp_fill_interior_host",
     "vp_morph", "vp_morph_host",
     "vp_components_label", "vp_components_sizes", "vp_components_filter", "vp_components_label_host", "vp_components_filter_host",
+    "vp_surfnets_count", "vp_surfnets", "vp_surfnets_host",
 ]
 
 
@@ -157,6 +163,10 @@ def lib():
         "vp_components_label_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
         "vp_components_filter_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                                      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_surfnets_count": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_surfnets": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp, _sz, _sz]),
+        "vp_surfnets_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _sz, _sz,
+                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -427,6 +437,19 @@ class Context:
         check(lib().vp_extract(self._h, ctypes.byref(frame), _vp(d_words), mode, _vp(d_sdf or None), _vp(d_records),
                                _vp(d_values or None), capacity))
 
+    def surfnets_count(self, frame: Frame, d_words: int, algo: int = ALGO_TILED):
+        """Vertices and quads of the surface-nets mesh of a whole grid: (V, Q).  Blocking."""
+        nv, nq = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().vp_surfnets_count(self._h, ctypes.byref(frame), _vp(d_words), algo, ctypes.byref(nv), ctypes.byref(nq)))
+        return int(nv.value), int(nq.value)
+
+    def surfnets(self, frame: Frame, d_words: int, algo: int, iterations: int, d_cells: int, d_xyz: int, d_quads: int,
+                 vertex_capacity: int, quad_capacity: int):
+        """After surfnets_count of the same grid and algo: V records (uint64), V x 3 float32 lattice positions after `iterations` (0 .. 64)
+        relaxation steps and Q x 4 uint32 vertex indices.  Enqueues only."""
+        check(lib().vp_surfnets(self._h, ctypes.byref(frame), _vp(d_words), algo, iterations, _vp(d_cells or None), _vp(d_xyz or None),
+                                _vp(d_quads or None), vertex_capacity, quad_capacity))
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
     def voxelize_host(self, frame: Frame, h_words, h_xyz, h_tri, algo: int = ALGO_TILED):
         check(lib().vp_voxelize_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp),
@@ -456,6 +479,20 @@ class Context:
                                               param, algo, ctypes.byref(count), ctypes.byref(kept)))
         return count.value, kept.value
 
+    def surfnets_host(self, frame: Frame, h_words, iterations: int = 0, counts_only: bool = False):
+        """numpy in, numpy out: (cells uint64[V], xyz float32[V, 3], quads uint32[Q, 4]), or (V, Q) with counts_only."""
+        np = __import__("numpy")
+        nv, nq = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().vp_surfnets_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), iterations, None, None, None, 0, 0,
+                                     ctypes.byref(nv), ctypes.byref(nq)))
+        if counts_only:
+            return int(nv.value), int(nq.value)
+        cells, xyz, quads = np.empty(nv.value, np.uint64), np.empty((nv.value, 3), np.float32), np.empty((nq.value, 4), np.uint32)
+        check(lib().vp_surfnets_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), iterations, cells.ctypes.data_as(_vp),
+                                     xyz.ctypes.data_as(_vp), quads.ctypes.data_as(_vp), cells.size, quads.shape[0],
+                                     ctypes.byref(nv), ctypes.byref(nq)))
+        return cells, xyz, quads
+
     def csg_host(self, h_a, h_b, op: int):
         check(lib().vp_csg_host(self._h, h_a.ctypes.data_as(_vp), h_b.ctypes.data_as(_vp), h_a.size, op))
 
@@ -469,7 +506,7 @@ class Context:
 
     def prof_select(self, names=None):
         """Time only the kernels whose timing keys are named (None = all): every event pair costs stream time."""
-        mask = (1 << 64) - 1 if names is None else sum(1 << PROF_KEYS.index(k) for k in names)
+        mask = (1 << 64) - 1 if names is None else sum(1 << ALL_PROF_KEYS.index(k) for k in names)
         check(lib().vp_prof_select(self._h, mask))
 
     def prof_reset(self):
@@ -477,7 +514,7 @@ class Context:
 
     def prof(self):
         out = {}
-        for i, name in enumerate(PROF_KEYS):
+        for i, name in enumerate(ALL_PROF_KEYS):
             ms = ctypes.c_double()
             n = ctypes.c_uint64()
             check(lib().vp_prof_get(self._h, i, ctypes.byref(ms), ctypes.byref(n)))

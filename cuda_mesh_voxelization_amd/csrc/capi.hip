@@ -125,16 +125,18 @@ static void grid_written(vp_ctx* ctx, const void* d_ptr, size_t bytes)
     const vp_ctx::JfaStarted& st = ctx->jfa_started;
     if (st.valid && (overlaps(d_ptr, bytes, st.words, (size_t)st.n * st.n * st.n / 8) || overlaps(d_ptr, bytes, st.work, st.work_bytes)))
         ctx->jfa_started.valid = false;
+    if (overlaps(d_ptr, bytes, ctx->sn_words, (size_t)ctx->sn_n * ctx->sn_n * ctx->sn_n / 8)) ctx->sn_words = nullptr;
 }
 
-static const char* kNames[VP_K_COUNT] = {
+static const char* kNames[VP_K_TOTAL] = {
     "vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
     "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
     "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
     "fill_x", "fill_y", "fill_z", "fill_final",
     "morph", "morph_naive",
     "comp_init", "comp_merge", "comp_init_naive", "comp_merge_naive", "comp_flatten", "comp_rank", "comp_relabel", "comp_sizes", "comp_select",
-    "comp_write"
+    "comp_write",
+    "sn_cells", "sn_scan", "sn_verts", "sn_quads", "sn_relax", "sn_cells_naive", "sn_verts_naive", "sn_quads_naive", "sn_relax_naive"
 };
 
 }  // namespace vp
@@ -182,7 +184,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
                        &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp,
-                       &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small };
+                       &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small,
+                       &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -259,8 +262,11 @@ int vp_ctx_release(vp_ctx* ctx)
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     release(ctx->jfa_work);
     release(ctx->comp_labels);                                     // vp_components_filter's label volume, 4 n^3 bytes
+    release(ctx->sn_rank);                                         // vp_surfnets' rank lookup and second position buffer
+    release(ctx->sn_xyz);
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
+    ctx->sn_words = nullptr;
     return 0;
 }
 
@@ -853,6 +859,49 @@ int vp_extract(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int mode
     return launch_extract_write(ctx, make_frame(f), d_words, mode, d_sdf, d_records, d_values, capacity);
 }
 
+// ---- surface nets ------------------------------------------------------------------------------
+// what the three vp_surfnets* entry points share: whole grids up to n = 1024
+static int check_surfnets(const vp_frame* f, const char* who)
+{
+    VP_TRY(check_frame(f, who, false));
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: cell indices are 32-bit)", who, f->n);
+    return 0;
+}
+
+int vp_surfnets_count(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint64_t* h_vertices, uint64_t* h_quads)
+{
+    const char* who = "vp_surfnets_count";
+    if (!ctx || !d_words || !h_vertices || !h_quads) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_surfnets(f, who));
+    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    VP_TRY(check_aligned(who, {d_words}));
+    return launch_surfnets_count(ctx, f->n, d_words, algo, h_vertices, h_quads);
+}
+
+int vp_surfnets(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint32_t iterations, uint64_t* d_cells, float* d_xyz,
+                uint32_t* d_quads, size_t vertex_capacity, size_t quad_capacity)
+{
+    const char* who = "vp_surfnets";
+    if (!ctx || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_surfnets(f, who));
+    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    if (iterations > 64) return set_error(VP_ERR_INVALID, "%s: %u iterations (0 .. 64)", who, iterations);
+    if (ctx->sn_words != d_words || ctx->sn_algo != algo || ctx->sn_n != f->n)
+        return set_error(VP_ERR_INVALID, "%s: call vp_surfnets_count with the same grid and algo first", who);
+    if (vertex_capacity < ctx->sn_vertices || quad_capacity < ctx->sn_quads)
+        return set_error(VP_ERR_INVALID, "%s: capacity %zu vertices / %zu quads, the grid has %llu / %llu", who, vertex_capacity, quad_capacity,
+                         (unsigned long long)ctx->sn_vertices, (unsigned long long)ctx->sn_quads);
+    if ((ctx->sn_vertices && (!d_cells || !d_xyz)) || (ctx->sn_quads && !d_quads)) return set_error(VP_ERR_INVALID, "%s: null output", who);
+    const size_t gb = vp_grid_words(f) * 4, cb = (size_t)ctx->sn_vertices * 8, xb = (size_t)ctx->sn_vertices * 12, qb = (size_t)ctx->sn_quads * 16;
+    if (overlaps(d_words, gb, d_cells, cb) || overlaps(d_words, gb, d_xyz, xb) || overlaps(d_words, gb, d_quads, qb))
+        return set_error(VP_ERR_INVALID, "%s: an output overlaps d_words", who);
+    grid_written(ctx, d_cells, cb); grid_written(ctx, d_xyz, xb); grid_written(ctx, d_quads, qb);     // writes like any other (not to this grid)
+    return launch_surfnets_write(ctx, f->n, d_words, algo, iterations, d_cells, d_xyz, d_quads);
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -951,6 +1000,37 @@ int vp_components_filter_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_
     return vp_download(ctx, h_out, db, wb);
 }
 
+int vp_surfnets_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t iterations, uint64_t* h_cells, float* h_xyz,
+                     uint32_t* h_quads, size_t vertex_capacity, size_t quad_capacity, uint64_t* h_vertices, uint64_t* h_quads_out)
+{
+    const char* who = "vp_surfnets_host";
+    if (!ctx || !h_words || !h_vertices || !h_quads_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_surfnets(f, who));
+    if (iterations > 64) return set_error(VP_ERR_INVALID, "%s: %u iterations (0 .. 64)", who, iterations);
+    const bool counts_only = !h_cells && !h_xyz && !h_quads;
+    if (!counts_only && (!h_cells || !h_xyz || !h_quads)) return set_error(VP_ERR_INVALID, "%s: the three outputs go together", who);
+    void *dw = nullptr, *dc = nullptr, *dx = nullptr, *dq = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
+    VP_TRY(vp_upload(ctx, dw, h_words, wb));
+    uint64_t nv = 0, nq = 0;
+    VP_TRY(vp_surfnets_count(ctx, f, (const uint32_t*)dw, VP_ALGO_TILED, &nv, &nq));
+    if (!counts_only && (vertex_capacity < nv || quad_capacity < nq))
+        return set_error(VP_ERR_INVALID, "%s: capacity %zu vertices / %zu quads, the grid has %llu / %llu", who, vertex_capacity, quad_capacity,
+                         (unsigned long long)nv, (unsigned long long)nq);
+    if (!counts_only && nv) {
+        VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, nv * 8, &dc));         // the grid stays in slot A, so the count stands
+        VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nv * 12, &dx));
+        VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, nq * 16, &dq));
+        VP_TRY(vp_surfnets(ctx, f, (const uint32_t*)dw, VP_ALGO_TILED, iterations, (uint64_t*)dc, (float*)dx, (uint32_t*)dq, nv, nq));
+        VP_TRY(vp_download(ctx, h_cells, dc, nv * 8));
+        VP_TRY(vp_download(ctx, h_xyz, dx, nv * 12));
+        VP_TRY(vp_download(ctx, h_quads, dq, nq * 16));
+    }
+    *h_vertices = nv; *h_quads_out = nq;
+    return 0;
+}
+
 int vp_csg_host(vp_ctx* ctx, uint32_t* h_a, const uint32_t* h_b, size_t nwords, int op)
 {
     if (!ctx || ((!h_a || !h_b) && nwords)) return set_error(VP_ERR_INVALID, "vp_csg_host: null argument");
@@ -998,13 +1078,13 @@ int vp_prof_reset(vp_ctx* ctx)
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_prof_reset: null ctx");
     VP_TRY(bind_device(ctx));
     VP_TRY(prof_fold(ctx));
-    for (int i = 0; i < VP_K_COUNT; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
+    for (int i = 0; i < VP_K_TOTAL; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
     return 0;
 }
 
 int vp_prof_get(vp_ctx* ctx, int kernel, double* total_ms, uint64_t* launches)
 {
-    if (!ctx || kernel < 0 || kernel >= VP_K_COUNT) return set_error(VP_ERR_INVALID, "vp_prof_get: bad argument");
+    if (!ctx || kernel < 0 || kernel >= VP_K_TOTAL) return set_error(VP_ERR_INVALID, "vp_prof_get: bad argument");
     VP_TRY(bind_device(ctx));
     VP_TRY(prof_fold(ctx));
     if (total_ms) *total_ms = ctx->prof_ms[kernel];
@@ -1012,6 +1092,6 @@ int vp_prof_get(vp_ctx* ctx, int kernel, double* total_ms, uint64_t* launches)
     return 0;
 }
 
-const char* vp_prof_name(int kernel) { return (kernel >= 0 && kernel < VP_K_COUNT) ? kNames[kernel] : "?"; }
+const char* vp_prof_name(int kernel) { return (kernel >= 0 && kernel < VP_K_TOTAL) ? kNames[kernel] : "?"; }
 
 }  // extern "C"

@@ -95,13 +95,21 @@ struct vp_ctx {
     // the pinned host words K and kept are read back through
     vp::Buffer comp_cnt, comp_off, comp_labels, comp_sizes, comp_keep, comp_small;
     uint64_t* comp_host = nullptr;
+    // surface nets (surfnets.hip): block counts of vertices and quads and their scans; the rank lookup -- NAIVE: the vertex-index volume,
+    // 4 (n+1)^3 bytes; TILED: active-cell bits + one exclusive count per word, about n^3/4 bytes -- and the second position buffer of the
+    // relaxation (sn_rank and sn_xyz are freed by vp_ctx_release); what the last vp_surfnets_count was for
+    vp::Buffer sn_cnt, sn_off, sn_rank, sn_xyz;
+    const uint32_t* sn_words = nullptr;
+    uint32_t sn_n = 0;
+    int sn_algo = 0;
+    uint64_t sn_vertices = 0, sn_quads = 0;
     // profiling
     bool prof_on = false;
     uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
     std::vector<vp::ProfSpan> prof_pending;
     std::vector<hipEvent_t> prof_pool;
-    double prof_ms[VP_K_COUNT] = {};
-    uint64_t prof_n[VP_K_COUNT] = {};
+    double prof_ms[VP_K_TOTAL] = {};
+    uint64_t prof_n[VP_K_TOTAL] = {};
 };
 
 namespace vp {
@@ -168,6 +176,11 @@ int launch_components_label(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, ui
 int launch_components_sizes(vp_ctx* ctx, uint32_t n, const uint32_t* d_labels, uint32_t count, uint32_t* d_sizes);
 int launch_components_filter(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, int conn, int mode, uint32_t param, int algo,
                              uint32_t* h_count, uint64_t* h_kept);
+// surfnets.hip: count (blocking: V and Q go to the host) and write (vertices, quads, `iterations` relaxation steps; enqueues only, once the
+// context's buffers have grown) of the surface-nets mesh of a whole grid
+int launch_surfnets_count(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int algo, uint64_t* h_vertices, uint64_t* h_quads);
+int launch_surfnets_write(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int algo, uint32_t iterations, uint64_t* d_cells, float* d_xyz,
+                          uint32_t* d_quads);
 int launch_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op);
 int launch_stream_copy(vp_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);   // 16 B per lane: the measured HBM copy rate
 // jfa_seed.hip

@@ -102,6 +102,18 @@ class Engine:
         count, kept = self.ctx.components_filter(frame, words.data_ptr(), out.data_ptr(), mode, param, conn, algo)
         return out, count, kept
 
+    def surface_nets(self, frame: Frame, words, iterations: int = 0, algo: int = ALGO_TILED):
+        """Surface-nets mesh of a whole grid (n <= 1024): one vertex per boundary cell, one quad per exposed voxel face, closed.  Returns
+        device tensors (cells int64[V]: cell index | corner mask << 40; xyz float32[V, 3]: lattice coordinates after `iterations` (0 .. 64)
+        relaxation steps; quads int32[Q, 4]: vertex indices, outward winding).  Blocking (the counts size the tensors)."""
+        nv, nq = self.ctx.surfnets_count(frame, words.data_ptr(), algo)
+        cells = torch.empty(nv, dtype=torch.int64, device=self.device)
+        xyz = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+        quads = torch.empty((nq, 4), dtype=torch.int32, device=self.device)
+        self.ctx.surfnets(frame, words.data_ptr(), algo, iterations, cells.data_ptr() if nv else 0, xyz.data_ptr() if nv else 0,
+                          quads.data_ptr() if nq else 0, nv, nq)
+        return cells, xyz, quads
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

@@ -214,6 +214,51 @@ int vp_components_sizes(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_labels
 int vp_components_filter(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int connectivity, int mode,
                          uint32_t param, int algo, uint32_t* h_count, uint64_t* h_kept);
 
+/* ---- surface nets: a closed quad mesh from a bit grid (Gibson 1998; no reference counterpart) ----------------
+ * Grid and cells.  Voxel (x, y, z) occupies the lattice cube [x, x+1]^3, its centre is at x + 0.5; voxels outside the grid are empty.  A
+ * CELL (cx, cy, cz), each coordinate in -1 .. n-1, is the cube whose eight corners are the centres of the voxels (cx+dx, cy+dy, cz+dz),
+ * d in {0, 1}: (n+1)^3 cells, linear cell index (cx+1) + (n+1) ((cy+1) + (n+1) (cz+1)).  Bit dx + 2 dy + 4 dz of the 8-bit CORNER MASK is
+ * set iff that voxel is set; a cell is ACTIVE iff its mask is neither 0 nor 255.
+ * Vertices.  One per active cell, numbered 0 .. V-1 in increasing linear cell index.  Record (d_cells): cell index | corner mask << 40,
+ * the shape of the vp_extract record.
+ * Positions (d_xyz): float32 x 3 per vertex, in LATTICE coordinates (voxel units; the frame's origin and voxel size are not applied).
+ * Before relaxation, over the cell's twelve edges in local coordinates 0 .. 1: m = the edges whose two corners differ, S_a = the sum over
+ * those edges of twice the midpoint's coordinate a (each term 0, 1 or 2);  p_a = ((float)c_a + 0.5f) + (float)S_a / (float)(2 m) -- the
+ * correctly rounded float quotient, then one float add.  Every component lies strictly inside (c_a + 0.5, c_a + 1.5).
+ * Quads (d_quads): uint32 x 4 vertex indices, one quad per pair of face-adjacent voxels of which exactly one is set (outside = unset).
+ * The quad is owned by the cell that has the edge between the two voxel centres as one of the three edges leaving its corner 0 towards
+ * +x, +y or +z (always active, always inside the cell range); quads are ordered by owner cell index, then by axis x, y, z.  With the
+ * owner (i, j, k) = (cx, cy, cz) the four vertices are those of the cells
+ *     x-edge: (i, j-1, k-1), (i, j, k-1), (i, j, k), (i, j-1, k)
+ *     y-edge: (i-1, j, k-1), (i-1, j, k), (i, j, k), (i, j, k-1)
+ *     z-edge: (i-1, j-1, k), (i, j-1, k), (i, j, k), (i-1, j, k)
+ * in that order when the LOWER voxel of the pair is the set one (the outward normal points along + axis), reversed (d, c, b, a) when the
+ * upper one is.  Triangles, where needed, are (a, b, c) and (a, c, d).  Q equals the number of faces vp_extract reports in
+ * VP_EXTRACT_EXPOSED mode; the surface is closed: every directed edge (a, b) occurs as often as (b, a).
+ * Relaxation.  iterations = 0 .. 64 Jacobi steps (each reads the previous buffer and writes the other).  The neighbours of a vertex are
+ * the cells across the faces -x, +x, -y, +y, -z, +z, in that order; a neighbour across a face exists iff that face's four corners are
+ * mixed (both cells are then active; an active cell has at least two such faces).  Per component: acc = the first neighbour's value, the
+ * others added left to right in float; q = acc / (float)deg, correctly rounded; then q = min(max(q, lo), hi) with lo = (float)c_a +
+ * 0.5625f, hi = (float)c_a + 1.4375f -- the cell shrunk by 1/16, exact in float for every served n.  Vertices never leave their cell.
+ * Every operation is one IEEE operation in a prescribed order (the library is built with -ffp-contract=off), so records, quads and
+ * positions are the same bits for both algos and for the host restatement.
+ *   vp_surfnets_count   *h_vertices = V, *h_quads = Q.  BLOCKING (the totals are read back); cannot be captured in a graph.
+ *   vp_surfnets         writes V records, V positions and Q quads and runs the relaxation; the result ends in d_xyz for any iteration
+ *                       count.  It must follow a vp_surfnets_count of the same grid CONTENTS, frame side and algo ("same grid" as for
+ *                       vp_extract: the count is dropped as soon as the grid is written through this ABI); otherwise, or with a capacity
+ *                       below V / Q: VP_ERR_INVALID.  Enqueues only, once the context's buffers have grown.  The outputs must not overlap
+ *                       d_words; d_cells / d_xyz / d_quads may be NULL only when V (Q) is 0.
+ * Scratch memory is the context's: the rank lookup (VP_ALGO_NAIVE: a uint32 vertex-index volume, 4 (n+1)^3 bytes -- 4.3 GB at n = 1024;
+ * VP_ALGO_TILED: active-cell bits and one exclusive count per 32 cells, about n^3/4 bytes) and the second position buffer (12 V bytes),
+ * grow-only, freed by vp_ctx_release.
+ * Whole-grid frames only: a slab frame returns VP_ERR_UNSUPPORTED; so does n > 1024 ((n+1)^3 stays below 2^31).  Null pointers, an unknown
+ * algo and iterations > 64: VP_ERR_INVALID.  Every refusal leaves the outputs untouched.
+ *   algo: VP_ALGO_NAIVE -- one thread per cell reads its eight voxel bits one by one; VP_ALGO_TILED -- one lane per 32 cells of a cell row,
+ *   corner words from two words of each of four voxel rows.  Same bytes. */
+int vp_surfnets_count(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint64_t* h_vertices, uint64_t* h_quads);
+int vp_surfnets(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint32_t iterations, uint64_t* d_cells, float* d_xyz,
+                uint32_t* d_quads, size_t vertex_capacity, size_t quad_capacity);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
@@ -456,6 +501,12 @@ int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_w
 int vp_components_filter_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int connectivity, int mode,
                               uint32_t param, int algo, uint32_t* h_count, uint64_t* h_kept);
 
+/* vp_surfnets_count + vp_surfnets (VP_ALGO_TILED) with the convention above (whole-grid frame); staged through workspace slots.
+ * *h_vertices = V and *h_quads_out = Q always; h_cells = h_xyz = h_quads = NULL: counts only; otherwise all three are written, and a
+ * capacity below V / Q is VP_ERR_INVALID (the counts are not stored then). */
+int vp_surfnets_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t iterations, uint64_t* h_cells, float* h_xyz,
+                     uint32_t* h_quads, size_t vertex_capacity, size_t quad_capacity, uint64_t* h_vertices, uint64_t* h_quads_out);
+
 /* ---- per-kernel timing (PROFILING_SCOPE equivalent for device time, vplib/src/profiling.h:8-33)
  * When enabled, every kernel launch is bracketed by hipEvents on the context's stream. */
 enum {
@@ -497,6 +548,19 @@ enum {
     VP_K_COMP_SELECT,       /* MIN_VOXELS: 5 K; KEEP_LARGEST m: min(m, K) rounds of 4 K */
     VP_K_COMP_WRITE,        /* 4 n^3 read + n^3/8 written + one gather per set voxel */
     VP_K_COUNT
+};
+/* the keys of vp_surfnets_count / vp_surfnets follow the enum above (bit i of vp_prof_select = key i, 64 at the most) */
+enum {
+    VP_K_SN_CELLS = VP_K_COUNT, /* TILED, count: corner words -> active-cell bits + block counts: about 2 n^3/8 */
+    VP_K_SN_SCAN,               /* both algos: one-workgroup scan of the two block-count arrays */
+    VP_K_SN_VERTS,              /* TILED: per-word exclusive counts, records, starting positions: n^3/8 read, n^3/8 + 20 V written */
+    VP_K_SN_QUADS,              /* TILED: n^3/8 read + four rank gathers per quad, 16 Q written */
+    VP_K_SN_RELAX,              /* TILED, one Jacobi step: 20 V read + up to six gathers per vertex, 12 V written */
+    VP_K_SN_CELLS_NAIVE,        /* NAIVE, count: eight bit reads per cell */
+    VP_K_SN_VERTS_NAIVE,        /* NAIVE: index volume 4 (n+1)^3 written + 20 V */
+    VP_K_SN_QUADS_NAIVE,        /* NAIVE: four index reads per quad, 16 Q written */
+    VP_K_SN_RELAX_NAIVE,        /* NAIVE, one Jacobi step */
+    VP_K_TOTAL
 };
 int vp_prof_enable(vp_ctx* ctx, int on);
 /* Restricts the bracketing to the keys whose bit is set (bit i = key i; default: all).  An event pair costs ~3 us of stream
