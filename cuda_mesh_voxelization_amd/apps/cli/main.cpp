@@ -38,6 +38,10 @@
 //                            edge and corner neighbours; the default: the fill floods the empty phase with 6, so the set phase takes 26).
 //                            Each prints "components: K, kept: M voxels".  --conservative --morph dilate:2,fill,erode:2,largest drops
 //                            the debris of a scan and leaves the object bit for bit (open:R would round its edges)
+//                            offset:R and inset:R are dilate and erode through the exact distance transform (include/vphip.h,
+//                            vp_edt_morph): any R = 0 .. 65535, the same bits as dilate:R / erode:R where those are served
+//         --exact-sdf        (extension, with -s) the field is the exact squared distance to the border voxels (include/vphip.h,
+//                            vp_edt_sdf) instead of the Jump Flooding approximation: same sign, same zeros, never larger.  One device only
 //         --surface-nets I   (extension, with -e) the grid meshes -- the files --surface-only affects -- hold the surface-nets mesh of the grid
 //                            (include/vphip.h, vp_surfnets): one vertex per boundary cell, two triangles per exposed voxel face, closed,
 //                            after I = 0 .. 64 relaxation steps; a smooth mesh back from a repaired grid instead of cube faces.  Not with
@@ -89,17 +93,19 @@ struct Options {
     int surfaceNets = -1;                                   // --surface-nets ITERS: relaxation steps, -1 = not asked for
     bool conservative = false;
     bool fill = false;
+    bool exactSdf = false;
     bool help = false;
-    // op = VOX::MorphOp, or -1: the interior fill, -2: largest component, -3: minsize (value = V); conn = 6 / 26 for the last two
+    // op = VOX::MorphOp, 4 / 5: offset / inset (dilate / erode through the distance transform), or -1: the interior fill, -2: largest
+    // component, -3: minsize (value = V); conn = 6 / 26 for the last two
     struct MorphStep { int op; unsigned radius; unsigned value = 0; int conn = 26; };
     std::vector<MorphStep> morph;
 };
 
-// --morph LIST: dilate:R,erode:R,open:R,close:R,fill with R = 0 .. 32, largest[:C] and minsize:V[:C] with C = 6 or 26; anything else is a
-// usage error
+// --morph LIST: dilate:R,erode:R,open:R,close:R,fill with R = 0 .. 32, offset:R,inset:R with R = 0 .. 65535, largest[:C] and minsize:V[:C]
+// with C = 6 or 26; anything else is a usage error
 std::vector<Options::MorphStep> ParseMorph(const std::string& list)
 {
-    static const char* names[] = {"dilate", "erode", "open", "close"};
+    static const char* names[] = {"dilate", "erode", "open", "close", "offset", "inset"};
     std::vector<Options::MorphStep> steps;
     size_t pos = 0;
     while (true) {
@@ -129,12 +135,13 @@ std::vector<Options::MorphStep> ParseMorph(const std::string& list)
             const size_t colon = item.find(':');
             int op = -1;
             if (colon != std::string::npos)
-                for (int k = 0; k < 4; ++k) if (item.substr(0, colon) == names[k]) op = k;
+                for (int k = 0; k < 6; ++k) if (item.substr(0, colon) == names[k]) op = k;
             const std::string num = colon == std::string::npos ? "" : item.substr(colon + 1);
-            const bool digits = !num.empty() && num.size() <= 2 && num.find_first_not_of("0123456789") == std::string::npos;
-            cpuAssert(op >= 0 && digits, "--morph: bad step '" + item + "' (dilate:R, erode:R, open:R, close:R, fill, largest[:C] or minsize:V[:C])\n");
+            const bool exact = op >= 4;                                              // offset / inset: through the distance transform
+            const bool digits = !num.empty() && num.size() <= (exact ? 5u : 2u) && num.find_first_not_of("0123456789") == std::string::npos;
+            cpuAssert(op >= 0 && digits, "--morph: bad step '" + item + "' (dilate:R, erode:R, open:R, close:R, offset:R, inset:R, fill, largest[:C] or minsize:V[:C])\n");
             const unsigned radius = static_cast<unsigned>(std::stoul(num));
-            cpuAssert(radius <= 32, "--morph: radius " + num + " outside 0..32\n");
+            cpuAssert(radius <= (exact ? 65535u : 32u), "--morph: radius " + num + (exact ? " outside 0..65535\n" : " outside 0..32\n"));
             steps.push_back({op, radius});
         }
         if (comma == std::string::npos) break;
@@ -187,6 +194,10 @@ const char* kUsage =
     "                        the default); each prints 'components: K, kept: M voxels'.  E.g. --conservative --morph\n"
     "                        dilate:2,fill,erode:2,largest removes floating debris and leaves the object bit for bit.\n"
     "                        One device only: not with -g > 1 (extension)\n"
+    "                        offset:R and inset:R are dilate and erode through the exact distance transform: any radius\n"
+    "                        R = 0..65535, e.g. --conservative --morph offset:40,fill,inset:40 for holes up to about 80 voxels wide\n"
+    "      --exact-sdf       With -s: the exact squared distance to the border voxels instead of the Jump Flooding approximation\n"
+    "                        (same sign, same zeros, never larger).  One device only: not with -g > 1 (extension)\n"
     "  -h, --help            Print usage\n";
 
 // Minimal getopt-style parser: -x V, -xV, --long V, --long=V, boolean switches, positionals.
@@ -194,7 +205,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -215,10 +226,10 @@ Options Parse(int argc, char** argv)
             o.filenames.push_back(a);
             continue;
         }
-        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F';
+        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X';
         if (isSwitch) {
             const bool v = !hasValue || value == "true" || value == "1";
-            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else o.help = v;
+            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else if (key == 'X') o.exactSdf = v; else o.help = v;
             continue;
         }
         if (!hasValue) {
@@ -272,6 +283,8 @@ void MorphSteps(const std::vector<Options::MorphStep>& steps, HostVoxelsGrid<gri
             const VOX::ComponentStats cs = st.op == -2 ? VOX::FilterComponents<T>(grid, VOX::ComponentFilter::KEEP_LARGEST, 1u, st.conn)
                                                        : VOX::FilterComponents<T>(grid, VOX::ComponentFilter::MIN_VOXELS, st.value, st.conn);
             std::printf("components: %u, kept: %llu voxels\n", cs.count, static_cast<unsigned long long>(cs.kept));
+        } else if (st.op >= 4) {
+            VOX::MorphExact<T>(grid, st.op == 4 ? VOX::MorphOp::DILATE : VOX::MorphOp::ERODE, st.radius);
         } else {
             VOX::Morph<T>(grid, static_cast<VOX::MorphOp>(st.op), st.radius);
         }
@@ -332,6 +345,8 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.conservative && opt.gpus > 1), "--conservative runs on one device: -g must be 1\n");
     cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.exactSdf && !opt.sdf), "--exact-sdf needs -s: it chooses how the distance field is computed\n");
+    cpuAssert(!(opt.exactSdf && opt.gpus > 1), "--exact-sdf runs on one device: -g must be 1\n");
     cpuAssert(!(opt.surfaceNets >= 0 && opt.surfaceOnly), "--surface-nets and --surface-only exclude each other: one mesh per grid file\n");
     cpuAssert(!(opt.surfaceNets >= 0 && opt.gpus > 1), "--surface-nets runs on one device: -g must be 1\n");
     cpuAssert(opt.multi == "ghost" || opt.multi == "halo" || opt.multi == "hybrid" || opt.multi == "transpose", "--multi must be ghost, halo, hybrid or transpose");
@@ -433,7 +448,14 @@ int main(int argc, char** argv)
 
         if (opt.sdf) {
             sdf = HostGrid<float>(N, -INFINITY);                                                        // main.cpp:200
-            switch (TYPE) {
+            if (opt.exactSdf) {
+                switch (TYPE) {
+                    case Types::SEQUENTIAL: JFA::ComputeExact<Types::SEQUENTIAL>(grids[0], sdf); break;
+                    case Types::OPENMP:     JFA::ComputeExact<Types::OPENMP>(grids[0], sdf); break;
+                    case Types::NAIVE:      JFA::ComputeExact<Types::NAIVE>(grids[0], sdf); break;
+                    case Types::TILED:      JFA::ComputeExact<Types::TILED>(grids[0], sdf); break;
+                }
+            } else switch (TYPE) {
                 case Types::SEQUENTIAL: JFA::Compute<Types::SEQUENTIAL>(grids[0], sdf); break;
                 case Types::OPENMP:     JFA::Compute<Types::OPENMP>(grids[0], sdf); break;
                 case Types::NAIVE:      JFA::Compute<Types::NAIVE>(grids[0], sdf); break;

@@ -14,6 +14,8 @@ HOOKS_LIB_PATH = os.path.join(PKG, "libvphip_hooks.so")
 ALGO_NAIVE, ALGO_TILED = 1, 2
 OP_VOID, OP_UNION, OP_INTERSECTION, OP_DIFFERENCE = 0, 1, 2, 3
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3     # vp_morph: ball morphology
+EDT_SEEDS_SET, EDT_SEEDS_UNSET, EDT_SEEDS_BORDER = 0, 1, 2              # vp_edt: which voxels the distances are measured to
+EDT_NONE = 0xFFFFFFFF                                               # vp_edt: "the grid has no seed"
 CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
 COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
@@ -33,6 +35,10 @@ PROF_KEYS = KERNELS + COMP_KERNELS
 SURFNETS_KERNELS = ["sn_cells", "sn_scan", "sn_verts", "sn_quads", "sn_relax", "sn_cells_naive", "sn_verts_naive", "sn_quads_naive",
                     "sn_relax_naive"]
 ALL_PROF_KEYS = PROF_KEYS + SURFNETS_KERNELS
+# the timing keys of vp_edt* are a third enum that starts where the second ends (= VP_K_TOTAL): EVERY_PROF_KEY is every key of the header
+# (VP_K_END of them) in its numbering -- what prof() and prof_select() look names up in
+EDT_KERNELS = ["edt_x", "edt_y", "edt_z", "edt_y_naive", "edt_z_naive", "edt_sdf", "edt_thresh"]
+EVERY_PROF_KEY = ALL_PROF_KEYS + EDT_KERNELS
 JFA_PASS_KEYS = ("jfa_pass", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last")
 
 # every symbol include/vphip.h declares (tests check the library exports all of them)
@@ -54,6 +60,7 @@ SYMBOLS = [
     "vp_morph", "vp_morph_host",
     "vp_components_label", "vp_components_sizes", "vp_components_filter", "vp_components_label_host", "vp_components_filter_host",
     "vp_surfnets_count", "vp_surfnets", "vp_surfnets_host",
+    "vp_edt", "vp_edt_sdf", "vp_edt_morph", "vp_edt_host", "vp_edt_sdf_host", "vp_edt_morph_host",
 ]
 
 
@@ -167,6 +174,12 @@ def lib():
         "vp_surfnets": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp, _sz, _sz]),
         "vp_surfnets_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _sz, _sz,
                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_edt": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
+        "vp_edt_sdf": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_float, _vp, ctypes.c_int]),
+        "vp_edt_morph": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
+        "vp_edt_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
+        "vp_edt_sdf_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_float, _vp, ctypes.c_int]),
+        "vp_edt_morph_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -297,6 +310,19 @@ class Context:
     def morph(self, frame: Frame, d_words: int, d_out: int, op: int, radius: int, algo: int = ALGO_TILED):
         """Ball morphology (MORPH_DILATE / ERODE / OPEN / CLOSE, integer radius 0 .. 32): d_out = op(d_words).  Enqueues only."""
         check(lib().vp_morph(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), op, radius, algo))
+
+    def edt(self, frame: Frame, d_words: int, d_dist2: int, seeds: int = EDT_SEEDS_SET, algo: int = ALGO_TILED):
+        """Exact squared voxel distance to the nearest seed (EDT_SEEDS_SET / UNSET / BORDER): d_dist2 takes one uint32 per voxel, x fastest;
+        EDT_NONE everywhere if the grid has no seed.  Enqueues only."""
+        check(lib().vp_edt(self._h, ctypes.byref(frame), _vp(d_words), seeds, _vp(d_dist2), algo))
+
+    def edt_sdf(self, frame: Frame, d_words: int, fill: float, d_sdf: int, algo: int = ALGO_TILED):
+        """The exact counterpart of jfa(): signed squared distance to the border voxels, +inside, -outside.  Enqueues only."""
+        check(lib().vp_edt_sdf(self._h, ctypes.byref(frame), _vp(d_words), fill, _vp(d_sdf), algo))
+
+    def edt_morph(self, frame: Frame, d_words: int, d_out: int, op: int, radius: int, algo: int = ALGO_TILED):
+        """morph() through the distance transform: any integer radius 0 .. 65535.  Enqueues only."""
+        check(lib().vp_edt_morph(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), op, radius, algo))
 
     def components_label(self, frame: Frame, d_words: int, d_labels: int, conn: int = CONN_26, algo: int = ALGO_TILED) -> int:
         """Connected components of the set voxels (CONN_6 / CONN_26): d_labels takes one uint32 per voxel, 0 = background, components
@@ -467,6 +493,15 @@ class Context:
     def morph_host(self, frame: Frame, h_words, h_out, op: int, radius: int, algo: int = ALGO_TILED):
         check(lib().vp_morph_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp), op, radius, algo))
 
+    def edt_host(self, frame: Frame, h_words, h_dist2, seeds: int = EDT_SEEDS_SET, algo: int = ALGO_TILED):
+        check(lib().vp_edt_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), seeds, h_dist2.ctypes.data_as(_vp), algo))
+
+    def edt_sdf_host(self, frame: Frame, h_words, fill: float, h_sdf, algo: int = ALGO_TILED):
+        check(lib().vp_edt_sdf_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), fill, h_sdf.ctypes.data_as(_vp), algo))
+
+    def edt_morph_host(self, frame: Frame, h_words, h_out, op: int, radius: int, algo: int = ALGO_TILED):
+        check(lib().vp_edt_morph_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp), op, radius, algo))
+
     def components_label_host(self, frame: Frame, h_words, h_labels, conn: int = CONN_26, algo: int = ALGO_TILED) -> int:
         count = ctypes.c_uint32()
         check(lib().vp_components_label_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_labels.ctypes.data_as(_vp), conn, algo,
@@ -506,7 +541,7 @@ class Context:
 
     def prof_select(self, names=None):
         """Time only the kernels whose timing keys are named (None = all): every event pair costs stream time."""
-        mask = (1 << 64) - 1 if names is None else sum(1 << ALL_PROF_KEYS.index(k) for k in names)
+        mask = (1 << 64) - 1 if names is None else sum(1 << EVERY_PROF_KEY.index(k) for k in names)
         check(lib().vp_prof_select(self._h, mask))
 
     def prof_reset(self):
@@ -514,7 +549,7 @@ class Context:
 
     def prof(self):
         out = {}
-        for i, name in enumerate(ALL_PROF_KEYS):
+        for i, name in enumerate(EVERY_PROF_KEY):
             ms = ctypes.c_double()
             n = ctypes.c_uint64()
             check(lib().vp_prof_get(self._h, i, ctypes.byref(ms), ctypes.byref(n)))

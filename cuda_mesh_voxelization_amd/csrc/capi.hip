@@ -128,7 +128,7 @@ static void grid_written(vp_ctx* ctx, const void* d_ptr, size_t bytes)
     if (overlaps(d_ptr, bytes, ctx->sn_words, (size_t)ctx->sn_n * ctx->sn_n * ctx->sn_n / 8)) ctx->sn_words = nullptr;
 }
 
-static const char* kNames[VP_K_TOTAL] = {
+static const char* kNames[VP_K_END] = {
     "vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
     "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
     "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
@@ -136,7 +136,8 @@ static const char* kNames[VP_K_TOTAL] = {
     "morph", "morph_naive",
     "comp_init", "comp_merge", "comp_init_naive", "comp_merge_naive", "comp_flatten", "comp_rank", "comp_relabel", "comp_sizes", "comp_select",
     "comp_write",
-    "sn_cells", "sn_scan", "sn_verts", "sn_quads", "sn_relax", "sn_cells_naive", "sn_verts_naive", "sn_quads_naive", "sn_relax_naive"
+    "sn_cells", "sn_scan", "sn_verts", "sn_quads", "sn_relax", "sn_cells_naive", "sn_verts_naive", "sn_quads_naive", "sn_relax_naive",
+    "edt_x", "edt_y", "edt_z", "edt_y_naive", "edt_z_naive", "edt_sdf", "edt_thresh"
 };
 
 }  // namespace vp
@@ -185,7 +186,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
                        &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp,
                        &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small,
-                       &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz };
+                       &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz, &ctx->edt_mask, &ctx->edt_vol, &ctx->edt_vol2, &ctx->edt_tmp };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -264,6 +265,10 @@ int vp_ctx_release(vp_ctx* ctx)
     release(ctx->comp_labels);                                     // vp_components_filter's label volume, 4 n^3 bytes
     release(ctx->sn_rank);                                         // vp_surfnets' rank lookup and second position buffer
     release(ctx->sn_xyz);
+    release(ctx->edt_mask);                                        // vp_edt*'s border mask, distance volumes and intermediate grid
+    release(ctx->edt_vol);
+    release(ctx->edt_vol2);
+    release(ctx->edt_tmp);
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -372,6 +377,75 @@ int vp_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* 
     if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
     grid_written(ctx, d_out, bytes);
     return launch_morph(ctx, f->n, d_words, d_out, op, radius, algo);
+}
+
+static int check_fill(float fill, const char* who);
+
+// what vp_edt, vp_edt_sdf and vp_edt_morph share: whole grids up to n = 1024, the algo
+static int check_edt(const vp_frame* f, const char* who, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: the distance volume would be 32 GiB)", who, f->n);
+    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    return 0;
+}
+
+static int check_edt_seeds(const char* who, int seeds)
+{
+    if (seeds != VP_EDT_SEEDS_SET && seeds != VP_EDT_SEEDS_UNSET && seeds != VP_EDT_SEEDS_BORDER)
+        return set_error(VP_ERR_INVALID, "%s: unknown seeds %d", who, seeds);
+    return 0;
+}
+
+static int check_edt_morph(const char* who, int op, uint32_t radius)
+{
+    if (op != VP_MORPH_DILATE && op != VP_MORPH_ERODE && op != VP_MORPH_OPEN && op != VP_MORPH_CLOSE)
+        return set_error(VP_ERR_INVALID, "%s: unknown op %d", who, op);
+    if (radius > 65535u) return set_error(VP_ERR_INVALID, "%s: radius %u (0 .. 65535)", who, radius);
+    return 0;
+}
+
+int vp_edt(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int seeds, uint32_t* d_dist2, int algo)
+{
+    const char* who = "vp_edt";
+    if (!ctx || !d_words || !d_dist2) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_edt(f, who, algo));
+    VP_TRY(check_edt_seeds(who, seeds));
+    VP_TRY(check_aligned(who, {d_words, d_dist2}));
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    if (overlaps(d_words, wb, d_dist2, vb)) return set_error(VP_ERR_INVALID, "%s: d_dist2 overlaps d_words", who);
+    grid_written(ctx, d_dist2, vb);
+    return launch_edt(ctx, make_frame(f), d_words, seeds, d_dist2, algo);
+}
+
+int vp_edt_sdf(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fill_unset, float* d_sdf, int algo)
+{
+    const char* who = "vp_edt_sdf";
+    if (!ctx || !d_words || !d_sdf) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_edt(f, who, algo));
+    VP_TRY(check_fill(fill_unset, who));
+    VP_TRY(check_aligned(who, {d_words, d_sdf}));
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    if (overlaps(d_words, wb, d_sdf, vb)) return set_error(VP_ERR_INVALID, "%s: d_sdf overlaps d_words", who);
+    grid_written(ctx, d_sdf, vb);
+    return launch_edt_sdf(ctx, make_frame(f), d_words, fill_unset, d_sdf, algo);
+}
+
+int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo)
+{
+    const char* who = "vp_edt_morph";
+    if (!ctx || !d_words || !d_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_edt(f, who, algo));
+    VP_TRY(check_edt_morph(who, op, radius));
+    VP_TRY(check_aligned(who, {d_words, d_out}));
+    const size_t bytes = vp_grid_words(f) * 4;
+    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    grid_written(ctx, d_out, bytes);
+    return launch_edt_morph(ctx, make_frame(f), d_words, d_out, op, radius, algo);
 }
 
 // what the three vp_components_* entry points share: whole grids up to n = 1024, connectivity and algo
@@ -969,6 +1043,51 @@ int vp_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint3
     return vp_download(ctx, h_out, db, wb);
 }
 
+int vp_edt_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int seeds, uint32_t* h_dist2, int algo)
+{
+    const char* who = "vp_edt_host";
+    if (!ctx || !h_words || !h_dist2) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_edt(f, who, algo));
+    VP_TRY(check_edt_seeds(who, seeds));
+    void *dw = nullptr, *dd = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, vb, &dd));              // one 32-bit value per voxel, like the sdf
+    VP_TRY(vp_upload(ctx, dw, h_words, wb));
+    VP_TRY(vp_edt(ctx, f, (const uint32_t*)dw, seeds, (uint32_t*)dd, algo));
+    return vp_download(ctx, h_dist2, dd, vb);
+}
+
+int vp_edt_sdf_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, float fill_unset, float* h_sdf, int algo)
+{
+    const char* who = "vp_edt_sdf_host";
+    if (!ctx || !h_words || !h_sdf) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_edt(f, who, algo));
+    VP_TRY(check_fill(fill_unset, who));
+    void *dw = nullptr, *ds = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, vb, &ds));
+    VP_TRY(vp_upload(ctx, dw, h_words, wb));
+    VP_TRY(vp_edt_sdf(ctx, f, (const uint32_t*)dw, fill_unset, (float*)ds, algo));
+    return vp_download(ctx, h_sdf, ds, vb);
+}
+
+int vp_edt_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo)
+{
+    const char* who = "vp_edt_morph_host";
+    if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_edt(f, who, algo));
+    VP_TRY(check_edt_morph(who, op, radius));
+    void *da = nullptr, *db = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
+    VP_TRY(vp_upload(ctx, da, h_words, wb));
+    VP_TRY(vp_edt_morph(ctx, f, (const uint32_t*)da, (uint32_t*)db, op, radius, algo));
+    return vp_download(ctx, h_out, db, wb);
+}
+
 int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,
                              uint32_t* h_count)
 {
@@ -1078,13 +1197,13 @@ int vp_prof_reset(vp_ctx* ctx)
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_prof_reset: null ctx");
     VP_TRY(bind_device(ctx));
     VP_TRY(prof_fold(ctx));
-    for (int i = 0; i < VP_K_TOTAL; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
+    for (int i = 0; i < VP_K_END; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
     return 0;
 }
 
 int vp_prof_get(vp_ctx* ctx, int kernel, double* total_ms, uint64_t* launches)
 {
-    if (!ctx || kernel < 0 || kernel >= VP_K_TOTAL) return set_error(VP_ERR_INVALID, "vp_prof_get: bad argument");
+    if (!ctx || kernel < 0 || kernel >= VP_K_END) return set_error(VP_ERR_INVALID, "vp_prof_get: bad argument");
     VP_TRY(bind_device(ctx));
     VP_TRY(prof_fold(ctx));
     if (total_ms) *total_ms = ctx->prof_ms[kernel];
@@ -1092,6 +1211,6 @@ int vp_prof_get(vp_ctx* ctx, int kernel, double* total_ms, uint64_t* launches)
     return 0;
 }
 
-const char* vp_prof_name(int kernel) { return (kernel >= 0 && kernel < VP_K_TOTAL) ? kNames[kernel] : "?"; }
+const char* vp_prof_name(int kernel) { return (kernel >= 0 && kernel < VP_K_END) ? kNames[kernel] : "?"; }
 
 }  // extern "C"

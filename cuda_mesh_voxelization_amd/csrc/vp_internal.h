@@ -103,13 +103,16 @@ struct vp_ctx {
     uint32_t sn_n = 0;
     int sn_algo = 0;
     uint64_t sn_vertices = 0, sn_quads = 0;
+    // exact distance transform (edt.hip): the border mask of SEEDS_BORDER, the distance volume of vp_edt_morph, the second volume of the NAIVE
+    // column passes (4 n^3 bytes each) and the intermediate grid of open / close; all four are freed by vp_ctx_release
+    vp::Buffer edt_mask, edt_vol, edt_vol2, edt_tmp;
     // profiling
     bool prof_on = false;
     uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
     std::vector<vp::ProfSpan> prof_pending;
     std::vector<hipEvent_t> prof_pool;
-    double prof_ms[VP_K_TOTAL] = {};
-    uint64_t prof_n[VP_K_TOTAL] = {};
+    double prof_ms[VP_K_END] = {};
+    uint64_t prof_n[VP_K_END] = {};
 };
 
 namespace vp {
@@ -171,6 +174,11 @@ int launch_voxelize_conservative(vp_ctx* ctx, const Frame& f, uint32_t* d_words,
 int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds);
 // morph.hip: ball dilate / erode / open / close of a whole grid (enqueues only, once the context's buffers have grown)
 int launch_morph(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
+// edt.hip: exact squared distances to the seeds of a whole grid, the exact sdf and ball morphology through the transform (enqueue only, once
+// the context's buffers have grown)
+int launch_edt(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int seeds, uint32_t* d_dist, int algo);
+int launch_edt_sdf(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, float fill, float* d_sdf, int algo);
+int launch_edt_morph(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
 // components.hip: labels, sizes and size filters of the connected components of a whole grid; all three are blocking (counts go to the host)
 int launch_components_label(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_labels, int conn, int algo, uint32_t* h_count);
 int launch_components_sizes(vp_ctx* ctx, uint32_t n, const uint32_t* d_labels, uint32_t count, uint32_t* d_sizes);

@@ -79,6 +79,29 @@ class Engine:
         self.ctx.morph(frame, words.data_ptr(), out.data_ptr(), op, radius, algo)
         return out
 
+    def edt(self, frame: Frame, words, seeds: int = capi.EDT_SEEDS_SET, out=None, algo: int = ALGO_TILED):
+        """Exact Euclidean distance transform of a whole grid (n <= 1024): an int32 tensor of n^3 squared voxel distances, x fastest, to
+        the nearest seed -- capi.EDT_SEEDS_SET (set voxels), EDT_SEEDS_UNSET (unset voxels) or EDT_SEEDS_BORDER (the JFA's seeds).  A grid
+        without seeds gives capi.EDT_NONE (-1 as int32) everywhere.  Enqueues only; returns out."""
+        if out is None:
+            out = torch.empty(frame.voxels, dtype=torch.int32, device=self.device)
+        self.ctx.edt(frame, words.data_ptr(), out.data_ptr(), seeds, algo)
+        return out
+
+    def edt_sdf(self, frame: Frame, words, out=None, fill=-math.inf, algo: int = ALGO_TILED):
+        """jfa() without its error: +-(squared distance to the nearest border voxel), exact.  Enqueues only; returns out."""
+        if out is None:
+            out = torch.empty(frame.voxels, dtype=torch.float32, device=self.device)
+        self.ctx.edt_sdf(frame, words.data_ptr(), fill, out.data_ptr(), algo)
+        return out
+
+    def edt_morph(self, frame: Frame, words, op: int, radius: int, out=None, algo: int = ALGO_TILED):
+        """morph() for any integer radius 0 .. 65535, through the distance transform.  `out` must not be `words`.  Enqueues only."""
+        if out is None:
+            out = self.new_grid(frame)
+        self.ctx.edt_morph(frame, words.data_ptr(), out.data_ptr(), op, radius, algo)
+        return out
+
     def components_label(self, frame: Frame, words, conn: int = capi.CONN_26, algo: int = ALGO_TILED, out=None):
         """Connected components of the set voxels of a whole grid (capi.CONN_6 / CONN_26).  Returns (labels, K): an int32 tensor of n^3
         labels, x fastest, 0 = background, components 1 .. K in the order of their lowest voxel index -- scipy.ndimage.label's

@@ -40,6 +40,12 @@ void FillDevice(const char* label, uint32_t* words, size_t n, float voxelSize, c
 // ball morphology (morph.cpp): host restatement by separable capped squared distances, and the GPU marshalling; both work in place
 void MorphHost(bool parallel, uint32_t* words, size_t n, int op, uint32_t radius);
 void MorphDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], int op, uint32_t radius);
+// exact distance transform (edt.cpp): host restatement by row sweeps and lower envelopes of parabolas, and the GPU marshalling; the
+// morphology works in place
+void EdtHost(bool parallel, const uint32_t* words, size_t n, int seeds, uint32_t* dist);
+void EdtDevice(int algo, const char* label, const uint32_t* words, size_t n, float voxelSize, const float origin[3], int seeds, uint32_t* dist);
+void MorphExactHost(bool parallel, uint32_t* words, size_t n, int op, uint32_t radius);
+void MorphExactDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], int op, uint32_t radius);
 // connected components (components.cpp): host restatement by a scan in index order with an explicit-stack flood per component, and the
 // GPU marshalling; the filters work in place
 struct ComponentStats { uint32_t count; uint64_t kept; };      // K components found, voxels kept
@@ -140,6 +146,45 @@ void Morph(HostVoxelsGrid<T>& grid, MorphOp op, uint32_t radius)
     else
         detail::MorphDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveMorph" : "TiledMorph", words, v.VoxelsPerSide(),
                             v.VoxelSize(), origin, static_cast<int>(op), radius);
+}
+
+// DistanceTransform / MorphExact: the exact Euclidean distance transform of a grid and ball morphology through it (include/vphip.h, vp_edt /
+// vp_edt_morph).  No reference counterpart.
+//   DistanceTransform  dist(x, y, z) = the smallest squared distance, in voxels, to a seed voxel -- EdtSeeds::SET (the set voxels), UNSET (the
+//                      unset voxels) or BORDER (the JFA's seeds: set voxels with an unset or outside 26-neighbour); voxels outside the grid are
+//                      never seeds; VP_EDT_NONE everywhere if there is no seed.  `dist` is resized to the grid.
+//   MorphExact         Morph for any radius 0 .. 65535, in place: dilate = D_SET <= r^2, erode = D_UNSET > r^2, open and close composed.
+//   SEQUENTIAL / OPENMP   host restatement in another formulation (row sweeps, then lower envelopes of parabolas); any grid side
+//   NAIVE / TILED         vp_edt_host / vp_edt_morph_host with VP_ALGO_NAIVE / VP_ALGO_TILED (n % 32 == 0, n <= 1024)
+// Every variant produces the same values and bits.
+enum class EdtSeeds : int { SET = 0, UNSET = 1, BORDER = 2 };     // = VP_EDT_SEEDS_*
+
+template <Types type, VGType T>
+void DistanceTransform(const HostVoxelsGrid<T>& grid, HostGrid<uint32_t>& dist, EdtSeeds seeds = EdtSeeds::SET)
+{
+    const auto& v = grid.View();
+    const size_t n = v.VoxelsPerSide();
+    if (dist.View().SizeX() != n || dist.View().SizeY() != n || dist.View().SizeZ() != n) dist = HostGrid<uint32_t>(n, 0u);
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(v.Data());
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        detail::EdtHost(type == Types::OPENMP, words, n, static_cast<int>(seeds), dist.View().Data());
+    else
+        detail::EdtDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveEdt" : "TiledEdt", words, n, v.VoxelSize(), origin,
+                          static_cast<int>(seeds), dist.View().Data());
+}
+
+template <Types type, VGType T>
+void MorphExact(HostVoxelsGrid<T>& grid, MorphOp op, uint32_t radius)
+{
+    auto& v = grid.View();
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    uint32_t* words = reinterpret_cast<uint32_t*>(v.Data());
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        detail::MorphExactHost(type == Types::OPENMP, words, v.VoxelsPerSide(), static_cast<int>(op), radius);
+    else
+        detail::MorphExactDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveMorphExact" : "TiledMorphExact", words,
+                                 v.VoxelsPerSide(), v.VoxelSize(), origin, static_cast<int>(op), radius);
 }
 
 // LabelComponents / FilterComponents: connected components of the set voxels (include/vphip.h, vp_components_*).  conn = 6 (face

@@ -183,6 +183,35 @@ int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, ui
 enum { VP_MORPH_DILATE = 0, VP_MORPH_ERODE = 1, VP_MORPH_OPEN = 2, VP_MORPH_CLOSE = 3 };
 int vp_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
 
+/* ---- exact Euclidean distance transform (no reference counterpart) ------------
+ * Integer arithmetic only: d_dist2[x + n (y + n z)] = the minimum over the SEED voxels q of |p - q|^2 in voxel units, one uint32 per voxel
+ * (4 n^3 bytes, x fastest like the sdf); VP_EDT_NONE where the grid has no seed at all.  The largest value is 3 * 1023^2, exact in float.
+ *   VP_EDT_SEEDS_SET     the set voxels
+ *   VP_EDT_SEEDS_UNSET   the unset voxels
+ *   VP_EDT_SEEDS_BORDER  the JFA's seeds (vp_surface): set voxels with an unset 26-neighbour or a 26-neighbour outside the grid
+ * Voxels outside the grid are never seeds.
+ *   vp_edt        the transform above.
+ *   vp_edt_sdf    the exact counterpart of vp_jfa: D = the SEEDS_BORDER transform, sdf = +-((float)D * (voxel_size * voxel_size)) --
+ *                 the product formed once in float, then one conversion and one multiply -- positive on set voxels, negative on unset
+ *                 ones; a grid without seeds (the empty grid) gives fill_unset everywhere.  fill_unset must be +-infinity.  D lives in
+ *                 d_sdf and is converted in place.  Same sign bits and the same zeros as vp_jfa; |vp_jfa| >= |vp_edt_sdf| everywhere.
+ *   vp_edt_morph  vp_morph's four ops with its two border rules, radius 0 .. 65535: dilate = D_SET <= r^2, erode = D_UNSET > r^2 (outside
+ *                 reads as set: it is never a seed), open = dilate(erode), close = erode(dilate); radius 0 copies; radius > 65535:
+ *                 VP_ERR_INVALID.  The distance volume (4 n^3 bytes) and the intermediate grid are grow-only buffers of the context.
+ * Three separable passes: x straight from the bit words (nearest seed bit left and right), then y and z as out(i) = min_j g(j) + (i - j)^2.
+ *   algo: VP_ALGO_NAIVE -- column passes with one thread per voxel from global memory into a second 4 n^3 volume of the context;
+ *   VP_ALGO_TILED -- whole columns of a bundle of adjacent x staged in LDS, written back in place (no second volume).  Same bytes.
+ * Whole-grid frames only: a slab frame returns VP_ERR_UNSUPPORTED; so does n > 1024 (the volume would be 32 GiB).  The outputs must not
+ * overlap d_words; every buffer is 16-byte aligned.  Null pointers, unknown seeds / op / algo: VP_ERR_INVALID.  Every refusal leaves the
+ * outputs untouched.  The calls only enqueue work once the context's buffers have grown (the border mask n^3/8, NAIVE's second volume,
+ * vp_edt_morph's distance volume and intermediate grid; the volumes are freed by vp_ctx_release).  Like every writer, they drop a pending
+ * vp_jfa_start / extract / surfnets count whose bytes the output overlaps. */
+enum { VP_EDT_SEEDS_SET = 0, VP_EDT_SEEDS_UNSET = 1, VP_EDT_SEEDS_BORDER = 2 };
+#define VP_EDT_NONE 0xFFFFFFFFu
+int vp_edt(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int seeds, uint32_t* d_dist2, int algo);
+int vp_edt_sdf(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fill_unset, float* d_sdf, int algo);
+int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
+
 /* ---- connected components: labels, sizes, size filters (no reference counterpart) ----------------
  * Set voxels are the foreground, voxels outside the grid are empty.  connectivity: VP_CONN_6 (face neighbours) or VP_CONN_26 (face, edge
  * and corner neighbours) = scipy.ndimage.generate_binary_structure(3, 1) and (3, 3).  Integer arithmetic only.
@@ -507,6 +536,12 @@ int vp_components_filter_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_
 int vp_surfnets_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t iterations, uint64_t* h_cells, float* h_xyz,
                      uint32_t* h_quads, size_t vertex_capacity, size_t quad_capacity, uint64_t* h_vertices, uint64_t* h_quads_out);
 
+/* vp_edt / vp_edt_sdf / vp_edt_morph with the convention above (whole-grid frame); staged through workspace slots.  h_dist2 and h_sdf hold
+ * n^3 values; h_out may equal h_words. */
+int vp_edt_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int seeds, uint32_t* h_dist2, int algo);
+int vp_edt_sdf_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, float fill_unset, float* h_sdf, int algo);
+int vp_edt_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo);
+
 /* ---- per-kernel timing (PROFILING_SCOPE equivalent for device time, vplib/src/profiling.h:8-33)
  * When enabled, every kernel launch is bracketed by hipEvents on the context's stream. */
 enum {
@@ -561,6 +596,17 @@ enum {
     VP_K_SN_QUADS_NAIVE,        /* NAIVE: four index reads per quad, 16 Q written */
     VP_K_SN_RELAX_NAIVE,        /* NAIVE, one Jacobi step */
     VP_K_TOTAL
+};
+/* the keys of vp_edt / vp_edt_sdf / vp_edt_morph follow the second enum (all three together: 64 keys at the most) */
+enum {
+    VP_K_EDT_X = VP_K_TOTAL,    /* both algos: bit words -> dx^2: n^3/8 read + 4 n^3 written */
+    VP_K_EDT_Y,                 /* TILED, y pass in place: 4 n^3 read + up to 4 n^3 written (bundles without a seed write nothing) */
+    VP_K_EDT_Z,                 /* TILED, z pass in place: as y */
+    VP_K_EDT_Y_NAIVE,           /* NAIVE, y pass into the second volume: 8 n^3 + the search */
+    VP_K_EDT_Z_NAIVE,           /* NAIVE, z pass back: as y */
+    VP_K_EDT_SDF,               /* D -> sdf in place: n^3/8 + 4 n^3 read, 4 n^3 written */
+    VP_K_EDT_THRESH,            /* D -> bit words: 4 n^3 read, n^3/8 written */
+    VP_K_END
 };
 int vp_prof_enable(vp_ctx* ctx, int on);
 /* Restricts the bracketing to the keys whose bit is set (bit i = key i; default: all).  An event pair costs ~3 us of stream
