@@ -144,6 +144,24 @@ static const char* kNames[VP_K_END] = {
 
 using namespace vp;
 
+// The workspace slots of the host-in / host-out calls at the end of this file, and the round trip of those with one grid in and one result
+// out (a template: it cannot stand inside extern "C"): the grid goes up into SLOT_GRID_A, call(d_words, d_out) is the device entry point,
+// and its output -- a grid in SLOT_GRID_B or one 32-bit value per voxel in SLOT_SDF -- comes down.  The callers validate first: asking
+// for a slot already drops the records of the grids that lay in it.
+enum { SLOT_GRID_A = 0, SLOT_GRID_B = 1, SLOT_XYZ = 2, SLOT_TRI = 3, SLOT_SDF = 4 };
+
+template <typename Call>
+static int host_round_trip(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, void* h_out, int out_slot, Call call)
+{
+    void *din = nullptr, *dout = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, ob = out_slot == SLOT_SDF ? vp_grid_voxels(f) * 4 : wb;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &din));
+    VP_TRY(vp_ctx_workspace(ctx, out_slot, ob, &dout));
+    VP_TRY(vp_upload(ctx, din, h_words, wb));
+    VP_TRY(call((const uint32_t*)din, dout));
+    return vp_download(ctx, h_out, dout, ob);
+}
+
 extern "C" {
 
 int vp_abi_version(void) { return VP_ABI_VERSION; }
@@ -318,33 +336,59 @@ static int check_aligned(const char* who, std::initializer_list<const void*> ptr
     return 0;
 }
 
-int vp_voxelize(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, const float* d_xyz, size_t nverts,
-                const uint32_t* d_tri, size_t ntris, int algo, int accumulate)
+// The calls that serve whole grids only refuse a slab frame as unsupported (a frame that passed check_frame; check_frame's own `whole`
+// refuses it as invalid: each entry point keeps the code it has always returned).
+static int check_whole(const vp_frame* f, const char* who)
 {
-    if (!ctx || !d_words) return set_error(VP_ERR_INVALID, "vp_voxelize: null argument");
-    VP_TRY(bind_device(ctx));
-    VP_TRY(check_frame(f, "vp_voxelize", false));
-    VP_TRY(check_aligned("vp_voxelize", {d_words}));
-    if (ntris && (!d_xyz || !d_tri || !nverts)) return set_error(VP_ERR_INVALID, "vp_voxelize: null mesh arrays");
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "vp_voxelize: algo %d", algo);
-    if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "vp_voxelize: too many triangles");
-    grid_written(ctx, d_words, vp_grid_words(f) * 4);
-    return launch_voxelize(ctx, make_frame(f), d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate ? 1 : 0);
+    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    return 0;
 }
 
-int vp_voxelize_conservative(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, const float* d_xyz, size_t nverts,
-                             const uint32_t* d_tri, size_t ntris, int algo, int accumulate)
+static int check_algo(const char* who, int algo)
 {
-    const char* who = "vp_voxelize_conservative";
+    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    return 0;
+}
+
+static int check_morph_op(const char* who, int op)
+{
+    if (op != VP_MORPH_DILATE && op != VP_MORPH_ERODE && op != VP_MORPH_OPEN && op != VP_MORPH_CLOSE)
+        return set_error(VP_ERR_INVALID, "%s: unknown op %d", who, op);
+    return 0;
+}
+
+// an output that would be written while the input grid d_words is still being read
+static int check_disjoint(const char* who, const char* out_name, const void* d_in, size_t in_bytes, const void* d_out, size_t out_bytes)
+{
+    if (overlaps(d_in, in_bytes, d_out, out_bytes)) return set_error(VP_ERR_INVALID, "%s: %s overlaps d_words", who, out_name);
+    return 0;
+}
+
+// vp_voxelize and vp_voxelize_conservative: the same checks in front of two launchers
+static int voxelize(const char* who, decltype(&launch_voxelize) launch, vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, const float* d_xyz,
+                    size_t nverts, const uint32_t* d_tri, size_t ntris, int algo, int accumulate)
+{
     if (!ctx || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, who, false));
     VP_TRY(check_aligned(who, {d_words}));
     if (ntris && (!d_xyz || !d_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: algo %d", who, algo);
+    VP_TRY(check_algo(who, algo));
     if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "%s: too many triangles", who);
     grid_written(ctx, d_words, vp_grid_words(f) * 4);
-    return launch_voxelize_conservative(ctx, make_frame(f), d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate ? 1 : 0);
+    return launch(ctx, make_frame(f), d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate ? 1 : 0);
+}
+
+int vp_voxelize(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, const float* d_xyz, size_t nverts,
+                const uint32_t* d_tri, size_t ntris, int algo, int accumulate)
+{
+    return voxelize("vp_voxelize", launch_voxelize, ctx, f, d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate);
+}
+
+int vp_voxelize_conservative(vp_ctx* ctx, const vp_frame* f, uint32_t* d_words, const float* d_xyz, size_t nverts,
+                             const uint32_t* d_tri, size_t ntris, int algo, int accumulate)
+{
+    return voxelize("vp_voxelize_conservative", launch_voxelize_conservative, ctx, f, d_words, d_xyz, nverts, d_tri, ntris, algo, accumulate);
 }
 
 int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, uint32_t* h_rounds)
@@ -353,10 +397,10 @@ int vp_fill_interior(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, ui
     if (!ctx || !d_words || !d_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, who, false));
-    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    VP_TRY(check_whole(f, who));
     VP_TRY(check_aligned(who, {d_words, d_out}));
     const size_t bytes = vp_grid_words(f) * 4;
-    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    VP_TRY(check_disjoint(who, "d_out", d_words, bytes, d_out, bytes));
     grid_written(ctx, d_out, bytes);
     return launch_fill_interior(ctx, f->n, d_words, d_out, h_rounds);
 }
@@ -367,14 +411,13 @@ int vp_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* 
     if (!ctx || !d_words || !d_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, who, false));
-    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
-    if (op != VP_MORPH_DILATE && op != VP_MORPH_ERODE && op != VP_MORPH_OPEN && op != VP_MORPH_CLOSE)
-        return set_error(VP_ERR_INVALID, "%s: unknown op %d", who, op);
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    VP_TRY(check_whole(f, who));
+    VP_TRY(check_morph_op(who, op));
+    VP_TRY(check_algo(who, algo));
     if (radius > 32) return set_error(VP_ERR_UNSUPPORTED, "%s: radius %u is not served (0 .. 32)", who, radius);
     VP_TRY(check_aligned(who, {d_words, d_out}));
     const size_t bytes = vp_grid_words(f) * 4;
-    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    VP_TRY(check_disjoint(who, "d_out", d_words, bytes, d_out, bytes));
     grid_written(ctx, d_out, bytes);
     return launch_morph(ctx, f->n, d_words, d_out, op, radius, algo);
 }
@@ -385,9 +428,9 @@ static int check_fill(float fill, const char* who);
 static int check_edt(const vp_frame* f, const char* who, int algo)
 {
     VP_TRY(check_frame(f, who, false));
-    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    VP_TRY(check_whole(f, who));
     if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: the distance volume would be 32 GiB)", who, f->n);
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    VP_TRY(check_algo(who, algo));
     return 0;
 }
 
@@ -400,8 +443,7 @@ static int check_edt_seeds(const char* who, int seeds)
 
 static int check_edt_morph(const char* who, int op, uint32_t radius)
 {
-    if (op != VP_MORPH_DILATE && op != VP_MORPH_ERODE && op != VP_MORPH_OPEN && op != VP_MORPH_CLOSE)
-        return set_error(VP_ERR_INVALID, "%s: unknown op %d", who, op);
+    VP_TRY(check_morph_op(who, op));
     if (radius > 65535u) return set_error(VP_ERR_INVALID, "%s: radius %u (0 .. 65535)", who, radius);
     return 0;
 }
@@ -415,7 +457,7 @@ int vp_edt(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int seeds, u
     VP_TRY(check_edt_seeds(who, seeds));
     VP_TRY(check_aligned(who, {d_words, d_dist2}));
     const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
-    if (overlaps(d_words, wb, d_dist2, vb)) return set_error(VP_ERR_INVALID, "%s: d_dist2 overlaps d_words", who);
+    VP_TRY(check_disjoint(who, "d_dist2", d_words, wb, d_dist2, vb));
     grid_written(ctx, d_dist2, vb);
     return launch_edt(ctx, make_frame(f), d_words, seeds, d_dist2, algo);
 }
@@ -429,7 +471,7 @@ int vp_edt_sdf(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fi
     VP_TRY(check_fill(fill_unset, who));
     VP_TRY(check_aligned(who, {d_words, d_sdf}));
     const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
-    if (overlaps(d_words, wb, d_sdf, vb)) return set_error(VP_ERR_INVALID, "%s: d_sdf overlaps d_words", who);
+    VP_TRY(check_disjoint(who, "d_sdf", d_words, wb, d_sdf, vb));
     grid_written(ctx, d_sdf, vb);
     return launch_edt_sdf(ctx, make_frame(f), d_words, fill_unset, d_sdf, algo);
 }
@@ -443,7 +485,7 @@ int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32
     VP_TRY(check_edt_morph(who, op, radius));
     VP_TRY(check_aligned(who, {d_words, d_out}));
     const size_t bytes = vp_grid_words(f) * 4;
-    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    VP_TRY(check_disjoint(who, "d_out", d_words, bytes, d_out, bytes));
     grid_written(ctx, d_out, bytes);
     return launch_edt_morph(ctx, make_frame(f), d_words, d_out, op, radius, algo);
 }
@@ -452,10 +494,10 @@ int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32
 static int check_components(const vp_frame* f, const char* who, int connectivity, int algo)
 {
     VP_TRY(check_frame(f, who, false));
-    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    VP_TRY(check_whole(f, who));
     if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: voxel indices are 32-bit)", who, f->n);
     if (connectivity != VP_CONN_6 && connectivity != VP_CONN_26) return set_error(VP_ERR_INVALID, "%s: unknown connectivity %d (6 or 26)", who, connectivity);
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    VP_TRY(check_algo(who, algo));
     return 0;
 }
 
@@ -475,7 +517,7 @@ int vp_components_label(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words,
     VP_TRY(check_components(f, who, connectivity, algo));
     VP_TRY(check_aligned(who, {d_words, d_labels}));
     const size_t wb = vp_grid_words(f) * 4, lb = vp_grid_voxels(f) * 4;
-    if (overlaps(d_words, wb, d_labels, lb)) return set_error(VP_ERR_INVALID, "%s: d_labels overlaps d_words", who);
+    VP_TRY(check_disjoint(who, "d_labels", d_words, wb, d_labels, lb));
     grid_written(ctx, d_labels, lb);
     return launch_components_label(ctx, f->n, d_words, d_labels, connectivity, algo, h_count);
 }
@@ -502,7 +544,7 @@ int vp_components_filter(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words
     VP_TRY(check_filter_mode(who, mode, param));
     VP_TRY(check_aligned(who, {d_words, d_out}));
     const size_t bytes = vp_grid_words(f) * 4;
-    if (overlaps(d_words, bytes, d_out, bytes)) return set_error(VP_ERR_INVALID, "%s: d_out overlaps d_words", who);
+    VP_TRY(check_disjoint(who, "d_out", d_words, bytes, d_out, bytes));
     grid_written(ctx, d_out, bytes);
     return launch_components_filter(ctx, f->n, d_words, d_out, connectivity, mode, param, algo, h_count, h_kept);
 }
@@ -568,7 +610,7 @@ int vp_jfa_pass(vp_ctx* ctx, const vp_frame* f, uint32_t k, const void* d_in, co
     VP_TRY(check_frame(f, "vp_jfa_pass", false));
     VP_TRY(check_aligned("vp_jfa_pass", {d_in, d_minus, d_plus, d_out}));
     if (k == 0 || k >= f->n) return set_error(VP_ERR_INVALID, "vp_jfa_pass: step %u out of range", k);
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "vp_jfa_pass: algo %d", algo);
+    VP_TRY(check_algo("vp_jfa_pass", algo));
     // halos are mandatory wherever a neighbour plane exists outside the slab
     if (f->z0 > 0 && !d_minus) return set_error(VP_ERR_INVALID, "vp_jfa_pass: slab needs d_minus");
     if (f->z1 < f->n && !d_plus) return set_error(VP_ERR_INVALID, "vp_jfa_pass: slab needs d_plus");
@@ -593,7 +635,7 @@ static int jfa_check(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, vo
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, who, true));
     VP_TRY(check_aligned(who, {d_words, d_work}));
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: algo %d", who, algo);
+    VP_TRY(check_algo(who, algo));
     if (!d_work) {                                                 // context-owned workspace (grow-only, reused by later calls)
         const void* before = ctx->jfa_work.ptr;
         VP_TRY(reserve(ctx, ctx->jfa_work, vp_jfa_workspace_bytes(f)));
@@ -700,7 +742,7 @@ int vp_jfa_last_pass(vp_ctx* ctx, const vp_frame* f, const void* d_in, const voi
     VP_TRY(check_frame(f, "vp_jfa_last_pass", false));
     VP_TRY(check_aligned("vp_jfa_last_pass", {d_in, d_minus, d_plus, d_words, d_sdf}));
     VP_TRY(check_fill(fill_unset, "vp_jfa_last_pass"));
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "vp_jfa_last_pass: algo %d", algo);
+    VP_TRY(check_algo("vp_jfa_last_pass", algo));
     if (f->z0 > 0 && !d_minus) return set_error(VP_ERR_INVALID, "vp_jfa_last_pass: slab needs d_minus");
     if (f->z1 < f->n && !d_plus) return set_error(VP_ERR_INVALID, "vp_jfa_last_pass: slab needs d_plus");
     const Frame fr = make_frame(f);
@@ -938,7 +980,7 @@ int vp_extract(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int mode
 static int check_surfnets(const vp_frame* f, const char* who)
 {
     VP_TRY(check_frame(f, who, false));
-    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
+    VP_TRY(check_whole(f, who));
     if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: cell indices are 32-bit)", who, f->n);
     return 0;
 }
@@ -949,7 +991,7 @@ int vp_surfnets_count(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, i
     if (!ctx || !d_words || !h_vertices || !h_quads) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(bind_device(ctx));
     VP_TRY(check_surfnets(f, who));
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    VP_TRY(check_algo(who, algo));
     VP_TRY(check_aligned(who, {d_words}));
     return launch_surfnets_count(ctx, f->n, d_words, algo, h_vertices, h_quads);
 }
@@ -961,7 +1003,7 @@ int vp_surfnets(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int alg
     if (!ctx || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(bind_device(ctx));
     VP_TRY(check_surfnets(f, who));
-    if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
+    VP_TRY(check_algo(who, algo));
     if (iterations > 64) return set_error(VP_ERR_INVALID, "%s: %u iterations (0 .. 64)", who, iterations);
     if (ctx->sn_words != d_words || ctx->sn_algo != algo || ctx->sn_n != f->n)
         return set_error(VP_ERR_INVALID, "%s: call vp_surfnets_count with the same grid and algo first", who);
@@ -979,13 +1021,12 @@ int vp_surfnets(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int alg
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
-enum { SLOT_GRID_A = 0, SLOT_GRID_B = 1, SLOT_XYZ = 2, SLOT_TRI = 3, SLOT_SDF = 4 };
-
-int vp_voxelize_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words, const float* h_xyz, size_t nverts,
-                     const uint32_t* h_tri, size_t ntris, int algo)
+// vp_voxelize_host and vp_voxelize_conservative_host: mesh up, one of the two device calls, grid down
+static int voxelize_host(const char* who, decltype(&vp_voxelize) call, vp_ctx* ctx, const vp_frame* f, uint32_t* h_words, const float* h_xyz,
+                         size_t nverts, const uint32_t* h_tri, size_t ntris, int algo)
 {
-    if (!ctx || !h_words) return set_error(VP_ERR_INVALID, "vp_voxelize_host: null argument");
-    VP_TRY(check_frame(f, "vp_voxelize_host", true));
+    if (!ctx || !h_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_frame(f, who, true));
     void *dw = nullptr, *dx = nullptr, *dt = nullptr;
     const size_t wb = vp_grid_words(f) * 4;
     VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
@@ -993,24 +1034,20 @@ int vp_voxelize_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words, const fl
     VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
     VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
     VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
-    VP_TRY(vp_voxelize(ctx, f, (uint32_t*)dw, (const float*)dx, nverts, (const uint32_t*)dt, ntris, algo, 0));
+    VP_TRY(call(ctx, f, (uint32_t*)dw, (const float*)dx, nverts, (const uint32_t*)dt, ntris, algo, 0));
     return vp_download(ctx, h_words, dw, wb);
+}
+
+int vp_voxelize_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words, const float* h_xyz, size_t nverts,
+                     const uint32_t* h_tri, size_t ntris, int algo)
+{
+    return voxelize_host("vp_voxelize_host", vp_voxelize, ctx, f, h_words, h_xyz, nverts, h_tri, ntris, algo);
 }
 
 int vp_voxelize_conservative_host(vp_ctx* ctx, const vp_frame* f, uint32_t* h_words, const float* h_xyz, size_t nverts,
                                   const uint32_t* h_tri, size_t ntris, int algo)
 {
-    if (!ctx || !h_words) return set_error(VP_ERR_INVALID, "vp_voxelize_conservative_host: null argument");
-    VP_TRY(check_frame(f, "vp_voxelize_conservative_host", true));
-    void *dw = nullptr, *dx = nullptr, *dt = nullptr;
-    const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nverts * 12, &dx));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
-    VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
-    VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
-    VP_TRY(vp_voxelize_conservative(ctx, f, (uint32_t*)dw, (const float*)dx, nverts, (const uint32_t*)dt, ntris, algo, 0));
-    return vp_download(ctx, h_words, dw, wb);
+    return voxelize_host("vp_voxelize_conservative_host", vp_voxelize_conservative, ctx, f, h_words, h_xyz, nverts, h_tri, ntris, algo);
 }
 
 int vp_fill_interior_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out)
@@ -1018,14 +1055,9 @@ int vp_fill_interior_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_word
     const char* who = "vp_fill_interior_host";
     if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_frame(f, who, false));
-    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
-    void *da = nullptr, *db = nullptr;
-    const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
-    VP_TRY(vp_upload(ctx, da, h_words, wb));
-    VP_TRY(vp_fill_interior(ctx, f, (const uint32_t*)da, (uint32_t*)db, nullptr));
-    return vp_download(ctx, h_out, db, wb);
+    VP_TRY(check_whole(f, who));
+    return host_round_trip(ctx, f, h_words, h_out, SLOT_GRID_B,
+                           [&](const uint32_t* dw, void* d) { return vp_fill_interior(ctx, f, dw, (uint32_t*)d, nullptr); });
 }
 
 int vp_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo)
@@ -1033,14 +1065,9 @@ int vp_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint3
     const char* who = "vp_morph_host";
     if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_frame(f, who, false));
-    if (f->z0 != 0 || f->z1 != f->n) return set_error(VP_ERR_UNSUPPORTED, "%s: slab frames are not served (whole grid only)", who);
-    void *da = nullptr, *db = nullptr;
-    const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
-    VP_TRY(vp_upload(ctx, da, h_words, wb));
-    VP_TRY(vp_morph(ctx, f, (const uint32_t*)da, (uint32_t*)db, op, radius, algo));
-    return vp_download(ctx, h_out, db, wb);
+    VP_TRY(check_whole(f, who));
+    return host_round_trip(ctx, f, h_words, h_out, SLOT_GRID_B,
+                           [&](const uint32_t* dw, void* d) { return vp_morph(ctx, f, dw, (uint32_t*)d, op, radius, algo); });
 }
 
 int vp_edt_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int seeds, uint32_t* h_dist2, int algo)
@@ -1049,13 +1076,8 @@ int vp_edt_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int see
     if (!ctx || !h_words || !h_dist2) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_edt(f, who, algo));
     VP_TRY(check_edt_seeds(who, seeds));
-    void *dw = nullptr, *dd = nullptr;
-    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, vb, &dd));              // one 32-bit value per voxel, like the sdf
-    VP_TRY(vp_upload(ctx, dw, h_words, wb));
-    VP_TRY(vp_edt(ctx, f, (const uint32_t*)dw, seeds, (uint32_t*)dd, algo));
-    return vp_download(ctx, h_dist2, dd, vb);
+    return host_round_trip(ctx, f, h_words, h_dist2, SLOT_SDF,
+                           [&](const uint32_t* dw, void* d) { return vp_edt(ctx, f, dw, seeds, (uint32_t*)d, algo); });
 }
 
 int vp_edt_sdf_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, float fill_unset, float* h_sdf, int algo)
@@ -1064,13 +1086,8 @@ int vp_edt_sdf_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, flo
     if (!ctx || !h_words || !h_sdf) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_edt(f, who, algo));
     VP_TRY(check_fill(fill_unset, who));
-    void *dw = nullptr, *ds = nullptr;
-    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, vb, &ds));
-    VP_TRY(vp_upload(ctx, dw, h_words, wb));
-    VP_TRY(vp_edt_sdf(ctx, f, (const uint32_t*)dw, fill_unset, (float*)ds, algo));
-    return vp_download(ctx, h_sdf, ds, vb);
+    return host_round_trip(ctx, f, h_words, h_sdf, SLOT_SDF,
+                           [&](const uint32_t* dw, void* d) { return vp_edt_sdf(ctx, f, dw, fill_unset, (float*)d, algo); });
 }
 
 int vp_edt_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo)
@@ -1079,13 +1096,8 @@ int vp_edt_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, u
     if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_edt(f, who, algo));
     VP_TRY(check_edt_morph(who, op, radius));
-    void *da = nullptr, *db = nullptr;
-    const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
-    VP_TRY(vp_upload(ctx, da, h_words, wb));
-    VP_TRY(vp_edt_morph(ctx, f, (const uint32_t*)da, (uint32_t*)db, op, radius, algo));
-    return vp_download(ctx, h_out, db, wb);
+    return host_round_trip(ctx, f, h_words, h_out, SLOT_GRID_B,
+                           [&](const uint32_t* dw, void* d) { return vp_edt_morph(ctx, f, dw, (uint32_t*)d, op, radius, algo); });
 }
 
 int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,
@@ -1094,13 +1106,8 @@ int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_w
     const char* who = "vp_components_label_host";
     if (!ctx || !h_words || !h_labels || !h_count) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_components(f, who, connectivity, algo));
-    void *dw = nullptr, *dl = nullptr;
-    const size_t wb = vp_grid_words(f) * 4, lb = vp_grid_voxels(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, lb, &dl));              // one 32-bit value per voxel, like the sdf
-    VP_TRY(vp_upload(ctx, dw, h_words, wb));
-    VP_TRY(vp_components_label(ctx, f, (const uint32_t*)dw, (uint32_t*)dl, connectivity, algo, h_count));
-    return vp_download(ctx, h_labels, dl, lb);
+    return host_round_trip(ctx, f, h_words, h_labels, SLOT_SDF,
+                           [&](const uint32_t* dw, void* d) { return vp_components_label(ctx, f, dw, (uint32_t*)d, connectivity, algo, h_count); });
 }
 
 int vp_components_filter_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int connectivity, int mode,
@@ -1110,13 +1117,9 @@ int vp_components_filter_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_
     if (!ctx || !h_words || !h_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_components(f, who, connectivity, algo));
     VP_TRY(check_filter_mode(who, mode, param));
-    void *da = nullptr, *db = nullptr;
-    const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &da));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &db));
-    VP_TRY(vp_upload(ctx, da, h_words, wb));
-    VP_TRY(vp_components_filter(ctx, f, (const uint32_t*)da, (uint32_t*)db, connectivity, mode, param, algo, h_count, h_kept));
-    return vp_download(ctx, h_out, db, wb);
+    return host_round_trip(ctx, f, h_words, h_out, SLOT_GRID_B, [&](const uint32_t* dw, void* d) {
+        return vp_components_filter(ctx, f, dw, (uint32_t*)d, connectivity, mode, param, algo, h_count, h_kept);
+    });
 }
 
 int vp_surfnets_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t iterations, uint64_t* h_cells, float* h_xyz,
@@ -1166,13 +1169,8 @@ int vp_jfa_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, float f
 {
     if (!ctx || !h_words || !h_sdf) return set_error(VP_ERR_INVALID, "vp_jfa_host: null argument");
     VP_TRY(check_frame(f, "vp_jfa_host", true));
-    void *dw = nullptr, *ds = nullptr;
-    const size_t wb = vp_grid_words(f) * 4, sb = vp_grid_voxels(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, sb, &ds));
-    VP_TRY(vp_upload(ctx, dw, h_words, wb));
-    VP_TRY(vp_jfa(ctx, f, (const uint32_t*)dw, fill_unset, (float*)ds, nullptr, 0, algo));
-    return vp_download(ctx, h_sdf, ds, sb);
+    return host_round_trip(ctx, f, h_words, h_sdf, SLOT_SDF,
+                           [&](const uint32_t* dw, void* d) { return vp_jfa(ctx, f, dw, fill_unset, (float*)d, nullptr, 0, algo); });
 }
 
 // ---- profiling -------------------------------------------------------------------------------

@@ -42,6 +42,7 @@
 // index order are the labels, so the label volume is a function of the grid alone.  No persistent kernel, grid barrier, cooperative
 // launch or inline assembly: kernel boundaries are the only synchronisation between the steps.
 #include "vp_internal.h"
+#include "wg_scan.h"
 
 #include <algorithm>
 
@@ -217,14 +218,6 @@ comp_merge_runs(const uint32_t* __restrict__ W, uint32_t* P, uint32_t n, uint32_
 }
 
 // ---- the steps both forms share ----
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* part)
-{
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
-}
-
 __global__ void __launch_bounds__(256)
 comp_flatten(uint32_t* P, uint32_t* __restrict__ block_roots)
 {
@@ -247,7 +240,7 @@ comp_flatten(uint32_t* P, uint32_t* __restrict__ block_roots)
         }
         if (any) P4[q] = make_uint4(o[0], o[1], o[2], o[3]);
     }
-    const uint32_t total = block_sum(roots, part);
+    const uint32_t total = wg_sum_256(roots, part);
     if (threadIdx.x == 0) block_roots[blockIdx.x] = total;
 }
 
@@ -256,22 +249,8 @@ __global__ void __launch_bounds__(1024)
 comp_scan(const uint32_t* __restrict__ cnt, uint32_t m, uint32_t* __restrict__ off)
 {
     __shared__ uint32_t part[1024];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t per = (m + 1023) / 1024;
-    const uint32_t b = min(tid * per, m), e = min(b + per, m);
-    uint32_t s = 0;
-    for (uint32_t i = b; i < e; ++i) s += cnt[i];
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint32_t v = tid >= d ? part[tid - d] : 0u;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - s;
-    for (uint32_t i = b; i < e; ++i) { off[i] = run; run += cnt[i]; }
-    if (tid == 1023) off[m] = part[1023];
+    const uint32_t total = wg_scan_1024(part, m, [&](uint32_t i) { return cnt[i]; }, [&](uint32_t i, uint32_t before) { off[i] = before; });
+    if (threadIdx.x == 1023) off[m] = total;
 }
 
 __global__ void __launch_bounds__(256)
@@ -279,7 +258,6 @@ comp_rank(uint32_t* P, const uint32_t* __restrict__ block_off)
 {
     __shared__ uint32_t wave_sum[4];
     const uint4* P4 = reinterpret_cast<const uint4*>(P);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t base = block_off[blockIdx.x];
     for (uint32_t it = 0; it < 8; ++it) {
         const size_t q = (size_t)blockIdx.x * kChunkVec + it * 256 + threadIdx.x;
@@ -287,17 +265,10 @@ comp_rank(uint32_t* P, const uint32_t* __restrict__ block_off)
         const uint4 p = P4[q];
         const uint32_t r0 = p.x == v, r1 = p.y == v + 1, r2 = p.z == v + 2, r3 = p.w == v + 3;
         const uint32_t cnt = r0 + r1 + r2 + r3;
-        uint32_t incl = cnt;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += o;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = base + incl - cnt;
-        for (uint32_t k = 0; k < wave; ++k) before += wave_sum[k];
-        base += wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-        __syncthreads();
+        uint32_t total;
+        const uint32_t before = base + wg_exclusive_256(cnt, wave_sum, &total);
+        base += total;
+        __syncthreads();                                       // wave_sum is written again in the next round
         if (r0) P[v] = kRankFlag | before;
         if (r1) P[v + 1] = kRankFlag | (before + r0);
         if (r2) P[v + 2] = kRankFlag | (before + r0 + r1);
@@ -427,7 +398,7 @@ comp_write(const uint4* __restrict__ L4, size_t nvec, const uint8_t* __restrict_
         word |= __shfl_xor(word, 4);
         if ((lane & 7u) == 0) out[q >> 3] = word;
     }
-    const uint32_t total = block_sum(cnt, part);
+    const uint32_t total = wg_sum_256(cnt, part);
     if (threadIdx.x == 0 && total) atomicAdd(kept, (unsigned long long)total);
 }
 

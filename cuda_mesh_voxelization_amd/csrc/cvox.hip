@@ -23,6 +23,7 @@
 // NAIVE: one thread per triangle over its candidate rows, one atomicOr per set voxel (the simple form TILED is tested against).
 // accumulate = 0 zero-fills the words first; 1 ORs into them (a union).  Both forms are order-free: OR commutes.
 #include "vp_internal.h"
+#include "wg_scan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -219,22 +220,9 @@ cvox_scan(const CRec* __restrict__ rec, const uint32_t* __restrict__ nbig, uint3
 {
     __shared__ unsigned long long part[1024];
     const uint32_t m = min(*nbig, rec_cap);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t per = (m + 1023u) / 1024u;
-    const uint32_t b = min(tid * per, m), e = min(b + per, m);
-    unsigned long long s = 0;
-    for (uint32_t i = b; i < e; ++i) s += rec[i].rows;
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const unsigned long long v = (tid >= d) ? part[tid - d] : 0ull;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[tid] - s;
-    for (uint32_t i = b; i < e; ++i) { base[i] = run; run += rec[i].rows; }
-    if (tid == 1023) base[m] = part[1023];
+    const unsigned long long total = wg_scan_1024(part, m, [&](uint32_t i) { return (unsigned long long)rec[i].rows; },
+                                                  [&](uint32_t i, unsigned long long before) { base[i] = before; });
+    if (threadIdx.x == 1023) base[m] = total;
 }
 
 // One lane per (listed triangle, candidate row), grid-stride over all of them.

@@ -15,6 +15,7 @@
 // the block counts (64-bit totals: n = 2048 has 8.6e9 voxels), and the write pass, which redoes the word tests, scans
 // the lane counts inside the workgroup and stores each lane's records behind its block's offset.
 #include "vp_internal.h"
+#include "wg_scan.h"
 
 namespace vp {
 
@@ -57,10 +58,8 @@ extract_count(Frame f, const uint32_t* __restrict__ words, size_t nwords, uint32
     uint32_t face[6];
     for (int j = 0; j < kWordsPerLane; ++j)
         if (w0 + j < nwords) cnt += __popc(select<MODE>(f, words, w0 + j, face));
-    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    const uint32_t total = wg_sum_256(cnt, part);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 
 // one workgroup: off[i] = sum of cnt[0..i), off[m] = total
@@ -68,22 +67,9 @@ __global__ void __launch_bounds__(1024)
 extract_scan(const uint32_t* __restrict__ cnt, size_t m, unsigned long long* __restrict__ off)
 {
     __shared__ unsigned long long part[1024];
-    const size_t tid = threadIdx.x;
-    const size_t per = (m + 1023) / 1024;
-    const size_t b = min(tid * per, m), e = min(b + per, m);
-    unsigned long long s = 0;
-    for (size_t i = b; i < e; ++i) s += cnt[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned long long v = (tid >= (size_t)d) ? part[tid - d] : 0ull;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[tid] - s;
-    for (size_t i = b; i < e; ++i) { off[i] = run; run += cnt[i]; }
-    if (tid == 1023) off[m] = part[1023];
+    const unsigned long long total = wg_scan_1024(part, m, [&](size_t i) { return (unsigned long long)cnt[i]; },
+                                                  [&](size_t i, unsigned long long before) { off[i] = before; });
+    if (threadIdx.x == 1023) off[m] = total;
 }
 
 template <int MODE>
@@ -93,7 +79,6 @@ extract_write(Frame f, const uint32_t* __restrict__ words, size_t nwords, const 
 {
     __shared__ uint32_t wave_sum[4];
     const size_t w0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * kWordsPerLane;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t sel[kWordsPerLane];
     uint32_t face[kWordsPerLane][6];
     uint32_t cnt = 0;
@@ -101,17 +86,7 @@ extract_write(Frame f, const uint32_t* __restrict__ words, size_t nwords, const 
         sel[j] = (w0 + j < nwords) ? select<MODE>(f, words, w0 + j, face[j]) : 0u;
         cnt += __popc(sel[j]);
     }
-    // exclusive scan of the lane counts inside the workgroup
-    uint32_t incl = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - cnt;
-    for (int w = 0; w < wave; ++w) before += wave_sum[w];
-    unsigned long long pos = block_off[blockIdx.x] + before;
+    unsigned long long pos = block_off[blockIdx.x] + wg_exclusive_256(cnt, wave_sum);      // the lane counts before mine in the workgroup
     for (int j = 0; j < kWordsPerLane; ++j) {
         uint32_t m = sel[j];
         while (m) {

@@ -12,6 +12,7 @@
 // Both: per-block counts of vertices and quads (one launch), a one-workgroup scan of both count arrays, the vertex pass (records,
 // starting positions, rank structure), the quad pass (gathers four ranks per quad) and one Jacobi launch per relaxation step.
 #include "vp_internal.h"
+#include "wg_scan.h"
 
 namespace vp {
 
@@ -69,32 +70,12 @@ __device__ __forceinline__ uint32_t owned_edges(uint32_t mask)      // bit axis
     return ((c0 ^ ((mask >> 1) & 1u))) | ((c0 ^ ((mask >> 2) & 1u)) << 1) | ((c0 ^ ((mask >> 4) & 1u)) << 2);
 }
 
-// exclusive scan of one value per thread inside a workgroup of 256 (four waves); smem holds four words
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* smem)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) smem[wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - v;
-    for (int w = 0; w < wave; ++w) before += smem[w];
-    return before;
-}
-
+// the workgroup's vertex and quad counts in one sum (one barrier): v in the low half, q in the high half, no carry (v <= 32, q <= 96 per thread)
 __device__ __forceinline__ void block_totals(uint32_t v, uint32_t q, uint32_t* __restrict__ cnt_v, uint32_t* __restrict__ cnt_q)
 {
-    __shared__ uint32_t part[2][4];
-    for (int d = 32; d >= 1; d >>= 1) { v += __shfl_xor(v, d); q += __shfl_xor(q, d); }
-    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = v; part[1][threadIdx.x >> 6] = q; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        cnt_v[blockIdx.x] = part[0][0] + part[0][1] + part[0][2] + part[0][3];
-        cnt_q[blockIdx.x] = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-    }
+    __shared__ unsigned long long part[4];
+    const unsigned long long both = wg_sum_256((unsigned long long)v | ((unsigned long long)q << 32), part);
+    if (threadIdx.x == 0) { cnt_v[blockIdx.x] = (uint32_t)both; cnt_q[blockIdx.x] = (uint32_t)(both >> 32); }
 }
 
 // starting position of the vertex of a cell: the mean of the midpoints of its crossing edges (include/vphip.h)
@@ -136,7 +117,7 @@ sn_verts_naive(Dim d, const uint32_t* __restrict__ words, uint32_t ncells, const
     uint32_t mask = 0;
     if (c < ncells) mask = cell_mask(d, words, i, j, k);
     const uint32_t v = mask != 0u && mask != 255u;
-    const unsigned long long pos = off_v[blockIdx.x] + block_exclusive(v, smem);
+    const unsigned long long pos = off_v[blockIdx.x] + wg_exclusive_256(v, smem);
     if (c >= ncells) return;
     index[c] = v ? (uint32_t)pos : kNoVertex;
     if (v && pos < capacity) {
@@ -164,7 +145,7 @@ sn_quads_naive(Dim d, const uint32_t* __restrict__ words, uint32_t ncells, const
     uint32_t mask = 0;
     if (c < ncells) mask = cell_mask(d, words, (int)(c % d.n1), (int)((c / d.n1) % d.n1), (int)(c / (d.n1 * d.n1)));
     const uint32_t own = owned_edges(mask);
-    unsigned long long pos = off_q[blockIdx.x] + block_exclusive(__popc(own), smem);
+    unsigned long long pos = off_q[blockIdx.x] + wg_exclusive_256(__popc(own), smem);
     for (int axis = 0; axis < 3; ++axis) {
         if (!((own >> axis) & 1u)) continue;
         uint32_t q[4];
@@ -207,7 +188,7 @@ sn_verts_tiled(Dim d, const uint32_t* __restrict__ words, uint32_t nwords, const
     uint32_t c[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     if (w < nwords) corner_words(d, words, wi, j, k, c);
     uint32_t act = active_word(c);
-    unsigned long long pos = off_v[blockIdx.x] + block_exclusive(__popc(act), smem);
+    unsigned long long pos = off_v[blockIdx.x] + wg_exclusive_256(__popc(act), smem);
     if (w >= nwords) return;
     prefix[w] = (uint32_t)pos;
     while (act) {
@@ -244,7 +225,7 @@ sn_quads_tiled(Dim d, const uint32_t* __restrict__ words, uint32_t nwords, const
     if (w < nwords) corner_words(d, words, wi, (int)(row % d.n1), (int)(row / d.n1), c);
     const uint32_t e[3] = {c[0] ^ c[1], c[0] ^ c[2], c[0] ^ c[4]};
     uint32_t any = e[0] | e[1] | e[2];
-    unsigned long long pos = off_q[blockIdx.x] + block_exclusive(__popc(e[0]) + __popc(e[1]) + __popc(e[2]), smem);
+    unsigned long long pos = off_q[blockIdx.x] + wg_exclusive_256(__popc(e[0]) + __popc(e[1]) + __popc(e[2]), smem);
     while (any) {
         const int b = __ffs((int)any) - 1;
         any &= any - 1;
@@ -270,26 +251,12 @@ sn_scan(const uint32_t* __restrict__ cnt_v, const uint32_t* __restrict__ cnt_q, 
         unsigned long long* __restrict__ off_q)
 {
     __shared__ unsigned long long part[1024];
-    const size_t tid = threadIdx.x;
-    const size_t per = (m + 1023) / 1024;
-    const size_t b = min(tid * per, m), e = min(b + per, m);
     for (int which = 0; which < 2; ++which) {
         const uint32_t* cnt = which ? cnt_q : cnt_v;
         unsigned long long* off = which ? off_q : off_v;
-        unsigned long long s = 0;
-        for (size_t i = b; i < e; ++i) s += cnt[i];
-        __syncthreads();
-        part[tid] = s;
-        __syncthreads();
-        for (int dd = 1; dd < 1024; dd <<= 1) {
-            const unsigned long long v = (tid >= (size_t)dd) ? part[tid - dd] : 0ull;
-            __syncthreads();
-            part[tid] += v;
-            __syncthreads();
-        }
-        unsigned long long run = part[tid] - s;
-        for (size_t i = b; i < e; ++i) { off[i] = run; run += cnt[i]; }
-        if (tid == 1023) off[m] = part[1023];
+        const unsigned long long total = wg_scan_1024(part, m, [&](size_t i) { return (unsigned long long)cnt[i]; },
+                                                      [&](size_t i, unsigned long long before) { off[i] = before; });
+        if (threadIdx.x == 1023) off[m] = total;
     }
 }
 

@@ -28,6 +28,7 @@
 // All float math below must not be contracted into FMAs: the file is built with
 // -ffp-contract=off and carries the pragma as well.
 #include "vp_internal.h"
+#include "wg_scan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -199,22 +200,8 @@ __global__ void __launch_bounds__(1024)
 vox_scan(const uint32_t* __restrict__ cnt, uint32_t m, uint32_t* __restrict__ off, uint32_t* __restrict__ cur)
 {
     __shared__ uint32_t part[1024];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t per = (m + 1023u) / 1024u;
-    const uint32_t b = min(tid * per, m), e = min(b + per, m);
-    uint32_t s = 0;
-    for (uint32_t i = b; i < e; ++i) s += cnt[i];
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint32_t v = (tid >= d) ? part[tid - d] : 0u;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - s;
-    for (uint32_t i = b; i < e; ++i) { off[i] = run; cur[i] = run; run += cnt[i]; }
-    if (tid == 1023) off[m] = part[1023];
+    const uint32_t total = wg_scan_1024(part, m, [&](uint32_t i) { return cnt[i]; }, [&](uint32_t i, uint32_t before) { off[i] = before; cur[i] = before; });
+    if (threadIdx.x == 1023) off[m] = total;
 }
 
 // One thread per record of the compact large-triangle list.  The list length is only known on the device (*nbig):

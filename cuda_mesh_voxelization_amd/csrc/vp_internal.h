@@ -135,7 +135,7 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 int reserve(vp_ctx* ctx, Buffer& b, size_t bytes, bool headroom = true);
 void release(Buffer& b);
 
-// RAII-less profiling bracket: begin() before the launch, end() after.
+// RAII profiling bracket: the constructor records the start event on the stream, the destructor the end event (scope = the launches timed).
 struct ProfScope {
     vp_ctx* ctx; int kernel; hipEvent_t a = nullptr, b = nullptr;
     ProfScope(vp_ctx* c, int k);

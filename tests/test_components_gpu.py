@@ -105,6 +105,27 @@ def test_random_grids(engine, n, conn):
             assert np.array_equal(st, sizes_of(ref, k))
 
 
+def test_isolated_voxels_are_ranked_in_flat_order(engine):
+    """n = 224 has 224^3 / 8192 = 1372 chunks (more than 1024, no multiple of it): in the one-workgroup scan of the root counts every thread
+    serves two chunks and threads 686 .. 1023 none.  A random subset of the voxels whose three coordinates are all even: no two of them
+    are 26-adjacent, so every set voxel is a component, K is their number and -- the header's scipy-order contract -- the label of a set
+    voxel is its 1-based rank in flat (x fastest) order: one cumsum.  Every chunk and every round of comp_rank holds some of them."""
+    n = 224
+    vox = np.zeros((n, n, n), bool)
+    vox[::2, ::2, ::2] = np.random.default_rng(224).random((n // 2, n // 2, n // 2)) < 0.5
+    flat = vox.reshape(-1)
+    exp = np.where(flat, np.cumsum(flat), 0).astype(np.uint32)
+    k = int(flat.sum())
+    assert k > n ** 3 // 20
+    words = _dev(engine, bool_to_words(vox))
+    for conn in CONNS:
+        for algo in (ALGO_TILED, ALGO_NAIVE):
+            labels, got = engine.components_label(_unit_frame(n), words, conn, algo)
+            assert got == k, (conn, algo, got, k)
+            labels = labels.cpu().numpy().view(np.uint32)
+            assert np.array_equal(labels, exp), (conn, algo, np.flatnonzero(labels != exp)[:8].tolist())
+
+
 @pytest.mark.parametrize("n", [64, 256])
 def test_long_chains_in_a_maze(engine, n):
     words, corridor = maze(n, seed=n)

@@ -784,6 +784,28 @@ def test_extract_records_match_numpy(engine):
                 assert np.array_equal(r2[:10].view(np.uint64), exp[:10]) and (r2[10:] == -1).all()
 
 
+def test_extract_ragged_block_count_scan(engine):
+    """n = 416 has 416^3 / 65536 = 1099 count blocks (more than 1024, no multiple of it): in the one-workgroup scan of the block counts every
+    thread serves two blocks, thread 549 a single one, threads 550 .. 1023 none, and the last count block is half full.  A sparse random
+    grid with its first and last voxel set; count and records against np.flatnonzero of the unpacked bits."""
+    from cuda_mesh_voxelization_amd.capi import EXTRACT_SET
+    n = 416
+    fr = Frame.make(n, 1.0, (0, 0, 0))
+    idx = np.random.default_rng(416).integers(0, n ** 3, size=n ** 3 // 1000, dtype=np.int64)       # about one voxel in a thousand
+    idx = np.concatenate([idx, np.array([0, n ** 3 - 1], np.int64)])
+    words = np.zeros(n ** 3 // 32, np.uint32)
+    np.bitwise_or.at(words, idx >> 5, np.uint32(1) << (idx & 31).astype(np.uint32))
+    exp = np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little")).astype(np.uint64)
+    assert exp[0] == 0 and exp[-1] == n ** 3 - 1 and 70000 < exp.size <= idx.size
+    g = torch.from_numpy(words.view(np.int32)).to(engine.device)
+    cnt = engine.ctx.extract_count(fr, g.data_ptr(), EXTRACT_SET)
+    assert cnt == exp.size
+    rec = torch.zeros(cnt, dtype=torch.int64, device=engine.device)
+    engine.ctx.extract(fr, g.data_ptr(), EXTRACT_SET, None, rec.data_ptr(), None, cnt)
+    engine.sync()
+    assert np.array_equal(rec.cpu().numpy().view(np.uint64), exp)
+
+
 def test_window_calls_check_their_arguments(engine):
     """vp_jfa_window_*: a window that is too small for its `planes`, planes of the frame that do not fit it, halo planes a pass would read
     outside it, windows of different geometry, a bad stride, n below the tile kernels -- all VP_ERR_INVALID / UNSUPPORTED, nothing launched
