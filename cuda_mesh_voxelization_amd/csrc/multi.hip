@@ -82,6 +82,9 @@ int grow(Rank& r, Buffer& b, size_t bytes)
     return reserve(r.ctx, b, bytes ? bytes : 1);
 }
 
+// the window of `planes` id planes in b, positioned for a frame whose first plane is plane `at` of it
+vp_window window(const Buffer& b, uint32_t planes, uint32_t at) { return vp_window{b.ptr, b.bytes, planes, at}; }
+
 // The id windows of a rank (two buffers of `planes` id planes in the library's layout, include/vphip.h: vp_jfa_window_*).  They are
 // cleared -- every id := "none" -- whenever their geometry changes: the ghost regions below are rounded OUTWARDS to the 8-plane tile, and
 // the excess planes of a pass read planes the pass before it never produced (see ghost_regions).  What they read is then "none" or ids an
@@ -105,7 +108,7 @@ int ensure_window_set(Rank& r, Buffer* bufs, int nbufs, uint32_t& gn, uint32_t& 
     fresh = fresh || poison != nullptr;
 #endif
     if (fresh)
-        for (int i = 0; i < nbufs; ++i) { const vp_window w{bufs[i].ptr, bufs[i].bytes, planes, 0}; VP_TRY(vp_jfa_window_clear(r.ctx, &G, &w)); }
+        for (int i = 0; i < nbufs; ++i) { const vp_window w = window(bufs[i], planes, 0); VP_TRY(vp_jfa_window_clear(r.ctx, &G, &w)); }
 #ifdef VP_TEST_HOOKS
     if (poison)
         for (int i = 0; i < nbufs; ++i) VP_HIP(hipMemsetAsync(bufs[i].ptr, (int)strtol(poison, nullptr, 0) & 0xFF, (size_t)planes * G.n * G.n * 4, r.ctx->stream));
@@ -173,10 +176,10 @@ int fence_copies(vp_multi* m)
 }
 
 // Every rank keeps its slab at its GLOBAL position inside a buffer of the whole grid (n^3/8 bytes, small next to the id
-// volumes): the halo mode uses the slab alone, the ghost mode fills in the rest.
-char* slab_words(const vp_multi* m, const Rank& r)
+// volumes): the halo mode uses the slab alone, the ghost mode fills in the rest.  The words of global plane z in it:
+uint32_t* plane_ptr(const vp_frame& G, const Rank& r, uint32_t z)
 {
-    return (char*)r.words.ptr + (size_t)r.z0 * ((size_t)m->frame.n * m->frame.n / 8);
+    return (uint32_t*)r.words.ptr + (size_t)z * ((size_t)G.n * G.n / 32);
 }
 
 struct HaloMove { uint32_t src, dst; bool minusSide; uint32_t g0, g1; };
@@ -201,29 +204,63 @@ std::vector<HaloMove> halo_plan(uint32_t n, uint32_t world, uint32_t k)
     return plan;
 }
 
+// ---- the planner: every plan below is made of these three (slab.py states the same three: steps, widened, reads)
 struct Region { uint32_t k, b0, b1; };
 
-// Planes each pass must produce on a rank so that no exchange is needed: the slab widened by the sum of the later steps
-// (its REACH g_i), rounded outwards to the 8-plane tile and clipped to the grid.
+// the steps n/2, n/4, ..., 1 of a JFA (jfa/sequential.cpp:72)
+std::vector<uint32_t> steps(uint32_t n)
+{
+    std::vector<uint32_t> ks;
+    for (uint32_t k = n / 2; k >= 1; k /= 2) ks.push_back(k);
+    return ks;
+}
+
+// In pass order: the planes the pass with step k_i must produce so that the passes after it need no exchange -- [z0, z1) widened by the
+// sum of the LATER steps of ks (its REACH g_i), rounded outwards to the 8-plane tile, clipped to the grid.
+std::vector<Region> widened(uint32_t n, uint32_t z0, uint32_t z1, const std::vector<uint32_t>& ks)
+{
+    std::vector<Region> out;
+    uint32_t g = 0;
+    for (uint32_t k : ks) g += k;
+    for (uint32_t k : ks) {
+        g -= k;
+        out.push_back({k, z0 > g ? (z0 - g) / 8 * 8 : 0, std::min(n, (z1 + g + 7) / 8 * 8)});
+    }
+    return out;
+}
+
+// [lo, hi) grown to hold what passes that READ ids read on regs[first ...]: k planes beyond each region, clipped
+void add_reads(uint32_t n, const std::vector<Region>& regs, size_t first, uint32_t& lo, uint32_t& hi)
+{
+    for (size_t i = first; i < regs.size(); ++i) {
+        const Region& r = regs[i];
+        lo = std::min(lo, r.b0 > r.k ? r.b0 - r.k : 0);
+        hi = std::max(hi, std::min(n, r.b1 + r.k));
+    }
+}
+
+// VP_MULTI_GHOST: `widened` for every step of the grid.
 // Invariant (tests/test_multi_gpu.py::test_multi_ghost_ignores_unproduced_planes): a plane of region i is NEEDED iff it lies within
 // g_i of the slab; needed planes of pass i read only planes within g_i + k_i = g_(i-1) of the slab, all of which pass i - 1 produced.
 // The planes the rounding adds are computed too (whole tiles) but from planes pass i - 1 may not have produced -- their values are
 // never read by a needed plane of any later pass, so the slab is exact whatever those planes held (grow_ids gives them defined bytes).
 // Rounding the regions so that each contains the next one widened by its step instead would cost up to 16 more planes per side
 // and pass (k = 8: 24 instead of 8), i.e. time, for values nobody reads.
-std::vector<Region> ghost_regions(uint32_t n, uint32_t z0, uint32_t z1)
+std::vector<Region> ghost_regions(uint32_t n, uint32_t z0, uint32_t z1) { return widened(n, z0, z1, steps(n)); }
+
+// The passes of regs[first ...] on the id windows of a rank (`planes` planes, plane 0 = global plane lo), ping-ponging from me.ids[cur];
+// fuseLast: the last region -- the bare slab -- is the last pass with the id -> sdf conversion.
+int run_regions(Rank& me, const vp_frame& G, const std::vector<Region>& regs, size_t first, uint32_t planes, uint32_t lo, int& cur, bool fuseLast, float fill)
 {
-    std::vector<uint32_t> ks;
-    for (uint32_t k = n / 2; k >= 1; k /= 2) ks.push_back(k);
-    std::vector<Region> out;
-    for (size_t i = 0; i < ks.size(); ++i) {
-        uint32_t g = 0;
-        for (size_t j = i + 1; j < ks.size(); ++j) g += ks[j];
-        const uint32_t b0 = z0 > g ? (z0 - g) / 8 * 8 : 0;
-        const uint32_t b1 = std::min(n, (z1 + g + 7) / 8 * 8);
-        out.push_back({ks[i], b0, b1});
+    for (size_t i = first; i < regs.size(); ++i) {
+        const Region& g = regs[i];
+        const vp_frame f = slab_frame(G, g.b0, g.b1);
+        const vp_window in = window(me.ids[cur], planes, g.b0 - lo), out = window(me.ids[cur ^ 1], planes, g.b0 - lo);
+        if (fuseLast && i + 1 == regs.size()) VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, 1, plane_ptr(G, me, g.b0), fill, (float*)me.sdf.ptr));
+        else                                  VP_TRY(vp_jfa_window_pass(me.ctx, &f, g.k, &in, &out, g.k));
+        cur ^= 1;
     }
-    return out;
+    return 0;
 }
 
 // `count` id planes from index `sp` of a window of src (splanes planes) to index `dp` of a window of dst (dplanes): one or two byte ranges
@@ -291,19 +328,19 @@ int jfa_halo(vp_multi* m, float fill)
     for (Rank& r : m->ranks) VP_TRY(mark_ready(r));
     for (uint32_t r = 0; r < world; ++r) {
         Rank& me = m->ranks[r];
-        if (r > 0) VP_TRY(peer_copy(m, me, me.below.ptr, m->ranks[r - 1], slab_words(m, m->ranks[r - 1]) + (size_t)(nz - 1) * planeWords, planeWords));
-        if (r + 1 < world) VP_TRY(peer_copy(m, me, me.above.ptr, m->ranks[r + 1], slab_words(m, m->ranks[r + 1]), planeWords));
+        if (r > 0) VP_TRY(peer_copy(m, me, me.below.ptr, m->ranks[r - 1], plane_ptr(G, m->ranks[r - 1], me.z0 - 1), planeWords));
+        if (r + 1 < world) VP_TRY(peer_copy(m, me, me.above.ptr, m->ranks[r + 1], plane_ptr(G, m->ranks[r + 1], me.z1), planeWords));
     }
     if (world > 1) VP_TRY(fence_copies(m));
     int cur = 0;
     for (uint32_t r = 0; r < world; ++r) {
         Rank& me = m->ranks[r];
         const vp_frame f = slab_frame(G, me.z0, me.z1);
-        const vp_window w{me.ids[cur].ptr, me.ids[cur].bytes, planes, at};
-        VP_TRY(vp_jfa_window_init(me.ctx, &f, (const uint32_t*)slab_words(m, me), r > 0 ? (const uint32_t*)me.below.ptr : nullptr,
+        const vp_window w = window(me.ids[cur], planes, at);
+        VP_TRY(vp_jfa_window_init(me.ctx, &f, plane_ptr(G, me, me.z0), r > 0 ? (const uint32_t*)me.below.ptr : nullptr,
                                   r + 1 < world ? (const uint32_t*)me.above.ptr : nullptr, &w));
     }
-    for (uint32_t k = n / 2; k >= 1; k /= 2) {
+    for (const uint32_t k : steps(n)) {
         const uint32_t stride = (world > 1 && k >= nz) ? nz : k;
         if (world > 1) {
             for (Rank& r : m->ranks) VP_TRY(mark_ready(r));
@@ -320,8 +357,8 @@ int jfa_halo(vp_multi* m, float fill)
         for (uint32_t r = 0; r < world; ++r) {
             Rank& me = m->ranks[r];
             const vp_frame f = slab_frame(G, me.z0, me.z1);
-            const vp_window in{me.ids[cur].ptr, me.ids[cur].bytes, planes, at}, out{me.ids[cur ^ 1].ptr, me.ids[cur ^ 1].bytes, planes, at};
-            if (k == 1) VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, stride, (const uint32_t*)slab_words(m, me), fill, (float*)me.sdf.ptr));
+            const vp_window in = window(me.ids[cur], planes, at), out = window(me.ids[cur ^ 1], planes, at);
+            if (k == 1) VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, stride, plane_ptr(G, me, me.z0), fill, (float*)me.sdf.ptr));
             else        VP_TRY(vp_jfa_window_pass(me.ctx, &f, k, &in, &out, stride));
         }
         cur ^= 1;
@@ -336,10 +373,9 @@ int jfa_ghost(vp_multi* m, float fill)
 {
     const vp_frame& G = m->frame;
     const uint32_t n = G.n, world = (uint32_t)m->ranks.size(), nz = n / world;
-    const size_t planeWords = (size_t)n * n / 8;
     m->last_mode = VP_MULTI_GHOST;                                  // (also what VP_MULTI_TRANSPOSE runs where no step is a multiple of the device count)
     for (Rank& r : m->ranks) {
-        VP_TRY(grow(r, r.border, (size_t)n * planeWords));
+        VP_TRY(grow(r, r.border, vp_grid_words(&G) * 4));
         VP_TRY(ensure_windows(r, G, n));
         VP_TRY(grow(r, r.sdf, (size_t)nz * n * n * 4));
     }
@@ -348,19 +384,11 @@ int jfa_ghost(vp_multi* m, float fill)
     VP_TRY(gather_words(m));
     for (uint32_t r = 0; r < world; ++r) {
         Rank& me = m->ranks[r];
-        const std::vector<Region> regs = ghost_regions(n, me.z0, me.z1);
-        const uint32_t* words = (const uint32_t*)me.words.ptr;
         int cur = 0;
-        VP_TRY(vp_surface(me.ctx, &G, words, nullptr, nullptr, (uint32_t*)me.border.ptr));
-        { const vp_window w{me.ids[cur].ptr, me.ids[cur].bytes, n, 0}; VP_TRY(vp_jfa_window_first_two(me.ctx, &G, (const uint32_t*)me.border.ptr, &w)); }
-        for (size_t i = 2; i < regs.size(); ++i) {
-            const Region& g = regs[i];
-            const vp_frame f = slab_frame(G, g.b0, g.b1);
-            const vp_window in{me.ids[cur].ptr, me.ids[cur].bytes, n, g.b0}, out{me.ids[cur ^ 1].ptr, me.ids[cur ^ 1].bytes, n, g.b0};
-            if (i + 1 == regs.size()) VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, 1, words + (size_t)g.b0 * (planeWords / 4), fill, (float*)me.sdf.ptr));
-            else                      VP_TRY(vp_jfa_window_pass(me.ctx, &f, g.k, &in, &out, g.k));
-            cur ^= 1;
-        }
+        VP_TRY(vp_surface(me.ctx, &G, plane_ptr(G, me, 0), nullptr, nullptr, (uint32_t*)me.border.ptr));
+        const vp_window w = window(me.ids[cur], n, 0);
+        VP_TRY(vp_jfa_window_first_two(me.ctx, &G, (const uint32_t*)me.border.ptr, &w));
+        VP_TRY(run_regions(me, G, ghost_regions(n, me.z0, me.z1), 2, n, 0, cur, true, fill));
     }
     return 0;
 }
@@ -375,21 +403,15 @@ struct HybridPlan { std::vector<Region> wide; std::vector<uint32_t> narrow; uint
 HybridPlan hybrid_plan(uint32_t n, uint32_t world, uint32_t z0, uint32_t z1, bool maskStart)
 {
     HybridPlan p;
-    const uint32_t nz = z1 - z0, H = world > 1 ? nz / 2 : 0;
+    const uint32_t H = world > 1 ? (z1 - z0) / 2 : 0;
     std::vector<uint32_t> wideK;
-    for (uint32_t k = n / 2; k >= 1; k /= 2) { if (k > H) wideK.push_back(k); else p.narrow.push_back(k); }
-    for (size_t i = 0; i < wideK.size(); ++i) {
-        uint32_t g = 0;
-        for (size_t j = i + 1; j < wideK.size(); ++j) g += wideK[j];
-        p.wide.push_back({wideK[i], z0 > g ? (z0 - g) / 8 * 8 : 0, std::min(n, (z1 + g + 7) / 8 * 8)});
-    }
+    for (const uint32_t k : steps(n)) (k > H ? wideK : p.narrow).push_back(k);
+    p.wide = widened(n, z0, z1, wideK);
     // window: the slab with room for the narrow halos, every wide region, and what a wide pass that READS ids reads beyond its region
+    // (maskStart: the first one starts from the border mask and reads none)
     p.lo = z0 > H ? z0 - H : 0; p.hi = std::min(n, z1 + H);
-    for (size_t i = 0; i < p.wide.size(); ++i) {
-        const Region& r = p.wide[i];
-        p.lo = std::min(p.lo, r.b0); p.hi = std::max(p.hi, r.b1);
-        if (i > 0 || !maskStart) { p.lo = std::min(p.lo, r.b0 > r.k ? r.b0 - r.k : 0); p.hi = std::max(p.hi, std::min(n, r.b1 + r.k)); }
-    }
+    for (const Region& r : p.wide) { p.lo = std::min(p.lo, r.b0); p.hi = std::max(p.hi, r.b1); }
+    add_reads(n, p.wide, maskStart ? 1 : 0, p.lo, p.hi);
     return p;
 }
 
@@ -397,7 +419,6 @@ int jfa_hybrid(vp_multi* m, float fill)
 {
     const vp_frame& G = m->frame;
     const uint32_t n = G.n, world = (uint32_t)m->ranks.size(), nz = n / world;
-    const size_t planeWords = (size_t)n * n / 8;
     const bool maskStart = vp_jfa_can_start_from_mask(&G, VP_ALGO_TILED) != 0;
     std::vector<HybridPlan> plans;
     m->window_lo.assign(world, 0); m->window_hi.assign(world, 0);
@@ -406,7 +427,7 @@ int jfa_hybrid(vp_multi* m, float fill)
         plans.push_back(hybrid_plan(n, world, me.z0, me.z1, maskStart));
         const HybridPlan& p = plans.back();
         m->window_lo[r] = p.lo; m->window_hi[r] = p.hi;
-        VP_TRY(grow(me, me.border, (size_t)n * planeWords));
+        VP_TRY(grow(me, me.border, vp_grid_words(&G) * 4));
         VP_TRY(ensure_windows(me, G, p.hi - p.lo));
         VP_TRY(grow(me, me.sdf, (size_t)nz * n * n * 4));
     }
@@ -415,15 +436,14 @@ int jfa_hybrid(vp_multi* m, float fill)
     const size_t nwide = plans[0].wide.size(), nnarrow = plans[0].narrow.size();     // the same on every rank (they depend on nz only)
     std::vector<int> cur(world, 0);
     // window `which` of rank r, positioned for a frame that starts at global plane g
-    auto win = [&](uint32_t r, int which, uint32_t g) { return vp_window{m->ranks[r].ids[which].ptr, m->ranks[r].ids[which].bytes, plans[r].hi - plans[r].lo, g - plans[r].lo}; };
+    auto win = [&](uint32_t r, int which, uint32_t g) { return window(m->ranks[r].ids[which], plans[r].hi - plans[r].lo, g - plans[r].lo); };
     // ---- wide passes: ghost planes inside the window, no exchange
     for (uint32_t r = 0; r < world; ++r) {
         Rank& me = m->ranks[r];
         const HybridPlan& p = plans[r];
-        const uint32_t* words = (const uint32_t*)me.words.ptr;
         size_t start = 0;
         if (maskStart && nwide > 0) {
-            VP_TRY(vp_surface(me.ctx, &G, words, nullptr, nullptr, (uint32_t*)me.border.ptr));
+            VP_TRY(vp_surface(me.ctx, &G, plane_ptr(G, me, 0), nullptr, nullptr, (uint32_t*)me.border.ptr));
             const vp_frame f = slab_frame(G, p.wide[0].b0, p.wide[0].b1);
             const vp_window w = win(r, 1, p.wide[0].b0);
             VP_TRY(vp_jfa_window_first_pass(me.ctx, &f, (const uint32_t*)me.border.ptr, &w));
@@ -431,19 +451,9 @@ int jfa_hybrid(vp_multi* m, float fill)
         } else {
             const vp_frame f = slab_frame(G, p.lo, p.hi);
             const vp_window w = win(r, 0, p.lo);
-            VP_TRY(vp_jfa_window_init(me.ctx, &f, words + (size_t)p.lo * (planeWords / 4), p.lo > 0 ? words + (size_t)(p.lo - 1) * (planeWords / 4) : nullptr,
-                                      p.hi < n ? words + (size_t)p.hi * (planeWords / 4) : nullptr, &w));
+            VP_TRY(vp_jfa_window_init(me.ctx, &f, plane_ptr(G, me, p.lo), p.lo > 0 ? plane_ptr(G, me, p.lo - 1) : nullptr, p.hi < n ? plane_ptr(G, me, p.hi) : nullptr, &w));
         }
-        for (size_t i = start; i < nwide; ++i) {
-            const Region& g = p.wide[i];
-            const vp_frame f = slab_frame(G, g.b0, g.b1);
-            const vp_window in = win(r, cur[r], g.b0), out = win(r, cur[r] ^ 1, g.b0);
-            if (i + 1 == nwide && nnarrow == 0)                     // one rank: the last pass is a wide one
-                VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, 1, words + (size_t)g.b0 * (planeWords / 4), fill, (float*)me.sdf.ptr));
-            else
-                VP_TRY(vp_jfa_window_pass(me.ctx, &f, g.k, &in, &out, g.k));
-            cur[r] ^= 1;
-        }
+        VP_TRY(run_regions(me, G, p.wide, start, p.hi - p.lo, p.lo, cur[r], /*fuseLast=*/nnarrow == 0, fill));     // one rank: the last pass is a wide one
     }
     // ---- narrow passes: k halo planes from each adjacent rank, device to device, then the bare slab
     for (size_t j = 0; j < nnarrow; ++j) {
@@ -462,8 +472,7 @@ int jfa_hybrid(vp_multi* m, float fill)
             Rank& me = m->ranks[r];
             const vp_frame f = slab_frame(G, me.z0, me.z1);
             const vp_window in = win(r, cur[r], me.z0), out = win(r, cur[r] ^ 1, me.z0);
-            const uint32_t* slabW = (const uint32_t*)me.words.ptr + (size_t)me.z0 * (planeWords / 4);
-            if (j + 1 == nnarrow) VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, 1, slabW, fill, (float*)me.sdf.ptr));
+            if (j + 1 == nnarrow) VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, 1, plane_ptr(G, me, me.z0), fill, (float*)me.sdf.ptr));
             else                  VP_TRY(vp_jfa_window_pass(me.ctx, &f, k, &in, &out, k));
             cur[r] ^= 1;
         }
@@ -478,23 +487,22 @@ int jfa_hybrid(vp_multi* m, float fill)
 // one peer copy per pair of devices (two above n = 1024) into chunk s of t's staging window, straight from the window the last cyclic pass
 // wrote -- no pack.  Phase B: vp_jfa_window_interleave weaves the chunks into consecutive planes and the remaining steps run on the slab
 // widened by their reach, as the last regions of the ghost mode do.  The one-process form of slab.py's TransposeSlabPipeline.
-struct TransposePlan { uint32_t c; std::vector<Region> regs; uint32_t t0, t1, lo, hi; };
+struct TransposePlan { std::vector<Region> regs; uint32_t t0, t1, lo, hi; };
 
 TransposePlan transpose_plan(uint32_t n, uint32_t world, uint32_t z0, uint32_t z1, uint32_t c)
 {
     TransposePlan p;
-    p.c = c;
-    const std::vector<Region> all = ghost_regions(n, z0, z1);
+    std::vector<uint32_t> ks = steps(n);
+    ks.erase(ks.begin(), ks.begin() + c);                            // the steps of the slab phase
+    p.regs = widened(n, z0, z1, ks);
     uint32_t g = 0;
-    for (size_t i = c; i < all.size(); ++i) { p.regs.push_back(all[i]); g += all[i].k; }
+    for (const uint32_t k : ks) g += k;
     p.t0 = z0 > g ? (z0 - g) / world * world : 0;
     p.t1 = std::min(n, (z1 + g + world - 1) / world * world);
     p.lo = p.t0; p.hi = p.t1;
-    for (const Region& r : p.regs) { p.lo = std::min(p.lo, r.b0 > r.k ? r.b0 - r.k : 0); p.hi = std::max(p.hi, std::min(n, r.b1 + r.k)); }
+    add_reads(n, p.regs, 0, p.lo, p.hi);
     return p;
 }
-
-int jfa_ghost(vp_multi* m, float fill);
 
 int jfa_transpose(vp_multi* m, float fill)
 {
@@ -502,7 +510,6 @@ int jfa_transpose(vp_multi* m, float fill)
     const uint32_t n = G.n, world = (uint32_t)m->ranks.size(), nz = n / world;
     const uint32_t c = (uint32_t)vp_jfa_cyclic_passes(&G, world);
     if (c == 0) return jfa_ghost(m, fill);                          // nothing to deal cyclically (one device, a count that is not a power of two)
-    const size_t planeWords = (size_t)n * n / 8;
     std::vector<TransposePlan> plans;
     m->window_lo.assign(world, 0); m->window_hi.assign(world, 0);
     for (uint32_t r = 0; r < world; ++r) {
@@ -510,7 +517,7 @@ int jfa_transpose(vp_multi* m, float fill)
         plans.push_back(transpose_plan(n, world, me.z0, me.z1, c));
         const TransposePlan& p = plans.back();
         m->window_lo[r] = p.lo; m->window_hi[r] = p.hi;
-        VP_TRY(grow(me, me.border, (size_t)n * planeWords));
+        VP_TRY(grow(me, me.border, vp_grid_words(&G) * 4));
         VP_TRY(ensure_window_set(me, me.cyc, 2, me.cyc_n, me.cyc_planes, G, nz));
         VP_TRY(ensure_window_set(me, &me.staging, 1, me.stg_n, me.stg_planes, G, p.t1 - p.t0));
         VP_TRY(ensure_windows(me, G, p.hi - p.lo));
@@ -519,15 +526,16 @@ int jfa_transpose(vp_multi* m, float fill)
     // every device needs the bitmask of the whole grid: the border bits of its planes z = r (mod G) depend on the planes z -+ 1
     VP_TRY(gather_words(m));
     // ---- phase A: cyclic planes, no exchange
+    const std::vector<uint32_t> ks = steps(n);
     std::vector<int> cur(world, 0);
     for (uint32_t r = 0; r < world; ++r) {
         Rank& me = m->ranks[r];
-        VP_TRY(vp_surface(me.ctx, &G, (const uint32_t*)me.words.ptr, nullptr, nullptr, (uint32_t*)me.border.ptr));
-        { const vp_window w{me.cyc[0].ptr, me.cyc[0].bytes, nz, 0}; VP_TRY(vp_jfa_window_first_two_cyclic(me.ctx, &G, (const uint32_t*)me.border.ptr, &w, world, r)); }
-        uint32_t k = n / 8;
-        for (uint32_t i = 2; i < c; ++i, k /= 2) {
-            const vp_window in{me.cyc[cur[r]].ptr, me.cyc[cur[r]].bytes, nz, 0}, out{me.cyc[cur[r] ^ 1].ptr, me.cyc[cur[r] ^ 1].bytes, nz, 0};
-            VP_TRY(vp_jfa_window_pass_cyclic(me.ctx, &G, k, &in, &out, world, r));
+        VP_TRY(vp_surface(me.ctx, &G, plane_ptr(G, me, 0), nullptr, nullptr, (uint32_t*)me.border.ptr));
+        const vp_window w = window(me.cyc[0], nz, 0);
+        VP_TRY(vp_jfa_window_first_two_cyclic(me.ctx, &G, (const uint32_t*)me.border.ptr, &w, world, r));
+        for (uint32_t i = 2; i < c; ++i) {
+            const vp_window in = window(me.cyc[cur[r]], nz, 0), out = window(me.cyc[cur[r] ^ 1], nz, 0);
+            VP_TRY(vp_jfa_window_pass_cyclic(me.ctx, &G, ks[i], &in, &out, world, r));
             cur[r] ^= 1;
         }
     }
@@ -547,21 +555,10 @@ int jfa_transpose(vp_multi* m, float fill)
     for (uint32_t r = 0; r < world; ++r) {
         Rank& me = m->ranks[r];
         const TransposePlan& p = plans[r];
-        const uint32_t planes = p.hi - p.lo, count = (p.t1 - p.t0) / world;
-        const uint32_t* words = (const uint32_t*)me.words.ptr;
+        const vp_window in = window(me.staging, p.t1 - p.t0, 0), out = window(me.ids[0], p.hi - p.lo, p.t0 - p.lo);
+        VP_TRY(vp_jfa_window_interleave(me.ctx, &G, &in, &out, world, (p.t1 - p.t0) / world));
         int w = 0;
-        {
-            const vp_window in{me.staging.ptr, me.staging.bytes, p.t1 - p.t0, 0}, out{me.ids[0].ptr, me.ids[0].bytes, planes, p.t0 - p.lo};
-            VP_TRY(vp_jfa_window_interleave(me.ctx, &G, &in, &out, world, count));
-        }
-        for (size_t i = 0; i < p.regs.size(); ++i) {
-            const Region& g = p.regs[i];
-            const vp_frame f = slab_frame(G, g.b0, g.b1);
-            const vp_window in{me.ids[w].ptr, me.ids[w].bytes, planes, g.b0 - p.lo}, out{me.ids[w ^ 1].ptr, me.ids[w ^ 1].bytes, planes, g.b0 - p.lo};
-            if (i + 1 == p.regs.size()) VP_TRY(vp_jfa_window_last_pass(me.ctx, &f, &in, &out, 1, words + (size_t)g.b0 * (planeWords / 4), fill, (float*)me.sdf.ptr));
-            else                        VP_TRY(vp_jfa_window_pass(me.ctx, &f, g.k, &in, &out, g.k));
-            w ^= 1;
-        }
+        VP_TRY(run_regions(me, G, p.regs, 0, p.hi - p.lo, p.lo, w, true, fill));
     }
     return 0;
 }
@@ -650,7 +647,7 @@ int vp_multi_voxelize(vp_multi* m, const vp_frame* f, int algo)
     for (Rank& r : m->ranks) {
         VP_TRY(grow(r, r.words, vp_grid_words(f) * 4));
         const vp_frame sf = slab_frame(*f, r.z0, r.z1);
-        VP_TRY(vp_voxelize(r.ctx, &sf, (uint32_t*)slab_words(m, r), (const float*)r.mesh_xyz.ptr, m->nverts, (const uint32_t*)r.mesh_tri.ptr, m->ntris, algo, 0));
+        VP_TRY(vp_voxelize(r.ctx, &sf, plane_ptr(*f, r, r.z0), (const float*)r.mesh_xyz.ptr, m->nverts, (const uint32_t*)r.mesh_tri.ptr, m->ntris, algo, 0));
     }
     m->have_grid = true;
     return 0;
@@ -665,7 +662,7 @@ int vp_multi_set_grid(vp_multi* m, const vp_frame* f, const uint32_t* h_words)
     const size_t planeWords = (size_t)f->n * f->n / 8;
     for (Rank& r : m->ranks) {
         VP_TRY(grow(r, r.words, vp_grid_words(f) * 4));
-        VP_HIP(hipMemcpyAsync(slab_words(m, r), (const char*)h_words + (size_t)r.z0 * planeWords, (size_t)(r.z1 - r.z0) * planeWords, hipMemcpyHostToDevice, r.ctx->stream));
+        VP_HIP(hipMemcpyAsync(plane_ptr(*f, r, r.z0), (const char*)h_words + (size_t)r.z0 * planeWords, (size_t)(r.z1 - r.z0) * planeWords, hipMemcpyHostToDevice, r.ctx->stream));
     }
     VP_TRY(vp_multi_sync(m));
     m->have_grid = true;
@@ -678,7 +675,7 @@ int vp_multi_get_grid(vp_multi* m, uint32_t* h_words)
     const size_t planeWords = (size_t)m->frame.n * m->frame.n / 8;
     for (Rank& r : m->ranks) {
         VP_TRY(bind(r));
-        VP_HIP(hipMemcpyAsync((char*)h_words + (size_t)r.z0 * planeWords, slab_words(m, r), (size_t)(r.z1 - r.z0) * planeWords, hipMemcpyDeviceToHost, r.ctx->stream));
+        VP_HIP(hipMemcpyAsync((char*)h_words + (size_t)r.z0 * planeWords, plane_ptr(m->frame, r, r.z0), (size_t)(r.z1 - r.z0) * planeWords, hipMemcpyDeviceToHost, r.ctx->stream));
     }
     return vp_multi_sync(m);
 }
@@ -693,7 +690,7 @@ int vp_multi_csg(vp_multi* m, const uint32_t* h_other, size_t nwords, int op)
         const size_t bytes = (size_t)(r.z1 - r.z0) * planeWords;
         VP_TRY(grow(r, r.other, bytes));
         VP_HIP(hipMemcpyAsync(r.other.ptr, (const char*)h_other + (size_t)r.z0 * planeWords, bytes, hipMemcpyHostToDevice, r.ctx->stream));
-        VP_TRY(vp_csg(r.ctx, (uint32_t*)slab_words(m, r), (const uint32_t*)r.other.ptr, bytes / 4, op));
+        VP_TRY(vp_csg(r.ctx, plane_ptr(m->frame, r, r.z0), (const uint32_t*)r.other.ptr, bytes / 4, op));
     }
     m->have_sdf = false;
     return vp_multi_sync(m);

@@ -202,6 +202,28 @@ def slab_range(n: int, rank: int, world: int):
     return rank * nz, (rank + 1) * nz
 
 
+# -- the planner: every plan below is made of these three (csrc/multi.hip states the same three for the one-process driver) --------------
+def steps(n: int):
+    """the steps n/2, n/4, ..., 1 of a JFA on an n^3 grid (integer halving: jfa/sequential.cpp:72)"""
+    ks, k = [], n // 2
+    while k >= 1:
+        ks.append(k)
+        k //= 2
+    return ks
+
+
+def widened(n: int, z0: int, z1: int, ks):
+    """[(k, b0, b1)] in pass order: the planes the pass with step k must produce so that the passes after it need NO exchange -- [z0, z1)
+    widened by the sum of the LATER steps of ks, rounded outwards to the 8-plane tile, clipped to the grid"""
+    reach = [sum(ks[i + 1:]) for i in range(len(ks))]
+    return [(k, max(0, (z0 - g) // 8 * 8), min(n, -(-(z1 + g) // 8) * 8)) for k, g in zip(ks, reach)]
+
+
+def reads(n: int, regions):
+    """[lo, hi): what passes that read ids read on `regions` -- k planes beyond each region, clipped ((n, 0), the empty range, for none)"""
+    return min([n] + [max(0, b0 - k) for k, b0, _ in regions]), max([0] + [min(n, b1 + k) for k, _, b1 in regions])
+
+
 def halo_plan(n: int, world: int, k: int):
     """For step k: list of (src_rank, dst_rank, side, g0, g1) = dst needs global planes [g0, g1) owned
     by src, for its 'minus' or 'plus' buffer.  Deterministic and identical on every rank."""
@@ -220,7 +242,51 @@ def halo_plan(n: int, world: int, k: int):
     return plan
 
 
-class SlabPipeline:
+class _Pipeline:
+    """What the four pipelines share: who the rank is, the stages that need no exchange, and the runner of ghost regions."""
+
+    def __init__(self, backend, frame: Frame, rank: int, world: int, dist=None):
+        self.be, self.dist = backend, dist
+        self.rank, self.world = rank, world
+        self.global_frame = frame
+        self.be.check_frame(frame)
+        self.z0, self.z1 = slab_range(frame.n, rank, world)
+        self.nz = self.z1 - self.z0
+        self.frame = frame.slab(self.z0, self.z1)
+        self.raster = frame                       # what voxelize rasterises into self.words: the whole grid (SlabPipeline: the slab)
+        self.plane_words = frame.n * frame.n // 32                  # bitmask words per plane
+        self.bytes_received = 0
+
+    def voxelize(self, d_xyz, d_tri, algo=ALGO_TILED, out=None):
+        out = self.words if out is None else out
+        self.be.voxelize(self.raster, out, d_xyz, d_tri, algo)
+        return out
+
+    def csg(self, other, op: int):
+        self.be.csg(self.words, other, op)
+        return self.words
+
+    def _plane_passes(self, passes: int):
+        """report(): the plane-passes of this rank against the n per pass of one GPU"""
+        n = self.global_frame.n
+        return {"plane_passes_this_rank": int(self.planes_computed), "plane_passes_one_gpu": n * passes,
+                "plane_pass_ratio": round(n * passes / self.planes_computed, 3)}
+
+    def _run_regions(self, regions, a, b, lo, fill, out, fused=True):
+        """The passes of `regions` [(k, b0, b1)] from window a into window b and back, each on its planes [b0, b1) of the whole-grid
+        self.words; plane 0 of the windows is the global plane lo.  fused: the last region -- the bare slab -- is the last pass with the
+        id -> sdf conversion into `out`.  Returns the windows as (holds the result, the other one)."""
+        G, pw = self.global_frame, self.plane_words
+        for i, (k, b0, b1) in enumerate(regions):
+            if fused and i == len(regions) - 1:
+                self.be.win_last_pass(G.slab(b0, b1), a, b, b0 - lo, self.words[b0 * pw:b1 * pw], fill, out)
+            else:
+                self.be.win_pass(G.slab(b0, b1), k, a, b, b0 - lo)
+                a, b = b, a
+        return a, b
+
+
+class SlabPipeline(_Pipeline):
     """voxelize -> (CSG) -> JFA for the slab of this rank, halo planes exchanged point to point before every pass.
 
     A rank's two id windows hold [slab holding z - k | own slab | slab holding z + k] = 3 nz planes, the own slab in the middle.  The halos
@@ -229,16 +295,8 @@ class SlabPipeline:
     (include/vphip.h, vp_jfa_window_pass) -- one kernel, one buffer layout, and above n = 1024 five bytes per voxel on the wire."""
 
     def __init__(self, backend, frame: Frame, rank: int, world: int, dist):
-        self.be = backend
-        self.dist = dist
-        self.rank, self.world = rank, world
-        self.global_frame = frame
-        self.be.check_frame(frame)
-        self.z0, self.z1 = slab_range(frame.n, rank, world)
-        self.frame = frame.slab(self.z0, self.z1)
-        n = frame.n
-        self.plane_words = n * n // 32            # bitmask words per plane
-        self.nz = self.z1 - self.z0
+        super().__init__(backend, frame, rank, world, dist)
+        self.raster = self.frame                  # every (y, z) column is independent: the slab alone
         self.words = self.be.empty_u32(self.frame.words)
         self.planes = 3 * self.nz if world > 1 else self.nz
         self.at = self.nz if world > 1 else 0
@@ -246,7 +304,6 @@ class SlabPipeline:
         self.sdf = self.be.empty_f32(self.frame.voxels)
         self.below = self.be.empty_u32(self.plane_words) if rank > 0 else None
         self.above = self.be.empty_u32(self.plane_words) if rank < world - 1 else None
-        self.bytes_received = 0
 
     def describe(self):
         return "z-slab x%d, RCCL p2p halo exchange before every pass" % self.world
@@ -254,16 +311,6 @@ class SlabPipeline:
     def report(self):
         return {"pipeline": "halo", "slab_planes": self.nz, "window_planes": self.planes, "bytes_received_total": int(self.bytes_received),
                 "hbm_bytes_this_rank": hbm_bytes(self)}
-
-    # -- stages ---------------------------------------------------------------------------
-    def voxelize(self, d_xyz, d_tri, algo=ALGO_TILED, out=None):
-        out = self.words if out is None else out
-        self.be.voxelize(self.frame, out, d_xyz, d_tri, algo)
-        return out
-
-    def csg(self, other, op: int):
-        self.be.csg(self.words, other, op)
-        return self.words
 
     def _exchange(self, ops):
         if ops:
@@ -309,8 +356,7 @@ class SlabPipeline:
             self._exchange_mask_planes()
         a, b = self.ids
         self.be.win_init(self.frame, self.words, self.below, self.above, a, self.at)
-        k = self.global_frame.n // 2
-        while k >= 1:                                             # jfa/sequential.cpp:72
+        for k in steps(self.global_frame.n):
             if self.world > 1:
                 self._exchange_ids(k, a)
             if k == 1:                                            # last pass + id -> sdf conversion fused
@@ -318,7 +364,6 @@ class SlabPipeline:
                 return out
             self.be.win_pass(self.frame, k, a, b, self.at, self._stride(k))
             a, b = b, a
-            k //= 2
         return out
 
 
@@ -339,21 +384,10 @@ def ghost_regions(n: int, rank: int, world: int):
     that it is never unwritten memory).  Nesting the regions instead (each containing the next one widened
     by its step) would cost up to 16 more planes per side and pass for values nobody reads."""
     z0, z1 = slab_range(n, rank, world)
-    ks = []
-    k = n // 2
-    while k >= 1:
-        ks.append(k)
-        k //= 2
-    out = []
-    for i, k in enumerate(ks):
-        g = sum(ks[i + 1:])
-        b0 = max(0, (z0 - g) // 8 * 8)
-        b1 = min(n, -((-(z1 + g)) // 8) * 8)
-        out.append((k, b0, b1))
-    return out
+    return widened(n, z0, z1, steps(n))
 
 
-class GhostSlabPipeline:
+class GhostSlabPipeline(_Pipeline):
     """Z-slab strong scaling WITHOUT halo exchange.
 
     Measured on MI355X one JFA pass costs ~1.6 us per 512^2 plane, while moving that plane (1 MiB) to a
@@ -368,12 +402,7 @@ class GhostSlabPipeline:
     """
 
     def __init__(self, backend, frame: Frame, rank: int, world: int):
-        self.be = backend
-        self.rank, self.world = rank, world
-        self.global_frame = frame
-        self.be.check_frame(frame)
-        self.z0, self.z1 = slab_range(frame.n, rank, world)
-        self.frame = frame.slab(self.z0, self.z1)
+        super().__init__(backend, frame, rank, world)
         self.regions = ghost_regions(frame.n, rank, world)
         self.words = self.be.empty_u32(frame.words)                 # whole grid
         self.ids = [self.be.window(frame, frame.n) for _ in range(2)]
@@ -385,21 +414,10 @@ class GhostSlabPipeline:
         return "z-slab x%d, ghost planes recomputed, no data-path exchange" % self.world
 
     def report(self):
-        n, passes = self.global_frame.n, len(self.regions)
-        return {"pipeline": "ghost", "slab_planes": self.z1 - self.z0, "regions": [[k, b0, b1] for k, b0, b1 in self.regions],
-                "plane_passes_this_rank": int(self.planes_computed), "plane_passes_one_gpu": n * passes,
-                "plane_pass_ratio": round(n * passes / self.planes_computed, 3), "bytes_exchanged": 0, "bytes_received_total": 0,
+        return {"pipeline": "ghost", "slab_planes": self.nz, "regions": [[k, b0, b1] for k, b0, b1 in self.regions],
+                **self._plane_passes(len(self.regions)), "bytes_exchanged": 0, "bytes_received_total": 0,
                 "id_window_bytes": int(self.ids[0].t.numel() * self.ids[0].t.element_size()),
                 "hbm_bytes_this_rank": hbm_bytes(self)}
-
-    def voxelize(self, d_xyz, d_tri, algo=ALGO_TILED, out=None):
-        out = self.words if out is None else out
-        self.be.voxelize(self.global_frame, out, d_xyz, d_tri, algo)
-        return out
-
-    def csg(self, other, op: int):
-        self.be.csg(self.words, other, op)
-        return self.words
 
     def jfa(self, fill=-math.inf, out=None):
         """border mask, passes n/2 + n/4 over the whole grid in one launch, every later pass on its region"""
@@ -408,17 +426,7 @@ class GhostSlabPipeline:
         G = self.global_frame
         self.be.surface(G, self.words, self.border)
         self.be.win_first_two(G, self.border, a)
-        pw = G.n * G.n // 32
-        last = len(self.regions) - 1
-        for i, (k, b0, b1) in enumerate(self.regions):
-            if i < 2:
-                continue
-            region = G.slab(b0, b1)
-            if i == last:
-                self.be.win_last_pass(region, a, b, b0, self.words[b0 * pw:b1 * pw], fill, out)
-                return out
-            self.be.win_pass(region, k, a, b, b0)
-            a, b = b, a
+        self._run_regions(self.regions[2:], a, b, 0, fill, out)
         return out
 
 
@@ -431,20 +439,21 @@ def hybrid_plan(n: int, rank: int, world: int):
     adjacent rank.  world == 1: every pass is 'wide' with the whole grid as its region."""
     z0, z1 = slab_range(n, rank, world)
     H = (z1 - z0) // 2 if world > 1 else 0
-    ks = []
-    k = n // 2
-    while k >= 1:
-        ks.append(k)
-        k //= 2
-    wide_ks = [k for k in ks if k > H]
-    wide = []
-    for i, k in enumerate(wide_ks):
-        g = sum(wide_ks[i + 1:])
-        wide.append((k, max(0, (z0 - g) // 8 * 8), min(n, -((-(z1 + g)) // 8) * 8)))
-    return wide, [k for k in ks if k <= H]
+    return widened(n, z0, z1, [k for k in steps(n) if k > H]), [k for k in steps(n) if k <= H]
 
 
-class HybridSlabPipeline:
+def hybrid_window(n: int, rank: int, world: int, mask_start: bool):
+    """[lo, hi): the global planes the two id windows of the hybrid pipeline hold (= vp_multi_window after VP_MULTI_HYBRID) -- the slab
+    with room for the halos of the narrow passes, every wide region, and what a wide pass that READS ids reads beyond its region
+    (mask_start: the first pass starts from the border mask and reads none)"""
+    z0, z1 = slab_range(n, rank, world)
+    H = (z1 - z0) // 2 if world > 1 else 0
+    wide, _ = hybrid_plan(n, rank, world)
+    spans = [(max(0, z0 - H), min(n, z1 + H)), reads(n, wide[1:] if mask_start else wide)] + [(b0, b1) for _, b0, b1 in wide]
+    return min(lo for lo, _ in spans), max(hi for _, hi in spans)
+
+
+class HybridSlabPipeline(_Pipeline):
     """Z-slabs, the two ways of feeding a pass mixed by what each costs.
 
     A pass with step k needs the planes z +- k.  For the WIDE passes (k > nz/2: whole slabs of distant ranks) the planes are
@@ -459,53 +468,24 @@ class HybridSlabPipeline:
     """
 
     def __init__(self, backend, frame: Frame, rank: int, world: int, dist):
-        self.be, self.dist = backend, dist
-        self.rank, self.world = rank, world
-        self.global_frame = frame
-        self.be.check_frame(frame)
-        self.z0, self.z1 = slab_range(frame.n, rank, world)
-        self.nz = self.z1 - self.z0
-        self.frame = frame.slab(self.z0, self.z1)
+        super().__init__(backend, frame, rank, world, dist)
         self.wide, self.narrow = hybrid_plan(frame.n, rank, world)
-        self.plane_words = frame.n * frame.n // 32
         self.words = self.be.empty_u32(frame.words)                  # whole grid: every rank rasterises it (0.06 ms at n = 512)
         self.sdf = self.be.empty_f32(self.frame.voxels)
         self.border = None
         self.mask_start = bool(self.wide) and len(self.wide) + len(self.narrow) > 1 and self.be.can_start_from_mask(frame)
-        self.window = list(self._window_planes(self.mask_start))     # global planes [lo, hi) the two id windows hold
+        self.window = list(hybrid_window(frame.n, rank, world, self.mask_start))     # global planes [lo, hi) the two id windows hold
         self.ids = [self.be.window(frame, self.window[1] - self.window[0]) for _ in range(2)]
-        self.bytes_received = 0
         self.planes_computed = sum(b1 - b0 for _, b0, b1 in self.wide) + self.nz * len(self.narrow)
 
     def describe(self):
         return "z-slab x%d, hybrid: ghost planes for k > nz/2, p2p halos under the interior planes for k <= nz/2" % self.world
 
     def report(self):
-        n, passes = self.global_frame.n, len(self.wide) + len(self.narrow)
         return {"pipeline": "hybrid", "slab_planes": self.nz, "wide_regions": [[k, b0, b1] for k, b0, b1 in self.wide],
-                "narrow_steps": list(self.narrow), "plane_passes_this_rank": int(self.planes_computed),
-                "plane_passes_one_gpu": n * passes, "plane_pass_ratio": round(n * passes / self.planes_computed, 3),
+                "narrow_steps": list(self.narrow), **self._plane_passes(len(self.wide) + len(self.narrow)),
                 "bytes_received_total": int(self.bytes_received), "id_buffer_planes": self.window,
                 "hbm_bytes_this_rank": hbm_bytes(self)}
-
-    def voxelize(self, d_xyz, d_tri, algo=ALGO_TILED, out=None):
-        out = self.words if out is None else out
-        self.be.voxelize(self.global_frame, out, d_xyz, d_tri, algo)
-        return out
-
-    def csg(self, other, op: int):
-        self.be.csg(self.words, other, op)
-        return self.words
-
-    # -- the window: planes [lo, hi) of the id volume ------------------------------------------
-    def _window_planes(self, mask_start: bool):
-        n, H = self.global_frame.n, (self.nz // 2 if self.world > 1 else 0)
-        lo, hi = max(0, self.z0 - H), min(n, self.z1 + H)            # room for the halos of the narrow passes
-        for i, (k, b0, b1) in enumerate(self.wide):
-            lo, hi = min(lo, b0), max(hi, b1)
-            if i > 0 or not mask_start:                               # every pass that reads ids reads k planes beyond its region
-                lo, hi = min(lo, max(0, b0 - k)), max(hi, min(n, b1 + k))
-        return lo, hi
 
     def _start_exchange(self, k: int, w):
         """Halo of k planes for the pass with step k on the state in `w`: my bottom / top k planes go down / up, theirs land
@@ -540,7 +520,6 @@ class HybridSlabPipeline:
         lo, hi = self.window
         a, b = self.ids
         slab_words = self.words[z0 * pw:z1 * pw]
-        npass = len(self.wide) + len(self.narrow)
         # ---- wide passes: ghost planes
         start = 0
         if self.mask_start:
@@ -555,13 +534,7 @@ class HybridSlabPipeline:
             below = self.words[(lo - 1) * pw:lo * pw] if lo > 0 else None
             above = self.words[hi * pw:(hi + 1) * pw] if hi < n else None
             self.be.win_init(G.slab(lo, hi), self.words[lo * pw:hi * pw], below, above, a, 0)
-        for i in range(start, len(self.wide)):
-            k, b0, b1 = self.wide[i]
-            if i == npass - 1:                                        # one rank: the last pass is a wide one
-                self.be.win_last_pass(G.slab(b0, b1), a, b, b0 - lo, slab_words, fill, out)
-                return out
-            self.be.win_pass(G.slab(b0, b1), k, a, b, b0 - lo)
-            a, b = b, a
+        a, b = self._run_regions(self.wide[start:], a, b, lo, fill, out, fused=not self.narrow)       # one rank: the last pass is a wide one
         # ---- narrow passes: halos from the adjacent ranks, the next pass's halo sent under this pass's interior planes
         pend = None
         at = z0 - lo
@@ -614,17 +587,16 @@ def transpose_plan(n: int, rank: int, world: int, min_n: int = 96):
     c = cyclic_passes(n, world, min_n)
     if c == 0:
         return None
-    regs = ghost_regions(n, rank, world)
-    ks = [k for k, _, _ in regs]
     z0, z1 = slab_range(n, rank, world)
+    ks = steps(n)
+    regs = widened(n, z0, z1, ks[c:])
     g = sum(ks[c:])
     t0, t1 = max(0, (z0 - g) // world * world), min(n, -(-(z1 + g) // world) * world)
-    lo = min([t0] + [max(0, b0 - k) for k, b0, _ in regs[c:]])
-    hi = max([t1] + [min(n, b1 + k) for k, _, b1 in regs[c:]])
-    return {"cyclic": ks[:c], "regions": regs[c:], "recv": (t0, t1), "window": (lo, hi)}
+    lo, hi = reads(n, regs)
+    return {"cyclic": ks[:c], "regions": regs, "recv": (t0, t1), "window": (min(t0, lo), max(t1, hi))}
 
 
-class TransposeSlabPipeline:
+class TransposeSlabPipeline(_Pipeline):
     """Z-slab strong scaling with ONE exchange.
 
     The reference's pass with step k reads the planes z - k, z, z + k of a voxel's plane z and nothing else (jfa/sequential.cpp:72,
@@ -645,23 +617,17 @@ class TransposeSlabPipeline:
         buffer, no staging buffer, no weave -- at the price of (world - 1) x count messages per rank instead of one collective)"""
         if exchange not in ("a2a", "p2p"):
             raise ValueError("exchange must be 'a2a' or 'p2p'")
-        self.be, self.dist, self.exchange_kind = backend, dist, exchange
-        self.rank, self.world = rank, world
-        self.global_frame = frame
-        self.be.check_frame(frame)
-        self.z0, self.z1 = slab_range(frame.n, rank, world)
-        self.frame = frame.slab(self.z0, self.z1)
+        super().__init__(backend, frame, rank, world, dist)
+        self.exchange_kind = exchange
         min_n = getattr(backend, "tile_min_n", 96)
         self.plan = transpose_plan(frame.n, rank, world, min_n)
         self.fallback = None
-        self.bytes_received = 0
         if self.plan is None:                                      # nothing to deal cyclically: ghost planes
             self.fallback = GhostSlabPipeline(backend, frame, rank, world)
             self.words, self.sdf = self.fallback.words, self.fallback.sdf
             return
         assert self.be.cyclic_passes(frame, world) == len(self.plan["cyclic"]), "the library counts the cyclic passes differently"
         n = frame.n
-        self.nzl = n // world                                       # planes of the cyclic share
         self.words = self.be.empty_u32(frame.words)                 # whole grid: every rank rasterises it
         self.border = self.be.empty_u32(frame.words)
         self.sdf = self.be.empty_f32(self.frame.voxels)
@@ -675,10 +641,10 @@ class TransposeSlabPipeline:
             self.send_ranges.append((p["recv"][0] // world, p["recv"][1] // world))
         # id windows, allocated at first use and kept (a steady-state step allocates nothing): the two of the cyclic phase, the packed
         # send buffer, the staging buffer the all-to-all fills, the two of the slab phase
-        self._planes = {"cyc0": self.nzl, "cyc1": self.nzl, "send": sum(b - a for a, b in self.send_ranges), "staging": self.count * world,
+        self._planes = {"cyc0": self.nz, "cyc1": self.nz, "send": sum(b - a for a, b in self.send_ranges), "staging": self.count * world,
                         "ids0": hi - lo, "ids1": hi - lo}
         self.win = {}
-        self.planes_computed = self.nzl * len(self.plan["cyclic"]) + sum(b1 - b0 for _, b0, b1 in self.plan["regions"])
+        self.planes_computed = self.nz * len(self.plan["cyclic"]) + sum(b1 - b0 for _, b0, b1 in self.plan["regions"])
 
     def _w(self, name):
         if name not in self.win:
@@ -700,24 +666,12 @@ class TransposeSlabPipeline:
     def report(self):
         if self.fallback is not None:
             return dict(self.fallback.report(), pipeline="transpose->ghost")
-        n, passes = self.global_frame.n, len(self.plan["cyclic"]) + len(self.plan["regions"])
-        return {"pipeline": "transpose", "exchange": self.exchange_kind, "slab_planes": self.z1 - self.z0, "cyclic_steps": list(self.plan["cyclic"]),
+        return {"pipeline": "transpose", "exchange": self.exchange_kind, "slab_planes": self.nz, "cyclic_steps": list(self.plan["cyclic"]),
                 "slab_regions": [[k, b0, b1] for k, b0, b1 in self.plan["regions"]], "recv_planes": list(self.plan["recv"]),
-                "window_planes": list(self.plan["window"]), "plane_passes_this_rank": int(self.planes_computed),
-                "plane_passes_one_gpu": n * passes, "plane_pass_ratio": round(n * passes / self.planes_computed, 3),
+                "window_planes": list(self.plan["window"]), **self._plane_passes(len(self.plan["cyclic"]) + len(self.plan["regions"])),
                 "bytes_received_total": int(self.bytes_received), "hbm_bytes_this_rank": hbm_bytes(self)}
 
-    def voxelize(self, d_xyz, d_tri, algo=ALGO_TILED, out=None):
-        if self.fallback is not None:
-            return self.fallback.voxelize(d_xyz, d_tri, algo, out)
-        out = self.words if out is None else out
-        self.be.voxelize(self.global_frame, out, d_xyz, d_tri, algo)
-        return out
-
-    def csg(self, other, op: int):
-        self.be.csg(self.words, other, op)
-        return self.words
-
+    # (voxelize and csg: the fallback shares self.words and rasterises the whole grid too, so the inherited ones serve both)
     # -- the four stages of a JFA (jfa() below runs them in order; tests drive them one by one) -----------------------------
     def phase_a(self):
         """cyclic planes, no exchange: border mask of the whole grid, the fused start for the rank's planes, every further step that is a
@@ -787,20 +741,11 @@ class TransposeSlabPipeline:
         """the weave into consecutive planes (exchange "a2a"), then the remaining steps on the widened slab (as the last regions of the ghost
         pipeline)"""
         out = self.sdf if out is None else out
-        G, be = self.global_frame, self.be
-        pw = G.n * G.n // 32
         lo, _ = self.plan["window"]
         a, b = self._w("ids0"), self._w("ids1")
         if weave:
-            be.win_interleave(G, self._w("staging"), a, self.plan["recv"][0] - lo, self.world, self.count)
-        regs = self.plan["regions"]
-        for i, (k, b0, b1) in enumerate(regs):
-            region = G.slab(b0, b1)
-            if i == len(regs) - 1:
-                be.win_last_pass(region, a, b, b0 - lo, self.words[b0 * pw:b1 * pw], fill, out)
-                return out
-            be.win_pass(region, k, a, b, b0 - lo)
-            a, b = b, a
+            self.be.win_interleave(self.global_frame, self._w("staging"), a, self.plan["recv"][0] - lo, self.world, self.count)
+        self._run_regions(self.plan["regions"], a, b, lo, fill, out)
         return out
 
     def jfa(self, fill=-math.inf, out=None):

@@ -315,3 +315,43 @@ def test_multi_transpose_equals_single(engine, world, n, name):
     finally:
         m.close()
         gc.collect(); torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("n,world", [(96, 2), (96, 4), (128, 4), (160, 2), (160, 4)])
+def test_multi_smallest_sides_of_every_branch_equal_single(engine, n, world):
+    """All four modes at the smallest sides at which each branch of the driver can go wrong: n = 96 and 160 are no multiples of 128, so the
+    hybrid mode starts from vp_jfa_window_init on the window instead of the border mask (n = 128: the smallest mask start); n = 160 has the
+    odd step 5 after 80, 40, 20, 10: the cyclic phase ends early and the slab phase runs with a wider margin.  Grid and sdf bit-identical
+    to the single-context result; the windows and the bytes moved are the ones slab.py plans (the two hosts share no code, only the rules)."""
+    from cuda_mesh_voxelization_amd.slab import halo_plan, hybrid_window, steps, transpose_plan
+    xyz, tri = M.import_mesh(M.asset("bunny.obj"))
+    origin, vs = M.frame([xyz], n)
+    fr = Frame.make(n, vs, origin)
+    ref_w, ref_s = _single(engine, fr, xyz, tri)
+    gather = world * (world - 1) * (fr.words // world) * 4
+    m = capi.Multi([0] * world)
+    try:
+        m.set_mesh(xyz, tri)
+        m.voxelize(fr)
+        assert np.array_equal(m.get_grid().view(np.uint32), ref_w.view(np.uint32))
+        for mode in (MULTI_HALO, MULTI_GHOST, MULTI_HYBRID, MULTI_TRANSPOSE):
+            m.jfa(mode=mode)
+            assert np.array_equal(m.get_sdf().view(np.uint32), ref_s.view(np.uint32)), mode
+            if mode == MULTI_HYBRID:
+                mask_start = engine.ctx.jfa_can_start_from_mask(fr)
+                assert mask_start == (n == 128)
+                for r in range(world):
+                    assert m.window(r)[:2] == hybrid_window(n, r, world, mask_start), r
+            elif mode == MULTI_TRANSPOSE:
+                plans = [transpose_plan(n, r, world) for r in range(world)]
+                assert m.bytes_moved == gather + sum((world - 1) * ((p["recv"][1] - p["recv"][0]) // world) * n * n * 4 for p in plans)
+                for r, p in enumerate(plans):
+                    lo, hi, nbytes = m.window(r)
+                    assert (lo, hi) == p["window"]
+                    assert nbytes == (2 * (hi - lo) + 2 * (n // world) + (p["recv"][1] - p["recv"][0])) * n * n * 4
+            elif mode == MULTI_HALO:
+                # two bitmask planes per interior boundary, then before every pass the id planes of every halo_plan entry that changes rank
+                ids = sum(g1 - g0 for k in steps(n) for s, t, _, g0, g1 in halo_plan(n, world, k) if s != t)
+                assert m.bytes_moved == 2 * (world - 1) * n * n // 8 + ids * n * n * 4
+    finally:
+        m.close()

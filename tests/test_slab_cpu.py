@@ -333,3 +333,30 @@ def test_transpose_plan_feeds_itself():
     # (slabs of a multiple of 8 planes make n/4 a multiple of the rank count: where the split is legal at all there are two cyclic passes)
     assert all(transpose_plan(*a) is None for a in ((64, 0, 2), (512, 0, 1), (96, 0, 8), (384, 0, 3)))
     assert cyclic_passes(96, 4) == 3 and cyclic_passes(128, 8) == 4 and cyclic_passes(1024, 8) == 7 and cyclic_passes(160, 4) == 3
+
+
+def test_plans_equal_the_recorded_ones():
+    """The property tests above prove that the plans are VALID; this one that they are the SAME plans: tests/golden/slab_plans.json holds what
+    slab.py planned before the planner was shared (ghost_regions, hybrid_plan, the hybrid window with and without the mask start,
+    transpose_plan, cyclic_passes and halo_plan of every step) for every split of n in 96, 128, 160, 256, 1152 over 1, 2, 3, 4, 8 ranks that
+    slab_range accepts.  A region one tile wider than needed would pass the property tests and cost time."""
+    import importlib.util
+    import json
+    sys.path.insert(0, ROOT)
+    from cuda_mesh_voxelization_amd import slab
+    spec = importlib.util.spec_from_file_location("make_slab_plans", os.path.join(ROOT, "tests", "golden", "make_slab_plans.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    with open(os.path.join(ROOT, "tests", "golden", "slab_plans.json")) as f:
+        want = json.load(f)
+    got = G.record(slab)
+    assert sorted(got) == sorted(want) and len(got) == 20 and sum(len(v["ranks"]) for v in got.values()) == 65
+    for split in want:
+        n, world = [int(v) for v in split.split("/")]
+        assert got[split]["halo"] == want[split]["halo"], split
+        for r in range(world):
+            for what in want[split]["ranks"][r]:
+                assert got[split]["ranks"][r][what] == want[split]["ranks"][r][what], (split, r, what)
+            lo, hi = slab.hybrid_window(n, r, world, False)                      # the planes a rank holds contain its slab
+            assert 0 <= lo <= r * (n // world) and (r + 1) * (n // world) <= hi <= n
+    assert slab.steps(160) == [80, 40, 20, 10, 5, 2, 1] and slab.steps(1) == []
