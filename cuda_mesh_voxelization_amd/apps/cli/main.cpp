@@ -42,6 +42,9 @@
 //                            vp_edt_morph): any R = 0 .. 65535, the same bits as dilate:R / erode:R where those are served
 //         --exact-sdf        (extension, with -s) the field is the exact squared distance to the border voxels (include/vphip.h,
 //                            vp_edt_sdf) instead of the Jump Flooding approximation: same sign, same zeros, never larger.  One device only
+//         --mesh-sdf BAND    (extension, with -s) the field is the narrow-band squared distance to the TRIANGLES of the mesh (include/vphip.h,
+//                            vp_mesh_distance), BAND = 1 .. 32 voxels wide and min(B2, .) beyond, signed by the solid grid the run computed;
+//                            written and exported in place of the Jump Flooding field.  One mesh, no CSG, one device
 //         --surface-nets I   (extension, with -e) the grid meshes -- the files --surface-only affects -- hold the surface-nets mesh of the grid
 //                            (include/vphip.h, vp_surfnets): one vertex per boundary cell, two triangles per exposed voxel face, closed,
 //                            after I = 0 .. 64 relaxation steps; a smooth mesh back from a repaired grid instead of cube faces.  Not with
@@ -94,6 +97,7 @@ struct Options {
     bool conservative = false;
     bool fill = false;
     bool exactSdf = false;
+    int meshSdf = 0;                                        // --mesh-sdf BAND: band in voxels, 0 = not asked for
     bool help = false;
     // op = VOX::MorphOp, 4 / 5: offset / inset (dilate / erode through the distance transform), or -1: the interior fill, -2: largest
     // component, -3: minsize (value = V); conn = 6 / 26 for the last two
@@ -198,6 +202,9 @@ const char* kUsage =
     "                        R = 0..65535, e.g. --conservative --morph offset:40,fill,inset:40 for holes up to about 80 voxels wide\n"
     "      --exact-sdf       With -s: the exact squared distance to the border voxels instead of the Jump Flooding approximation\n"
     "                        (same sign, same zeros, never larger).  One device only: not with -g > 1 (extension)\n"
+    "      --mesh-sdf BAND   With -s: the narrow-band squared distance to the triangles of the mesh itself, BAND = 1..32 voxels wide,\n"
+    "                        signed by the solid grid of the run, instead of the Jump Flooding field between voxels.  One mesh,\n"
+    "                        no CSG, one device (extension)\n"
     "  -h, --help            Print usage\n";
 
 // Minimal getopt-style parser: -x V, -xV, --long V, --long=V, boolean switches, positionals.
@@ -205,7 +212,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -247,6 +254,12 @@ Options Parse(int argc, char** argv)
             case 'd': o.dump = value; break;
             case 'g': o.gpus = static_cast<unsigned>(std::stoul(value)); break;
             case 'M': o.multi = value; break;
+            case 'D': {
+                const bool digits = !value.empty() && value.size() <= 2 && value.find_first_not_of("0123456789") == std::string::npos;
+                cpuAssert(digits && std::stoi(value) >= 1 && std::stoi(value) <= 32, "--mesh-sdf: '" + value + "' is not a band of 1..32 voxels\n");
+                o.meshSdf = std::stoi(value);
+                break;
+            }
             case 'N': {
                 const bool digits = !value.empty() && value.size() <= 2 && value.find_first_not_of("0123456789") == std::string::npos;
                 cpuAssert(digits && std::stoi(value) <= 64, "--surface-nets: '" + value + "' is not a number of relaxation steps in 0..64\n");
@@ -347,6 +360,11 @@ int main(int argc, char** argv)
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
     cpuAssert(!(opt.exactSdf && !opt.sdf), "--exact-sdf needs -s: it chooses how the distance field is computed\n");
     cpuAssert(!(opt.exactSdf && opt.gpus > 1), "--exact-sdf runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.meshSdf && !opt.sdf), "--mesh-sdf needs -s: it chooses how the distance field is computed\n");
+    cpuAssert(!(opt.meshSdf && opt.exactSdf), "--mesh-sdf and --exact-sdf exclude each other: one distance field per run\n");
+    cpuAssert(!(opt.meshSdf && opt.gpus > 1), "--mesh-sdf runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.meshSdf && (opt.filenames.size() != 1 || OPERATION != CSG::Op::VOID || BENCHMARK)),
+              "--mesh-sdf needs a single mesh without CSG (and no -m): the field of a CSG result is not the field of any one mesh\n");
     cpuAssert(!(opt.surfaceNets >= 0 && opt.surfaceOnly), "--surface-nets and --surface-only exclude each other: one mesh per grid file\n");
     cpuAssert(!(opt.surfaceNets >= 0 && opt.gpus > 1), "--surface-nets runs on one device: -g must be 1\n");
     cpuAssert(opt.multi == "ghost" || opt.multi == "halo" || opt.multi == "hybrid" || opt.multi == "transpose", "--multi must be ghost, halo, hybrid or transpose");
@@ -448,7 +466,15 @@ int main(int argc, char** argv)
 
         if (opt.sdf) {
             sdf = HostGrid<float>(N, -INFINITY);                                                        // main.cpp:200
-            if (opt.exactSdf) {
+            if (opt.meshSdf) {
+                const uint32_t band = static_cast<uint32_t>(opt.meshSdf);
+                switch (TYPE) {
+                    case Types::SEQUENTIAL: VOX::MeshDistance<Types::SEQUENTIAL>(grids[0], meshes[0], band, sdf); break;
+                    case Types::OPENMP:     VOX::MeshDistance<Types::OPENMP>(grids[0], meshes[0], band, sdf); break;
+                    case Types::NAIVE:      VOX::MeshDistance<Types::NAIVE>(grids[0], meshes[0], band, sdf); break;
+                    case Types::TILED:      VOX::MeshDistance<Types::TILED>(grids[0], meshes[0], band, sdf); break;
+                }
+            } else if (opt.exactSdf) {
                 switch (TYPE) {
                     case Types::SEQUENTIAL: JFA::ComputeExact<Types::SEQUENTIAL>(grids[0], sdf); break;
                     case Types::OPENMP:     JFA::ComputeExact<Types::OPENMP>(grids[0], sdf); break;

@@ -1,7 +1,7 @@
 """Build recipes for the native parts (in-tree, so the built files travel with the repo snapshot).
 
   libvphip.so   HIP kernels + C ABI (include/vphip.h), hipcc --offload-arch=gfx950
-  libvphip_hooks.so   the same with the test hooks of vox.hip / multi.hip / cvox.hip compiled in (-DVP_TEST_HOOKS); only tests load it
+  libvphip_hooks.so   the same with the test hooks of vox.hip / multi.hip / cvox.hip / meshdist.hip compiled in (-DVP_TEST_HOOKS); only tests load it
   vpcli         C++23 CLI mirroring the reference's apps/cli (links libvphip.so)
 
 hipcc cross-compiles gfx950 code objects without a GPU present.
@@ -18,9 +18,9 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvphip.so")
 CLI = os.path.join(PKG, "vpcli")
 
-HIP_SOURCES = ["capi.hip", "vox.hip", "csg.hip", "jfa_seed.hip", "jfa_first_two.hip", "jfa_dense.hip", "extract.hip", "multi.hip", "cvox.hip", "fill.hip", "morph.hip", "components.hip", "surfnets.hip", "edt.hip"]
+HIP_SOURCES = ["capi.hip", "vox.hip", "csg.hip", "jfa_seed.hip", "jfa_first_two.hip", "jfa_dense.hip", "extract.hip", "multi.hip", "cvox.hip", "fill.hip", "morph.hip", "components.hip", "surfnets.hip", "edt.hip", "meshdist.hip"]
 DENSE_PARTS = 10                 # jfa_dense.hip is compiled once per id format and pass kind, side by side (-DVP_DENSE_PART=1..10, see the end of the file)
-HOOK_SOURCES = ["vox.hip", "multi.hip", "cvox.hip"]     # the sources that read test hooks from the environment under -DVP_TEST_HOOKS (libvphip_hooks.so)
+HOOK_SOURCES = ["vox.hip", "multi.hip", "cvox.hip", "meshdist.hip"]     # the sources that read test hooks from the environment under -DVP_TEST_HOOKS (libvphip_hooks.so)
 HOOKS_LIB = os.path.join(PKG, "libvphip_hooks.so")
 # -ffp-contract=off is part of the parity contract: an FMA changes the bitmask / sdf bits.
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -51,7 +51,7 @@ def _jobs(n: int) -> int:
 
 
 def build_lib(force: bool = False, verbose: bool = False, hooks: bool = False) -> str:
-    """libvphip.so; hooks=True: also libvphip_hooks.so -- the same objects except vox.hip / multi.hip / cvox.hip compiled with -DVP_TEST_HOOKS, the
+    """libvphip.so; hooks=True: also libvphip_hooks.so -- the same objects except vox.hip / multi.hip / cvox.hip / meshdist.hip compiled with -DVP_TEST_HOOKS, the
     build the tests that force rare paths load (the default library reads no environment variable on any call path)."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     deps = srcs + [os.path.join(CSRC, "vp_internal.h"), os.path.join(CSRC, "jfa_common.h"), os.path.join(CSRC, "wg_scan.h"), os.path.join(ROOT, "include", "vphip.h")]

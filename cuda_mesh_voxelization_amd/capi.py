@@ -16,6 +16,7 @@ OP_VOID, OP_UNION, OP_INTERSECTION, OP_DIFFERENCE = 0, 1, 2, 3
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3     # vp_morph: ball morphology
 EDT_SEEDS_SET, EDT_SEEDS_UNSET, EDT_SEEDS_BORDER = 0, 1, 2              # vp_edt: which voxels the distances are measured to
 EDT_NONE = 0xFFFFFFFF                                               # vp_edt: "the grid has no seed"
+MESH_NONE = 0xFFFFFFFF                                              # vp_mesh_distance: "no triangle within the band"
 CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
 COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
@@ -39,6 +40,9 @@ ALL_PROF_KEYS = PROF_KEYS + SURFNETS_KERNELS
 # (VP_K_END of them) in its numbering -- what prof() and prof_select() look names up in
 EDT_KERNELS = ["edt_x", "edt_y", "edt_z", "edt_y_naive", "edt_z_naive", "edt_sdf", "edt_thresh"]
 EVERY_PROF_KEY = ALL_PROF_KEYS + EDT_KERNELS
+# the keys of vp_mesh_distance are a fourth enum behind the third (= VP_K_END); HEADER_PROF_KEYS is every key of the header, VP_K_ALL of them
+MESHDIST_KERNELS = ["md_setup", "md_scan", "md_count", "md_write", "md_brick", "md_fill", "md_prefill", "md_naive", "md_split"]
+HEADER_PROF_KEYS = EVERY_PROF_KEY + MESHDIST_KERNELS
 JFA_PASS_KEYS = ("jfa_pass", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last")
 
 # every symbol include/vphip.h declares (tests check the library exports all of them)
@@ -61,6 +65,7 @@ SYMBOLS = [
     "vp_components_label", "vp_components_sizes", "vp_components_filter", "vp_components_label_host", "vp_components_filter_host",
     "vp_surfnets_count", "vp_surfnets", "vp_surfnets_host",
     "vp_edt", "vp_edt_sdf", "vp_edt_morph", "vp_edt_host", "vp_edt_sdf_host", "vp_edt_morph_host",
+    "vp_mesh_distance", "vp_mesh_distance_host", "vp_mesh_distance_stats",
 ]
 
 
@@ -180,6 +185,9 @@ def lib():
         "vp_edt_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
         "vp_edt_sdf_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_float, _vp, ctypes.c_int]),
         "vp_edt_morph_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
+        "vp_mesh_distance": (ctypes.c_int, [_vp, fp, _vp, _sz, _vp, _sz, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_int]),
+        "vp_mesh_distance_host": (ctypes.c_int, [_vp, fp, _vp, _sz, _vp, _sz, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_int]),
+        "vp_mesh_distance_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -323,6 +331,20 @@ class Context:
     def edt_morph(self, frame: Frame, d_words: int, d_out: int, op: int, radius: int, algo: int = ALGO_TILED):
         """morph() through the distance transform: any integer radius 0 .. 65535.  Enqueues only."""
         check(lib().vp_edt_morph(self._h, ctypes.byref(frame), _vp(d_words), _vp(d_out), op, radius, algo))
+
+    def mesh_distance(self, frame: Frame, d_xyz: int, nverts: int, d_tri: int, ntris: int, band: int, d_dist2: int, d_nearest: int = 0,
+                      d_sign_words: int = 0, algo: int = ALGO_TILED):
+        """Narrow-band squared distance from every voxel centre to the triangles of the mesh, band = 1 .. 32 voxels: d_dist2 takes one
+        float32 per voxel (min(B2, .), signed by d_sign_words if given: + on set voxels, - on unset ones), d_nearest (optional) the index
+        of the nearest face or MESH_NONE.  ALGO_TILED reads the list lengths back once (blocking); ALGO_NAIVE enqueues only."""
+        check(lib().vp_mesh_distance(self._h, ctypes.byref(frame), _vp(d_xyz), nverts, _vp(d_tri), ntris, _vp(d_sign_words) if d_sign_words else None,
+                                     band, _vp(d_dist2), _vp(d_nearest) if d_nearest else None, algo))
+
+    def mesh_distance_list_entries(self) -> int:
+        """(triangle, brick) pairs the last ALGO_TILED mesh_distance of this context listed."""
+        n = ctypes.c_uint64()
+        check(lib().vp_mesh_distance_stats(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def components_label(self, frame: Frame, d_words: int, d_labels: int, conn: int = CONN_26, algo: int = ALGO_TILED) -> int:
         """Connected components of the set voxels (CONN_6 / CONN_26): d_labels takes one uint32 per voxel, 0 = background, components
@@ -502,6 +524,16 @@ class Context:
     def edt_morph_host(self, frame: Frame, h_words, h_out, op: int, radius: int, algo: int = ALGO_TILED):
         check(lib().vp_edt_morph_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_out.ctypes.data_as(_vp), op, radius, algo))
 
+    def mesh_distance_host(self, frame: Frame, h_xyz, h_tri, band: int, h_sign_words=None, want_nearest: bool = True, algo: int = ALGO_TILED):
+        """numpy in, numpy out: (dist2 float32[n^3], nearest uint32[n^3] or None)."""
+        np = __import__("numpy")
+        dist = np.empty(frame.voxels, np.float32)
+        near = np.empty(frame.voxels, np.uint32) if want_nearest else None
+        check(lib().vp_mesh_distance_host(self._h, ctypes.byref(frame), h_xyz.ctypes.data_as(_vp), h_xyz.shape[0], h_tri.ctypes.data_as(_vp),
+                                          h_tri.shape[0], h_sign_words.ctypes.data_as(_vp) if h_sign_words is not None else None, band,
+                                          dist.ctypes.data_as(_vp), near.ctypes.data_as(_vp) if want_nearest else None, algo))
+        return dist, near
+
     def components_label_host(self, frame: Frame, h_words, h_labels, conn: int = CONN_26, algo: int = ALGO_TILED) -> int:
         count = ctypes.c_uint32()
         check(lib().vp_components_label_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), h_labels.ctypes.data_as(_vp), conn, algo,
@@ -541,7 +573,7 @@ class Context:
 
     def prof_select(self, names=None):
         """Time only the kernels whose timing keys are named (None = all): every event pair costs stream time."""
-        mask = (1 << 64) - 1 if names is None else sum(1 << EVERY_PROF_KEY.index(k) for k in names)
+        mask = (1 << 64) - 1 if names is None else sum(1 << HEADER_PROF_KEYS.index(k) for k in names)
         check(lib().vp_prof_select(self._h, mask))
 
     def prof_reset(self):
@@ -549,7 +581,7 @@ class Context:
 
     def prof(self):
         out = {}
-        for i, name in enumerate(EVERY_PROF_KEY):
+        for i, name in enumerate(HEADER_PROF_KEYS):
             ms = ctypes.c_double()
             n = ctypes.c_uint64()
             check(lib().vp_prof_get(self._h, i, ctypes.byref(ms), ctypes.byref(n)))

@@ -128,7 +128,7 @@ static void grid_written(vp_ctx* ctx, const void* d_ptr, size_t bytes)
     if (overlaps(d_ptr, bytes, ctx->sn_words, (size_t)ctx->sn_n * ctx->sn_n * ctx->sn_n / 8)) ctx->sn_words = nullptr;
 }
 
-static const char* kNames[VP_K_END] = {
+static const char* kNames[VP_K_ALL] = {
     "vox_setup", "vox_scan", "vox_scatter", "vox_tile", "vox_naive", "vox_fill",
     "csg_words", "jfa_init", "jfa_pass", "jfa_final", "surface", "jfa_first", "jfa_sparse", "jfa_dense", "jfa_last", "extract", "vox_zero", "jfa_redeal",
     "cvox_zero", "cvox_setup", "cvox_scan", "cvox_rows", "cvox_naive",
@@ -137,7 +137,8 @@ static const char* kNames[VP_K_END] = {
     "comp_init", "comp_merge", "comp_init_naive", "comp_merge_naive", "comp_flatten", "comp_rank", "comp_relabel", "comp_sizes", "comp_select",
     "comp_write",
     "sn_cells", "sn_scan", "sn_verts", "sn_quads", "sn_relax", "sn_cells_naive", "sn_verts_naive", "sn_quads_naive", "sn_relax_naive",
-    "edt_x", "edt_y", "edt_z", "edt_y_naive", "edt_z_naive", "edt_sdf", "edt_thresh"
+    "edt_x", "edt_y", "edt_z", "edt_y_naive", "edt_z_naive", "edt_sdf", "edt_thresh",
+    "md_setup", "md_scan", "md_count", "md_write", "md_brick", "md_fill", "md_prefill", "md_naive", "md_split"
 };
 
 }  // namespace vp
@@ -148,7 +149,7 @@ using namespace vp;
 // out (a template: it cannot stand inside extern "C"): the grid goes up into SLOT_GRID_A, call(d_words, d_out) is the device entry point,
 // and its output -- a grid in SLOT_GRID_B or one 32-bit value per voxel in SLOT_SDF -- comes down.  The callers validate first: asking
 // for a slot already drops the records of the grids that lay in it.
-enum { SLOT_GRID_A = 0, SLOT_GRID_B = 1, SLOT_XYZ = 2, SLOT_TRI = 3, SLOT_SDF = 4 };
+enum { SLOT_GRID_A = 0, SLOT_GRID_B = 1, SLOT_XYZ = 2, SLOT_TRI = 3, SLOT_SDF = 4, SLOT_NEAREST = 5 };
 
 template <typename Call>
 static int host_round_trip(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, void* h_out, int out_slot, Call call)
@@ -204,7 +205,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
     Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
                        &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp,
                        &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small,
-                       &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz, &ctx->edt_mask, &ctx->edt_vol, &ctx->edt_vol2, &ctx->edt_tmp };
+                       &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz, &ctx->edt_mask, &ctx->edt_vol, &ctx->edt_vol2, &ctx->edt_tmp,
+                       &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -215,6 +217,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->cvox_host) (void)hipHostFree(ctx->cvox_host);
     if (ctx->fill_host) (void)hipHostFree(ctx->fill_host);
     if (ctx->comp_host) (void)hipHostFree(ctx->comp_host);
+    if (ctx->md_host) (void)hipHostFree(ctx->md_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -287,6 +290,7 @@ int vp_ctx_release(vp_ctx* ctx)
     release(ctx->edt_vol);
     release(ctx->edt_vol2);
     release(ctx->edt_tmp);
+    for (Buffer* b : { &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list }) release(*b);   // vp_mesh_distance
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -488,6 +492,45 @@ int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32
     VP_TRY(check_disjoint(who, "d_out", d_words, bytes, d_out, bytes));
     grid_written(ctx, d_out, bytes);
     return launch_edt_morph(ctx, make_frame(f), d_words, d_out, op, radius, algo);
+}
+
+// what vp_mesh_distance and its host form share: whole grids up to n = 1024, the algo, the band
+static int check_mesh_distance(const vp_frame* f, const char* who, uint32_t band, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_whole(f, who));
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
+    VP_TRY(check_algo(who, algo));
+    if (band < 1 || band > 32) return set_error(VP_ERR_INVALID, "%s: band %u (1 .. 32 voxels)", who, band);
+    return 0;
+}
+
+int vp_mesh_distance(vp_ctx* ctx, const vp_frame* f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,
+                     const uint32_t* d_sign_words, uint32_t band, float* d_dist2, uint32_t* d_nearest, int algo)
+{
+    const char* who = "vp_mesh_distance";
+    if (!ctx || !d_dist2) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_mesh_distance(f, who, band, algo));
+    if (ntris && (!d_xyz || !d_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
+    if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "%s: too many triangles", who);
+    VP_TRY(check_aligned(who, {d_xyz, d_tri, d_sign_words, d_dist2, d_nearest}));
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    for (const void* out : {(const void*)d_dist2, (const void*)d_nearest}) {
+        if (overlaps(out, vb, d_xyz, nverts * 12) || overlaps(out, vb, d_tri, ntris * 12) || overlaps(out, vb, d_sign_words, wb))
+            return set_error(VP_ERR_INVALID, "%s: an output overlaps an input", who);
+    }
+    if (overlaps(d_dist2, vb, d_nearest, vb)) return set_error(VP_ERR_INVALID, "%s: d_nearest overlaps d_dist2", who);
+    grid_written(ctx, d_dist2, vb);
+    grid_written(ctx, d_nearest, vb);
+    return launch_mesh_distance(ctx, make_frame(f), d_xyz, nverts, d_tri, ntris, d_sign_words, band, d_dist2, d_nearest, algo);
+}
+
+int vp_mesh_distance_stats(vp_ctx* ctx, uint64_t* list_entries)
+{
+    if (!ctx || !list_entries) return set_error(VP_ERR_INVALID, "vp_mesh_distance_stats: null argument");
+    *list_entries = ctx->md_last_total;
+    return 0;
 }
 
 // what the three vp_components_* entry points share: whole grids up to n = 1024, connectivity and algo
@@ -1100,6 +1143,28 @@ int vp_edt_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, u
                            [&](const uint32_t* dw, void* d) { return vp_edt_morph(ctx, f, dw, (uint32_t*)d, op, radius, algo); });
 }
 
+int vp_mesh_distance_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, size_t nverts, const uint32_t* h_tri, size_t ntris,
+                          const uint32_t* h_sign_words, uint32_t band, float* h_dist2, uint32_t* h_nearest, int algo)
+{
+    const char* who = "vp_mesh_distance_host";
+    if (!ctx || !h_dist2) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_mesh_distance(f, who, band, algo));
+    if (ntris && (!h_xyz || !h_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
+    void *dw = nullptr, *dx = nullptr, *dt = nullptr, *dd = nullptr, *dn = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    if (h_sign_words) VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nverts * 12, &dx));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, vb, &dd));
+    if (h_nearest) VP_TRY(vp_ctx_workspace(ctx, SLOT_NEAREST, vb, &dn));
+    if (h_sign_words) VP_TRY(vp_upload(ctx, dw, h_sign_words, wb));
+    VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
+    VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
+    VP_TRY(vp_mesh_distance(ctx, f, (const float*)dx, nverts, (const uint32_t*)dt, ntris, (const uint32_t*)dw, band, (float*)dd, (uint32_t*)dn, algo));
+    VP_TRY(vp_download(ctx, h_dist2, dd, vb));
+    return h_nearest ? vp_download(ctx, h_nearest, dn, vb) : 0;
+}
+
 int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,
                              uint32_t* h_count)
 {
@@ -1195,13 +1260,13 @@ int vp_prof_reset(vp_ctx* ctx)
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_prof_reset: null ctx");
     VP_TRY(bind_device(ctx));
     VP_TRY(prof_fold(ctx));
-    for (int i = 0; i < VP_K_END; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
+    for (int i = 0; i < VP_K_ALL; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
     return 0;
 }
 
 int vp_prof_get(vp_ctx* ctx, int kernel, double* total_ms, uint64_t* launches)
 {
-    if (!ctx || kernel < 0 || kernel >= VP_K_END) return set_error(VP_ERR_INVALID, "vp_prof_get: bad argument");
+    if (!ctx || kernel < 0 || kernel >= VP_K_ALL) return set_error(VP_ERR_INVALID, "vp_prof_get: bad argument");
     VP_TRY(bind_device(ctx));
     VP_TRY(prof_fold(ctx));
     if (total_ms) *total_ms = ctx->prof_ms[kernel];
@@ -1209,6 +1274,6 @@ int vp_prof_get(vp_ctx* ctx, int kernel, double* total_ms, uint64_t* launches)
     return 0;
 }
 
-const char* vp_prof_name(int kernel) { return (kernel >= 0 && kernel < VP_K_END) ? kNames[kernel] : "?"; }
+const char* vp_prof_name(int kernel) { return (kernel >= 0 && kernel < VP_K_ALL) ? kNames[kernel] : "?"; }
 
 }  // extern "C"

@@ -106,13 +106,19 @@ struct vp_ctx {
     // exact distance transform (edt.hip): the border mask of SEEDS_BORDER, the distance volume of vp_edt_morph, the second volume of the NAIVE
     // column passes (4 n^3 bytes each) and the intermediate grid of open / close; all four are freed by vp_ctx_release
     vp::Buffer edt_mask, edt_vol, edt_vol2, edt_tmp;
+    // mesh distance (meshdist.hip): NAIVE's key volume (8 n^3 bytes), the triangle records and their row scan, the brick counts (+ write
+    // cursors and plane sums) and offsets, the brick lists; the pinned host words the plane sums are read back through and the list
+    // length of the last TILED call (vp_mesh_distance_stats); the six buffers are freed by vp_ctx_release
+    vp::Buffer md_keys, md_rec, md_base, md_cnt, md_off, md_list;
+    uint64_t* md_host = nullptr;
+    uint64_t md_last_total = 0;
     // profiling
     bool prof_on = false;
     uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
     std::vector<vp::ProfSpan> prof_pending;
     std::vector<hipEvent_t> prof_pool;
-    double prof_ms[VP_K_END] = {};
-    uint64_t prof_n[VP_K_END] = {};
+    double prof_ms[VP_K_ALL] = {};
+    uint64_t prof_n[VP_K_ALL] = {};
 };
 
 namespace vp {
@@ -179,6 +185,10 @@ int launch_morph(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_o
 int launch_edt(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int seeds, uint32_t* d_dist, int algo);
 int launch_edt_sdf(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, float fill, float* d_sdf, int algo);
 int launch_edt_morph(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
+// meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
+// the list lengths back)
+int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,
+                         const uint32_t* d_sign, uint32_t band, float* d_dist, uint32_t* d_nearest, int algo);
 // components.hip: labels, sizes and size filters of the connected components of a whole grid; all three are blocking (counts go to the host)
 int launch_components_label(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_labels, int conn, int algo, uint32_t* h_count);
 int launch_components_sizes(vp_ctx* ctx, uint32_t n, const uint32_t* d_labels, uint32_t count, uint32_t* d_sizes);

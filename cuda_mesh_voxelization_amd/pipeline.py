@@ -102,6 +102,20 @@ class Engine:
         self.ctx.edt_morph(frame, words.data_ptr(), out.data_ptr(), op, radius, algo)
         return out
 
+    def mesh_distance(self, frame: Frame, d_xyz, d_tri, band: int, sign_words=None, want_nearest: bool = False, out=None, algo: int = ALGO_TILED):
+        """Narrow-band distance field to the triangles themselves (n <= 1024, band = 1 .. 32 voxels): a float32 tensor of n^3 values
+        min(B2, squared distance from the voxel centre to the nearest triangle), B = band * voxel size, x fastest; signed by `sign_words`
+        (a grid: + on set voxels, - on unset ones) if given.  want_nearest: also an int32 tensor with the index of the nearest face,
+        capi.MESH_NONE (-1 as int32) outside the band.  `out` = dist2, or (dist2, nearest).  Returns dist2, or (dist2, nearest)."""
+        dist, nearest = out if isinstance(out, (tuple, list)) else (out, None)
+        if dist is None:
+            dist = torch.empty(frame.voxels, dtype=torch.float32, device=self.device)
+        if want_nearest and nearest is None:
+            nearest = torch.empty(frame.voxels, dtype=torch.int32, device=self.device)
+        self.ctx.mesh_distance(frame, d_xyz.data_ptr(), d_xyz.shape[0], d_tri.data_ptr(), d_tri.shape[0], band, dist.data_ptr(),
+                               nearest.data_ptr() if want_nearest else 0, sign_words.data_ptr() if sign_words is not None else 0, algo)
+        return (dist, nearest) if want_nearest else dist
+
     def components_label(self, frame: Frame, words, conn: int = capi.CONN_26, algo: int = ALGO_TILED, out=None):
         """Connected components of the set voxels of a whole grid (capi.CONN_6 / CONN_26).  Returns (labels, K): an int32 tensor of n^3
         labels, x fastest, 0 = background, components 1 .. K in the order of their lowest voxel index -- scipy.ndimage.label's

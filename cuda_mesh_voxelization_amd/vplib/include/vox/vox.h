@@ -46,6 +46,12 @@ void EdtHost(bool parallel, const uint32_t* words, size_t n, int seeds, uint32_t
 void EdtDevice(int algo, const char* label, const uint32_t* words, size_t n, float voxelSize, const float origin[3], int seeds, uint32_t* dist);
 void MorphExactHost(bool parallel, uint32_t* words, size_t n, int op, uint32_t radius);
 void MorphExactDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], int op, uint32_t radius);
+// mesh distance (meshdist.cpp): host restatement by plain loops over the triangles and their band boxes, and the GPU marshalling; `sign`
+// (grid words) and `nearest` may be null
+void MeshDistanceHost(bool parallel, const uint32_t* sign, size_t n, float voxelSize, const float origin[3], const Mesh& mesh, uint32_t band,
+                      float* dist2, uint32_t* nearest);
+void MeshDistanceDevice(int algo, const char* label, const uint32_t* sign, size_t n, float voxelSize, const float origin[3], const Mesh& mesh,
+                        uint32_t band, float* dist2, uint32_t* nearest);
 // connected components (components.cpp): host restatement by a scan in index order with an explicit-stack flood per component, and the
 // GPU marshalling; the filters work in place
 struct ComponentStats { uint32_t count; uint64_t kept; };      // K components found, voxels kept
@@ -185,6 +191,33 @@ void MorphExact(HostVoxelsGrid<T>& grid, MorphOp op, uint32_t radius)
     else
         detail::MorphExactDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveMorphExact" : "TiledMorphExact", words,
                                  v.VoxelsPerSide(), v.VoxelSize(), origin, static_cast<int>(op), radius);
+}
+
+// MeshDistance: the narrow-band distance field to the TRIANGLES of `mesh`, sampled at the voxel centres of `grid`'s frame (include/vphip.h,
+// vp_mesh_distance): dist2(x, y, z) = min(B2, the squared distance from the centre to the nearest triangle), B = band voxels (1 .. 32),
+// positive on the set voxels of `grid` and negative on the unset ones when `withSign` (the grid is then whatever solid the caller made of
+// the mesh), +everywhere otherwise; `nearest` (optional) = the index of the nearest face, VP_MESH_NONE outside the band.  Both are resized
+// to the grid.  No reference counterpart.
+//   SEQUENTIAL / OPENMP   host restatement: plain loops over the triangles and the voxels of their band boxes, the header's float32
+//                         expressions (OPENMP: parallel over z planes); any grid side
+//   NAIVE / TILED         vp_mesh_distance_host with VP_ALGO_NAIVE / VP_ALGO_TILED (n % 32 == 0, n <= 1024)
+// Every variant produces the same bits.
+template <Types type, VGType T>
+void MeshDistance(const HostVoxelsGrid<T>& grid, const Mesh& mesh, uint32_t band, HostGrid<float>& dist2, HostGrid<uint32_t>* nearest = nullptr,
+                  bool withSign = true)
+{
+    const auto& v = grid.View();
+    const size_t n = v.VoxelsPerSide();
+    if (dist2.View().SizeX() != n || dist2.View().SizeY() != n || dist2.View().SizeZ() != n) dist2 = HostGrid<float>(n, 0.0f);
+    if (nearest && (nearest->View().SizeX() != n || nearest->View().SizeY() != n || nearest->View().SizeZ() != n)) *nearest = HostGrid<uint32_t>(n, 0u);
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    const uint32_t* words = withSign ? reinterpret_cast<const uint32_t*>(v.Data()) : nullptr;
+    uint32_t* near = nearest ? nearest->View().Data() : nullptr;
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        detail::MeshDistanceHost(type == Types::OPENMP, words, n, v.VoxelSize(), origin, mesh, band, dist2.View().Data(), near);
+    else
+        detail::MeshDistanceDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveMeshDistance" : "TiledMeshDistance", words, n,
+                                   v.VoxelSize(), origin, mesh, band, dist2.View().Data(), near);
 }
 
 // LabelComponents / FilterComponents: connected components of the set voxels (include/vphip.h, vp_components_*).  conn = 6 (face

@@ -212,6 +212,61 @@ int vp_edt(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int seeds, u
 int vp_edt_sdf(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fill_unset, float* d_sdf, int algo);
 int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
 
+/* ---- narrow-band distance to the triangles of a mesh, with the nearest face (no reference counterpart) ----------
+ * vp_jfa and vp_edt_sdf measure from voxel centre to the centre of the nearest border VOXEL; this field is measured to the TRIANGLES.
+ * Everything is float32, every operation one correctly rounded IEEE operation in the association written here, no FMA contraction (the
+ * library is built with -ffp-contract=off); the branch conditions are part of the contract.  Dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ *   sample point  p = the voxel centre as vp_voxelize forms it: p.a = o.a + (((float)i * vs) + (vs / 2.0f))
+ *   triangle      a, b, c = its three vertices in index order.  It contributes NOTHING if an index is >= nverts, a vertex coordinate is not
+ *                 finite, or Cross(e0, e1) == (0, 0, 0) with e0 = b - a, e1 = c - b in the association of vp_voxelize_conservative.
+ *   D2(p, t)      the region walk of Ericson, Real-Time Collision Detection 5.1.5, to the closest point q of the closed triangle:
+ *                   ab = b - a, ac = c - a, ap = p - a;  d1 = Dot(ab, ap), d2 = Dot(ac, ap);      d1 <= 0 && d2 <= 0:  q = a
+ *                   bp = p - b;  d3 = Dot(ab, bp), d4 = Dot(ac, bp);                              d3 >= 0 && d4 <= d3:  q = b
+ *                   vc = (d1 d4) - (d3 d2);      vc <= 0 && d1 >= 0 && d3 <= 0:  v = d1 / (d1 - d3),  q.a = a.a + (ab.a v)
+ *                   cp = p - c;  d5 = Dot(ab, cp), d6 = Dot(ac, cp);                              d6 >= 0 && d5 <= d6:  q = c
+ *                   vb = (d5 d2) - (d1 d6);      vb <= 0 && d2 >= 0 && d6 <= 0:  w = d2 / (d2 - d6),  q.a = a.a + (ac.a w)
+ *                   va = (d3 d6) - (d5 d4), e43 = d4 - d3, e56 = d5 - d6;
+ *                                                va <= 0 && e43 >= 0 && e56 >= 0:  w = e43 / (e43 + e56),  q.a = b.a + ((c.a - b.a) w)
+ *                   otherwise the face: den = (va + vb) + vc, v0 = vb / den, w0 = vc / den;  v = v0 > 0 ? v0 : 0, then v = v < 1 ? v : 1;
+ *                                                wl = 1 - v;  w = w0 > 0 ? w0 : 0, then w = w < wl ? w : wl;  q.a = (a.a + (ab.a v)) + (ac.a w)
+ *                 the first condition that holds decides, in this order.  The two clamps of the face are the identity in exact arithmetic
+ *                 (there 0 < v0, 0 < w0, v0 + w0 < 1); in float they keep q inside the triangle when rounding has left va, vb, vc with mixed
+ *                 signs, which is what lets every culling below be proved.  A comparison with a NaN is false.
+ *                 Then d = p - q and D2 = (d.x d.x + d.y d.y) + d.z d.z.
+ *   band          B = (float)band * vs, B2 = B * B; band = 1 .. 32 voxels, anything else: VP_ERR_INVALID.  A candidate whose D2 is not
+ *                 finite, or for which D2 < B2 does not hold, is dropped: a centre at distance exactly B is NOT within the band.
+ *   field         m(p) = min(B2, the minimum of D2(p, t) over the candidates);  d_dist2[x + n (y + n z)] = s m(p), squared world units like
+ *                 the sdf; s = +1 everywhere when d_sign_words is NULL (unsigned field), otherwise +1 on the set voxels of that grid and -1
+ *                 on the unset ones (the sign convention of vp_jfa and vp_edt_sdf; a zero distance on an unset voxel is -0.0f).
+ *   nearest face  d_nearest[...] (may be NULL) = the lowest triangle index among the candidates that attain m(p), VP_MESH_NONE where there
+ *                 is no candidate: the lexicographic minimum of (D2 bits, index).  Ties are the normal case -- every triangle around a
+ *                 shared vertex returns that vertex bit for bit.  ntris = 0 gives s B2 and VP_MESH_NONE everywhere.
+ * A min over a set: the result does not depend on the order of evaluation, nor on which pairs were culled -- candidate ranges never decide a
+ * value, they only skip pairs that provably fail D2 < B2 as computed in float32.
+ * THE SIGN is whatever grid the caller passes.  With vp_voxelize's grid it is the reference's column rule: a voxel is set from the cell
+ * that CONTAINS the crossing, not from the first centre behind it, so along x a centre up to half a voxel outside the surface can carry +.
+ * That is a property of the reference's solid rule, not of this field; a caller who needs a centre-exact sign passes a grid of their own.
+ *   algo: VP_ALGO_NAIVE -- one thread per triangle over the voxels of its band box, one 64-bit atomicMin per accepted pair on the key
+ *   (D2 bits << 32) | index, then a streaming split; VP_ALGO_TILED -- triangles binned to 8 x 8 x 8-voxel bricks (count, scan, write; the
+ *   brick rows of large triangles dealt to lanes), one workgroup per brick with the records staged through LDS, (D2, index) in registers,
+ *   one plain store per voxel; bricks without a list by a streaming fill.  Same bytes.
+ * Whole-grid frames only: a slab frame returns VP_ERR_UNSUPPORTED; so does n > 1024.  Every buffer is 16-byte aligned; the outputs must not
+ * overlap the inputs or each other.  Null ctx / f / d_dist2, null mesh arrays with ntris > 0, an unknown algo, band 0 or above 32:
+ * VP_ERR_INVALID.  Every refusal leaves the outputs untouched.
+ * VP_ALGO_TILED is BLOCKING once per call: the list lengths of the brick planes (n / 8 totals) are read back to size the lists, so it
+ * cannot be captured in a graph; VP_ALGO_NAIVE only enqueues once its buffer has grown.  Grow-only buffers of the context, all freed by
+ * vp_ctx_release: the key volume of NAIVE (8 n^3 bytes), the triangle records (96 B each), their row counts and row scan (12 B per
+ * triangle), the brick counts, write cursors and offsets (16 B per brick, plus 8 B per plane of bricks) and the brick lists (4 B per entry; at most 2^27 entries per launch -- a grid whose lists are longer runs in several z
+ * ranges of bricks, a single plane of bricks above the cap being a range of its own).  Like every writer, it drops a pending
+ * vp_jfa_start / extract / surfnets count whose bytes an output overlaps.
+ * vp_mesh_distance_stats: *list_entries = the (triangle, brick) pairs the last VP_ALGO_TILED call of this context listed (512 pairs of
+ * (triangle, voxel) each reach the per-pair bounds).  Measurement only. */
+#define VP_MESH_NONE 0xFFFFFFFFu
+int vp_mesh_distance(vp_ctx* ctx, const vp_frame* f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,
+                     const uint32_t* d_sign_words /* may be NULL */, uint32_t band, float* d_dist2, uint32_t* d_nearest /* may be NULL */,
+                     int algo);
+int vp_mesh_distance_stats(vp_ctx* ctx, uint64_t* list_entries);
+
 /* ---- connected components: labels, sizes, size filters (no reference counterpart) ----------------
  * Set voxels are the foreground, voxels outside the grid are empty.  connectivity: VP_CONN_6 (face neighbours) or VP_CONN_26 (face, edge
  * and corner neighbours) = scipy.ndimage.generate_binary_structure(3, 1) and (3, 3).  Integer arithmetic only.
@@ -542,6 +597,11 @@ int vp_edt_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int see
 int vp_edt_sdf_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, float fill_unset, float* h_sdf, int algo);
 int vp_edt_morph_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_out, int op, uint32_t radius, int algo);
 
+/* vp_mesh_distance with the convention above (whole-grid frame): mesh and sign grid up, the field and the nearest faces down; staged
+ * through workspace slots.  h_sign_words and h_nearest may be NULL; h_dist2 and h_nearest hold n^3 values. */
+int vp_mesh_distance_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, size_t nverts, const uint32_t* h_tri, size_t ntris,
+                          const uint32_t* h_sign_words, uint32_t band, float* h_dist2, uint32_t* h_nearest, int algo);
+
 /* ---- per-kernel timing (PROFILING_SCOPE equivalent for device time, vplib/src/profiling.h:8-33)
  * When enabled, every kernel launch is bracketed by hipEvents on the context's stream. */
 enum {
@@ -607,6 +667,21 @@ enum {
     VP_K_EDT_SDF,               /* D -> sdf in place: n^3/8 + 4 n^3 read, 4 n^3 written */
     VP_K_EDT_THRESH,            /* D -> bit words: 4 n^3 read, n^3/8 written */
     VP_K_END
+};
+/* the keys of vp_mesh_distance follow the third enum.  THE MASK IS NOW FULL: the four enums together hold exactly 64 keys, the width of
+ * vp_prof_select's mask (md_offsets and md_plane_sums already share the keys of md_scan and md_count for that reason).  The next kernel
+ * that wants a key of its own needs a wider mask, i.e. a new vp_prof_select and a new VP_ABI_VERSION; until then it shares a key. */
+enum {
+    VP_K_MD_SETUP = VP_K_END,   /* TILED: triangle records, brick ranges and row counts: 36 T read + 100 T written (T triangles) */
+    VP_K_MD_SCAN,               /* TILED: one-workgroup scans that read their counts twice: the triangles' row counts (8 T read + 8 T written); per z range the brick counts (8 B read + 8 B written per brick) */
+    VP_K_MD_COUNT,              /* TILED: brick test per (triangle, brick) of every brick row, one add per listed pair; + the plane sums (4 B per brick) */
+    VP_K_MD_WRITE,              /* TILED: the same walk, 4 B written per list entry L */
+    VP_K_MD_BRICK,              /* TILED: 4 L + 96 L read (records, mostly from L2), 4 or 8 B written per voxel of a listed brick */
+    VP_K_MD_FILL,               /* both algos: bricks without a list (ntris = 0: all): n^3/8 sign bits read, 4 or 8 B per voxel written */
+    VP_K_MD_PREFILL,            /* NAIVE: 8 n^3 written */
+    VP_K_MD_NAIVE,              /* NAIVE: 36 T read + one 8-byte atomic per accepted pair */
+    VP_K_MD_SPLIT,              /* NAIVE: 8 n^3 + n^3/8 read, 4 or 8 n^3 written */
+    VP_K_ALL
 };
 int vp_prof_enable(vp_ctx* ctx, int on);
 /* Restricts the bracketing to the keys whose bit is set (bit i = key i; default: all).  An event pair costs ~3 us of stream
