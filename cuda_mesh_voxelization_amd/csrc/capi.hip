@@ -111,6 +111,11 @@ static int bind_device(vp_ctx* ctx)
 // buffer it was taken from is written through this ABI or handed out again as a workspace slot.
 // The same holds for the record of vp_jfa_start: its border mask (or init ids) was computed from the grid CONTENTS, so a write to
 // that grid -- or to the workspace itself -- between start and run invalidates it ("same grid" in the header means same contents).
+// The rule: ANY output of ANY call of this ABI that the caller addresses -- grids, id planes and windows, sdf and distance volumes, record
+// and mesh arrays, an explicit JFA workspace -- is such a write; every entry point reports each of its outputs to grid_written before it
+// launches (tests/test_ctx_records_gpu.py holds the table of writers against the entry points of the header).  "Before it launches" is
+// before the checks of the launch functions themselves (vp_jfa_pass, vp_jfa_last_pass, vp_extract and the window calls can still be
+// refused there): a record may be dropped by a call that then writes nothing, never kept by one that writes.
 // Byte RANGES are compared: a write into the interior of the grid -- vp_voxelize / vp_csg on a slab frame, vp_memcpy_d2d
 // into a sub-range -- invalidates the records like a write to its first byte does.
 static bool overlaps(const void* a, size_t an, const void* b, size_t bn)
@@ -252,7 +257,11 @@ int vp_free(vp_ctx* ctx, void* d_ptr)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_free: null ctx");
     VP_TRY(bind_device(ctx));
-    grid_written(ctx, d_ptr, 1);
+    // the whole allocation goes, not its first byte: a record may be about a range anywhere inside it
+    void* base = nullptr;
+    size_t size = 0;
+    if (d_ptr && hipMemGetAddressRange(&base, &size, d_ptr) == hipSuccess && base == d_ptr && size) grid_written(ctx, d_ptr, size);
+    else { (void)hipGetLastError(); grid_written(ctx, d_ptr, 1); }
     if (d_ptr) { VP_HIP(hipStreamSynchronize(ctx->stream)); VP_HIP(hipFree(d_ptr)); }
     return 0;
 }
@@ -632,6 +641,7 @@ int vp_jfa_init(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, const u
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, "vp_jfa_init", false));
     VP_TRY(check_aligned("vp_jfa_init", {d_words, d_plane_below, d_plane_above, d_ids}));
+    grid_written(ctx, d_ids, vp_grid_voxels(f) * vp_jfa_id_bytes(f));
     return launch_jfa_init(ctx, make_frame(f), d_words, d_plane_below, d_plane_above, d_ids, nullptr);
 }
 
@@ -642,6 +652,7 @@ int vp_surface(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, const ui
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, "vp_surface", false));
     VP_TRY(check_aligned("vp_surface", {d_words, d_plane_below, d_plane_above, d_border_words}));
+    grid_written(ctx, d_border_words, vp_grid_words(f) * 4);
     return launch_jfa_init(ctx, make_frame(f), d_words, d_plane_below, d_plane_above, nullptr, d_border_words);
 }
 
@@ -657,6 +668,7 @@ int vp_jfa_pass(vp_ctx* ctx, const vp_frame* f, uint32_t k, const void* d_in, co
     // halos are mandatory wherever a neighbour plane exists outside the slab
     if (f->z0 > 0 && !d_minus) return set_error(VP_ERR_INVALID, "vp_jfa_pass: slab needs d_minus");
     if (f->z1 < f->n && !d_plus) return set_error(VP_ERR_INVALID, "vp_jfa_pass: slab needs d_plus");
+    grid_written(ctx, d_out, vp_grid_voxels(f) * vp_jfa_id_bytes(f));
     return launch_jfa_pass(ctx, make_frame(f), k, d_in, d_minus, d_plus, d_out, algo);
 }
 
@@ -667,6 +679,7 @@ int vp_jfa_finalize(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, con
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, "vp_jfa_finalize", false));
     VP_TRY(check_fill(fill_unset, "vp_jfa_finalize"));
+    grid_written(ctx, d_sdf, vp_grid_voxels(f) * 4);
     return launch_jfa_final(ctx, make_frame(f), d_words, d_ids, fill_unset, d_sdf);
 }
 
@@ -697,12 +710,14 @@ static bool jfa_tile_sequence(const Frame& fr, int algo) { return jfa_can_fuse_f
 
 int vp_jfa_start(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, void* d_work, size_t work_bytes, int algo)
 {
+    const bool explicitWork = d_work != nullptr;                   // the context's own workspace is nobody's grid
     VP_TRY(jfa_check(ctx, f, d_words, d_work, work_bytes, algo, "vp_jfa_start"));
     const Frame fr = make_frame(f);
     const size_t volBytes = vp_grid_voxels(f) * vp_jfa_id_bytes(f);
     char* a = (char*)d_work;
     const bool mask = jfa_tile_sequence(fr, algo);
     ctx->jfa_started.valid = false;
+    if (explicitWork) grid_written(ctx, d_work, vp_jfa_workspace_bytes(f));     // the workspace may be a grid somebody counted
     if (mask) VP_TRY(launch_jfa_init(ctx, fr, d_words, nullptr, nullptr, nullptr, (uint32_t*)(a + 2 * volBytes)));   // border mask only
     else      VP_TRY(launch_jfa_init(ctx, fr, d_words, nullptr, nullptr, a, nullptr));
     ctx->jfa_started = {true, mask, f->n, algo, d_work, work_bytes, d_words};
@@ -714,6 +729,7 @@ int vp_jfa_run(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fi
 {
     if (!d_sdf) return set_error(VP_ERR_INVALID, "vp_jfa_run: null argument");
     VP_TRY(check_aligned("vp_jfa_run", {d_sdf}));
+    const bool explicitWork = d_work != nullptr;
     VP_TRY(jfa_check(ctx, f, d_words, d_work, work_bytes, algo, "vp_jfa_run"));
     VP_TRY(check_fill(fill_unset, "vp_jfa_run"));
     const Frame fr = make_frame(f);
@@ -728,6 +744,8 @@ int vp_jfa_run(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fi
     ctx->jfa_started.valid = false;
     if (!st.valid || st.n != f->n || st.algo != algo || st.work != d_work || st.words != d_words || st.mask != wantMask)
         return set_error(VP_ERR_INVALID, "vp_jfa_run: call vp_jfa_start with the same grid, frame, algo and workspace first");
+    if (explicitWork) grid_written(ctx, d_work, vp_jfa_workspace_bytes(f));     // the passes overwrite the volumes (the caller's: the context's own is nobody's grid)
+    grid_written(ctx, d_sdf, vp_grid_voxels(f) * 4);               // the sdf is an output like any other
     if (wantMask) {
         // two windows of n planes (5 bytes per voxel above n = 1024, inside the 8-byte volumes of the workspace: nobody outside this
         // function sees them)
@@ -788,6 +806,8 @@ int vp_jfa_last_pass(vp_ctx* ctx, const vp_frame* f, const void* d_in, const voi
     VP_TRY(check_algo("vp_jfa_last_pass", algo));
     if (f->z0 > 0 && !d_minus) return set_error(VP_ERR_INVALID, "vp_jfa_last_pass: slab needs d_minus");
     if (f->z1 < f->n && !d_plus) return set_error(VP_ERR_INVALID, "vp_jfa_last_pass: slab needs d_plus");
+    grid_written(ctx, d_scratch, vp_grid_voxels(f) * vp_jfa_id_bytes(f));
+    grid_written(ctx, d_sdf, vp_grid_voxels(f) * 4);
     const Frame fr = make_frame(f);
     if (jfa_pass_can_fuse_final(fr, 1, algo))
         return launch_jfa_pass_ex(ctx, fr, 1, d_in, d_minus, d_plus, d_scratch, algo, d_words, fill_unset, d_sdf);
@@ -980,6 +1000,7 @@ static int window_pass(vp_ctx* ctx, const vp_frame* f, uint32_t k, const vp_wind
     VP_TRY(window_check(ctx, f, in, who, below, above, wi));
     VP_TRY(window_check(ctx, f, out, who, 0, 0, wo));
     window_written(ctx, out);
+    if (d_sdf) grid_written(ctx, d_sdf, vp_grid_voxels(f) * 4);     // vp_jfa_window_last_pass: the sdf of the region
     return launch_win_pass(ctx, make_frame(f), k, wi, wo, stride, d_words, fill, d_sdf);
 }
 
@@ -1015,6 +1036,14 @@ int vp_extract(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int mode
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, "vp_extract", true));
     if (mode < VP_EXTRACT_SET || mode > VP_EXTRACT_FACES) return set_error(VP_ERR_INVALID, "vp_extract: mode %d", mode);
+    // the records and values are outputs like any other: at most min(capacity, the standing count) of them are written.  Reported whether or
+    // not that count is of this grid -- launch_extract_write alone decides that, and refuses below where it is not; an output that lies on
+    // the grid itself drops the count here and is refused too
+    const size_t cnt = (size_t)std::min<uint64_t>(capacity, ctx->ext_total);
+    if (cnt) {
+        grid_written(ctx, d_records, cnt * 8);
+        grid_written(ctx, d_values, cnt * 4);
+    }
     return launch_extract_write(ctx, make_frame(f), d_words, mode, d_sdf, d_records, d_values, capacity);
 }
 

@@ -49,6 +49,7 @@ struct Rank {
     uint32_t win_n = 0, win_planes = 0;        // ... and their geometry
     Buffer cyc[2], staging;                    // VP_MULTI_TRANSPOSE: the two windows of the cyclic phase, the chunks the re-deal delivers
     uint32_t cyc_n = 0, cyc_planes = 0, stg_n = 0, stg_planes = 0;
+    uint64_t job_id_bytes = 0;                 // bytes of the id windows the LAST vp_multi_jfa used (set by its mode's driver; 0: not sharded)
     Buffer border;                             // ghost / hybrid: border mask of the whole grid
     Buffer whole_sdf;                          // n < 96 (not sharded): sdf of the whole grid
     Buffer sdf;                                // slab
@@ -301,6 +302,7 @@ int jfa_small(vp_multi* m, float fill, int algo)
     const size_t plane = (size_t)G.n * G.n;
     VP_TRY(gather_words(m));
     for (Rank& r : m->ranks) {
+        r.job_id_bytes = 0;                                         // no id window: the context's own workspace holds the ids
         VP_TRY(grow(r, r.whole_sdf, vp_grid_voxels(&G) * 4));
         VP_TRY(grow(r, r.sdf, (size_t)(r.z1 - r.z0) * plane * 4));
         VP_TRY(vp_jfa(r.ctx, &G, (const uint32_t*)r.words.ptr, fill, (float*)r.whole_sdf.ptr, nullptr, 0, algo));
@@ -321,6 +323,7 @@ int jfa_halo(vp_multi* m, float fill)
     const uint32_t planes = world > 1 ? 3 * nz : nz, at = world > 1 ? nz : 0;
     for (Rank& r : m->ranks) {
         VP_TRY(ensure_windows(r, G, planes));
+        r.job_id_bytes = 2 * (uint64_t)vp_jfa_window_bytes(&G, planes);
         VP_TRY(grow(r, r.sdf, (size_t)nz * n * n * 4));
         if (world > 1) { VP_TRY(grow(r, r.below, planeWords)); VP_TRY(grow(r, r.above, planeWords)); }
     }
@@ -377,6 +380,7 @@ int jfa_ghost(vp_multi* m, float fill)
     for (Rank& r : m->ranks) {
         VP_TRY(grow(r, r.border, vp_grid_words(&G) * 4));
         VP_TRY(ensure_windows(r, G, n));
+        r.job_id_bytes = 2 * (uint64_t)vp_jfa_window_bytes(&G, n);
         VP_TRY(grow(r, r.sdf, (size_t)nz * n * n * 4));
     }
     // words buffers hold the whole grid with the rank's own slab at its global position (vp_multi_set_grid / vp_multi_voxelize place it
@@ -429,6 +433,7 @@ int jfa_hybrid(vp_multi* m, float fill)
         m->window_lo[r] = p.lo; m->window_hi[r] = p.hi;
         VP_TRY(grow(me, me.border, vp_grid_words(&G) * 4));
         VP_TRY(ensure_windows(me, G, p.hi - p.lo));
+        me.job_id_bytes = 2 * (uint64_t)vp_jfa_window_bytes(&G, p.hi - p.lo);
         VP_TRY(grow(me, me.sdf, (size_t)nz * n * n * 4));
     }
     // the wide passes need the bitmask of the whole grid on every device (as in the ghost mode)
@@ -521,6 +526,7 @@ int jfa_transpose(vp_multi* m, float fill)
         VP_TRY(ensure_window_set(me, me.cyc, 2, me.cyc_n, me.cyc_planes, G, nz));
         VP_TRY(ensure_window_set(me, &me.staging, 1, me.stg_n, me.stg_planes, G, p.t1 - p.t0));
         VP_TRY(ensure_windows(me, G, p.hi - p.lo));
+        me.job_id_bytes = 2 * (uint64_t)vp_jfa_window_bytes(&G, p.hi - p.lo) + 2 * (uint64_t)vp_jfa_window_bytes(&G, nz) + vp_jfa_window_bytes(&G, p.t1 - p.t0);
         VP_TRY(grow(me, me.sdf, (size_t)nz * n * n * 4));
     }
     // every device needs the bitmask of the whole grid: the border bits of its planes z = r (mod G) depend on the planes z -+ 1
@@ -738,11 +744,9 @@ int vp_multi_window(const vp_multi* m, int rank, uint32_t* lo, uint32_t* hi, uin
     else if (n >= 96 && (m->last_mode == VP_MULTI_HYBRID || m->last_mode == VP_MULTI_TRANSPOSE)) { a = m->window_lo[(size_t)rank]; b = m->window_hi[(size_t)rank]; }
     if (lo) *lo = a;
     if (hi) *hi = b;
-    // the id windows the mode of the last job used (buffers are grow-only and kept: those of other modes are not this job's state)
-    if (id_bytes) {
-        *id_bytes = (uint64_t)vp_jfa_window_bytes(&m->frame, r.win_planes) * 2;
-        if (n >= 96 && m->last_mode == VP_MULTI_TRANSPOSE) *id_bytes += (uint64_t)vp_jfa_window_bytes(&m->frame, r.cyc_planes) * 2 + vp_jfa_window_bytes(&m->frame, r.stg_planes);
-    }
+    // the id windows the last job used, as its driver recorded them (buffers are grow-only and kept: those of earlier jobs, other modes or
+    // other sides are not this job's state; a grid below the sharded range uses none)
+    if (id_bytes) *id_bytes = r.job_id_bytes;
     return 0;
 }
 

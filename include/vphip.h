@@ -76,6 +76,8 @@ int vp_abi_version(void);
  * hipMalloc, vp_malloc and the usual framework allocators return; the kernels move these buffers as 16-byte vectors.  A pointer
  * that is not is refused with VP_ERR_INVALID (slab planes inside such a buffer are aligned by construction: n % 32 == 0). */
 int vp_malloc(vp_ctx* ctx, size_t bytes, void** d_out);
+/* vp_free takes the base pointer of an allocation and counts as a write to ALL of it for the records a context keeps about caller
+ * buffers (see vp_jfa_start): a record about a range anywhere inside the freed allocation is dropped. */
 int vp_free(vp_ctx* ctx, void* d_ptr);
 int vp_memset(vp_ctx* ctx, void* d_ptr, int byte_value, size_t bytes);           /* async */
 /* CudaPtr's copy constructor / assignment: device-to-device deep copy (cuda_ptr.h:42-53).  async */
@@ -329,7 +331,8 @@ int vp_components_filter(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words
  *   vp_surfnets_count   *h_vertices = V, *h_quads = Q.  BLOCKING (the totals are read back); cannot be captured in a graph.
  *   vp_surfnets         writes V records, V positions and Q quads and runs the relaxation; the result ends in d_xyz for any iteration
  *                       count.  It must follow a vp_surfnets_count of the same grid CONTENTS, frame side and algo ("same grid" as for
- *                       vp_extract: the count is dropped as soon as the grid is written through this ABI); otherwise, or with a capacity
+ *                       vp_extract: the count is dropped as soon as any output of any call of this ABI lands on any part of the
+ *                       grid -- the rule stated at vp_jfa_start); otherwise, or with a capacity
  *                       below V / Q: VP_ERR_INVALID.  Enqueues only, once the context's buffers have grown.  The outputs must not overlap
  *                       d_words; d_cells / d_xyz / d_quads may be NULL only when V (Q) is 0.
  * Scratch memory is the context's: the rank lookup (VP_ALGO_NAIVE: a uint32 vertex-index volume, 4 (n+1)^3 bytes -- 4.3 GB at n = 1024;
@@ -380,9 +383,12 @@ int vp_jfa(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fill_u
  * The context records what vp_jfa_start left in the workspace (grid pointer, n, algo, workspace, border mask or init ids);
  * vp_jfa_run returns VP_ERR_INVALID unless exactly that start preceded it -- one start serves one run, and the record is
  * dropped when the workspace is released, regrown or freed, and when the grid buffer or the workspace is written through this ABI
- * in between -- vp_voxelize, vp_csg, vp_upload, vp_memset, vp_memcpy_d2d, vp_stream_copy into ANY part of it (a slab of the grid, a
- * sub-range of the workspace: the byte ranges are compared), vp_free, or the buffer handed out again by vp_ctx_workspace: "the same
- * grid" means the same CONTENTS -- the border mask of the start no longer describes them. */
+ * in between.  The rule, not a list of functions: ANY output of ANY call of this ABI that lands on ANY part of the grid or of the
+ * workspace (a slab of the grid, a sub-range of the workspace: the byte ranges are compared) is such a write -- grids, id planes and
+ * windows, sdf and distance volumes, labels, records and mesh arrays, the explicit workspace of another vp_jfa* call -- and so are
+ * vp_free of the allocation that holds it and the buffer handed out again by vp_ctx_workspace: "the same grid" means the same
+ * CONTENTS -- the border mask of the start no longer describes them.  A buffer that merely touches the range (ends where it begins, begins where it ends)
+ * is no write to it.  A caller that writes with its own kernels must start again itself. */
 int vp_jfa_start(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, void* d_work, size_t work_bytes, int algo);
 int vp_jfa_run(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fill_unset,
                float* d_sdf, void* d_work, size_t work_bytes, int algo);
@@ -497,9 +503,10 @@ int vp_surface(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words,
  *   record = linear voxel index x + n (y + n z) in bits 0..39 | face mask << 40 (bit = axis * 2 + side; X, Y, Z; 0 = minus)
  * vp_extract_count runs the counting pass and returns the number of records (blocking); vp_extract then writes up to
  * `capacity` records (and, when d_sdf and d_values are given, the sdf value of each voxel) -- it must follow a count call for
- * the same grid and mode, else VP_ERR_INVALID.  "Same grid" means same contents: the count is forgotten as soon as d_words is
- * written through this ABI (vp_voxelize, vp_csg, vp_upload, vp_memset, vp_memcpy_d2d), freed, or handed out again by
- * vp_ctx_workspace; a caller that writes the buffer with its own kernels must count again itself. */
+ * the same grid and mode, else VP_ERR_INVALID.  "Same grid" means same contents: the count is forgotten as soon as any part of
+ * d_words is written through this ABI -- the rule stated at vp_jfa_start: any output of any call of this ABI whose byte range
+ * overlaps the grid's, vp_extract's own d_records / d_values included --, freed, or handed out again by vp_ctx_workspace; a caller
+ * that writes the buffer with its own kernels must count again itself. */
 enum { VP_EXTRACT_SET = 0, VP_EXTRACT_EXPOSED = 1, VP_EXTRACT_FACES = 2 };
 int vp_extract_count(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int mode, uint64_t* h_count);
 int vp_extract(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int mode, const float* d_sdf,
@@ -558,7 +565,8 @@ uint64_t vp_multi_bytes_moved(const vp_multi* m);
 /* JFA state a rank held during the last vp_multi_jfa: the global planes [lo, hi) its two id windows are addressed by -- the whole grid with
  * VP_MULTI_GHOST, the slab with VP_MULTI_HALO (its windows also hold the two slabs received from z -+ k), the planes the rank touches
  * with VP_MULTI_HYBRID, the widened slab of the second phase with VP_MULTI_TRANSPOSE -- and the bytes of device memory in the id windows
- * that job used.  Any out pointer may be NULL. */
+ * THAT job used (not those an earlier job of another side or mode left allocated; 0 below n = 96, where the grid is not sharded and no id
+ * window is used).  Any out pointer may be NULL. */
 int vp_multi_window(const vp_multi* m, int rank, uint32_t* lo, uint32_t* hi, uint64_t* id_bytes);
 
 /* ---- host-in / host-out conveniences (the reference's Compute() calling convention) -------

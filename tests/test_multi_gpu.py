@@ -355,3 +355,52 @@ def test_multi_smallest_sides_of_every_branch_equal_single(engine, n, world):
                 assert m.bytes_moved == 2 * (world - 1) * n * n // 8 + ids * n * n * 4
     finally:
         m.close()
+
+
+def test_multi_window_after_a_change_of_job(engine):
+    """vp_multi_window reports the id windows of the LAST job, whatever the driver ran before: one vp_multi goes through jobs of other
+    sides and modes -- larger to smaller, sharded to unsharded (n = 64) and back, modes that use the cyclic and staging windows and modes
+    that do not -- and after each one grid and sdf are bit-identical to the single-context result, (lo, hi) is what slab.py plans, and
+    id_bytes of every rank is what a FRESH vp_multi reports after that one job alone (the history-free object is the reference); the job
+    below the sharded range uses no id window at all."""
+    from cuda_mesh_voxelization_amd.slab import hybrid_window, transpose_plan
+    world = 4
+    xyz, tri = M.import_mesh(M.asset("bunny.obj"))
+    jobs = [(160, MULTI_TRANSPOSE), (96, MULTI_HYBRID), (128, MULTI_HALO), (64, MULTI_GHOST), (96, MULTI_GHOST), (160, MULTI_HYBRID)]
+    m = capi.Multi([0] * world)
+    try:
+        m.set_mesh(xyz, tri)
+        for n, mode in jobs:
+            origin, vs = M.frame([xyz], n)
+            fr = Frame.make(n, vs, origin)
+            ref_w, ref_s = _single(engine, fr, xyz, tri)
+            fresh = capi.Multi([0] * world)
+            try:
+                fresh.set_mesh(xyz, tri)
+                for mm in (m, fresh):
+                    mm.voxelize(fr)
+                    mm.jfa(mode=mode)
+                    assert np.array_equal(mm.get_grid().view(np.uint32), ref_w.view(np.uint32)), (n, mode, mm is fresh)
+                    assert np.array_equal(mm.get_sdf().view(np.uint32), ref_s.view(np.uint32)), (n, mode, mm is fresh)
+                nz = n // world
+                for r in range(world):
+                    lo, hi, nbytes = m.window(r)
+                    if n < 96 or mode == MULTI_GHOST:
+                        plan = (0, n)
+                    elif mode == MULTI_HALO:
+                        plan = (r * nz, (r + 1) * nz)
+                    elif mode == MULTI_HYBRID:
+                        plan = hybrid_window(n, r, world, engine.ctx.jfa_can_start_from_mask(fr))
+                    else:
+                        plan = transpose_plan(n, r, world)["window"]
+                    assert (lo, hi) == tuple(plan), (n, mode, r)
+                    assert (lo, hi, nbytes) == fresh.window(r), (n, mode, r)
+                    if n < 96:
+                        assert nbytes == 0, (n, mode, r)
+                    else:
+                        assert nbytes >= 2 * (hi - lo) * n * n * 4, (n, mode, r)
+            finally:
+                fresh.close()
+    finally:
+        m.close()
+        torch.cuda.empty_cache()
