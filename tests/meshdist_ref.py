@@ -5,11 +5,14 @@ mesh_distance_f32   the contract: brute force over all voxels x all triangles, e
 mesh_distance_f64   an independent float64 distance in another formulation: the minimum of the in-triangle plane projection and the three
                     segment distances.  Returns (dist2 unsigned float64, nearest, second-best dist2) without any band.
 Results are cached per argument bytes, computed once and handed out read-only."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
 F = np.float32
 NONE = 0xFFFFFFFF
-_CHUNK = 1 << 21            # (voxel, triangle) pairs per numpy pass
+_CHUNK = 1 << 18            # (voxel, triangle) pairs per numpy pass
 _cache = {}
 
 
@@ -103,6 +106,40 @@ def _key(*parts):
     return tuple(np.ascontiguousarray(x).tobytes() if isinstance(x, np.ndarray) else x for x in parts)
 
 
+def _nearest_f32(xyz, tri, n, vs, origin):
+    """(best float32[n^3], idx uint32[n^3]) over ALL valid triangles, no band: the smallest finite D2 of each voxel (inf without one) and
+    the lowest index that attains it.  A band only ever removes pairs with D2 >= B2, so the banded minimum and its first index follow from
+    these two; they are what every band and sign of one (mesh, frame) share, and are computed once.  Chunks of triangles run on a few
+    threads (numpy releases the GIL) and are merged in index order with a strict '<'."""
+    k = _key("nearest", xyz, tri, n, F(vs), origin)
+    if k in _cache:
+        return _cache[k]
+    P = centres(n, vs, origin)
+    V = P.shape[0]
+    best = np.full(V, np.inf, F)
+    idx = np.full(V, NONE, np.uint32)
+    keep = valid_triangles(xyz, tri)
+    step = max(1, _CHUNK // V)
+
+    def chunk(s):
+        t = keep[s:s + step]
+        vtx = xyz[tri[t].astype(np.int64)]
+        D = pair_d2_f32(P, vtx[:, 0], vtx[:, 1], vtx[:, 2])
+        with np.errstate(all="ignore"):
+            D = np.where(np.isfinite(D), D, F(np.inf))
+        return D.min(1), t[D.argmin(1)]                            # the first minimum of the chunk = its lowest index
+
+    with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))) as pool:
+        for m, am in pool.map(chunk, range(0, keep.size, step)):
+            up = m < best                                          # strict: an earlier (lower) index keeps a tie
+            best[up] = m[up]
+            idx[up] = am[up].astype(np.uint32)
+    best.setflags(write=False)
+    idx.setflags(write=False)
+    _cache[k] = (best, idx)
+    return _cache[k]
+
+
 def mesh_distance_f32(xyz, tri, n, vs, origin, band, sign_words=None):
     """(dist2 float32[n^3], nearest uint32[n^3]) of the contract; sign_words: + on set voxels, - on unset ones"""
     xyz = np.ascontiguousarray(xyz, F).reshape(-1, 3)
@@ -111,27 +148,12 @@ def mesh_distance_f32(xyz, tri, n, vs, origin, band, sign_words=None):
     k = _key("f32", xyz, tri, n, F(vs), origin, band, sign_words)
     if k in _cache:
         return _cache[k]
-    P = centres(n, vs, origin)
-    V = P.shape[0]
+    best, idx = _nearest_f32(xyz, tri, n, vs, origin)
+    V = best.shape[0]
     Bf = F(band) * F(vs)
     B2 = Bf * Bf
-    best = np.full(V, np.inf, F)
-    idx = np.full(V, NONE, np.uint32)
-    keep = valid_triangles(xyz, tri)
-    step = max(1, _CHUNK // V)
-    for s in range(0, keep.size, step):
-        t = keep[s:s + step]
-        vtx = xyz[tri[t].astype(np.int64)]
-        D = pair_d2_f32(P, vtx[:, 0], vtx[:, 1], vtx[:, 2])
-        with np.errstate(all="ignore"):
-            D = np.where(np.isfinite(D) & (D < B2), D, F(np.inf))
-        m = D.min(1)
-        am = t[D.argmin(1)]                                        # the first minimum of the chunk = its lowest index
-        up = m < best                                              # strict: an earlier (lower) index keeps a tie
-        best[up] = m[up]
-        idx[up] = am[up].astype(np.uint32)
     dist = np.where(best < B2, best, B2).astype(F)
-    idx[~(best < B2)] = NONE
+    idx = np.where(best < B2, idx, np.uint32(NONE)).astype(np.uint32)
     if sign_words is not None:
         bits = np.unpackbits(np.ascontiguousarray(sign_words, np.uint32).view(np.uint8), bitorder="little")[:V].astype(bool)
         dist = np.where(bits, dist, -dist).astype(F)

@@ -1,4 +1,7 @@
-"""Dev tool (GPU box): randomized parity campaign, many seeds of the families the GPU suite pins at fixed seeds.
+"""Dev tool (GPU box): randomized parity campaign over the families of inputs the GPU suite runs at fixed seeds.  The suite pins the INPUTS
+(soups, grids) and runs them in a handful of fixed frames: dyadic ones near the origin in tests/test_gpu_parity.py, where float32 is exact,
+and the rounding, far and collapsed frames of tests/float_frames.py in tests/test_float_frames_gpu.py.  This tool draws a random frame per
+seed -- voxel size 10^-2.5 .. 10^0.5, origin within +-10 per axis: frames that round, but none far from the origin; those are only in the suite.
   python tools/fuzz_parity.py [--seconds 600] [--seed0 1000]
 Per seed, one of
   soup   random triangle soup (size classes, slivers, snapped vertices, in-plane triangles, outside the frame): tiled and naive
