@@ -49,6 +49,14 @@
 //                            (include/vphip.h, vp_surfnets): one vertex per boundary cell, two triangles per exposed voxel face, closed,
 //                            after I = 0 .. 64 relaxation steps; a smooth mesh back from a repaired grid instead of cube faces.  Not with
 //                            --surface-only.  -t 0 / -t 3: host scan; -t 1 / -t 2: the device (n <= 1024), same bytes
+//         --iso-nets L[:I]   (extension, with -s and -e) out/iso_<type>_<output> holds the iso-surface nets of the distance field -s computed
+//                            (the Jump Flooding field, --exact-sdf or --mesh-sdf BAND; include/vphip.h, vp_isonets) at the level L VOXELS
+//                            (any finite decimal number; + is inside, so L > 0 shrinks and L < 0 grows the solid by a fraction of a voxel
+//                            where dilate:R / offset:R know whole voxels only), after I = 0 .. 64 relaxation steps (default 0): vertices at the
+//                            field's edge crossings, closed, "vn" per vertex from the field's gradient and faces "f a//a".  Not with
+//                            --surface-nets or --surface-only.  -t 0 / -t 3: host scan; -t 1 / -t 2: the device (n <= 1024), same bytes.
+//                            --mesh-sdf is signed by the solid grid's column rule, so its iso surface can sit up to half
+//                            a voxel off along x; the accuracy figures of DESIGN section 16 are for a sign taken at the voxel centres
 //     -h, --help
 #include <cmath>
 #include <cstdint>
@@ -98,6 +106,9 @@ struct Options {
     bool fill = false;
     bool exactSdf = false;
     int meshSdf = 0;                                        // --mesh-sdf BAND: band in voxels, 0 = not asked for
+    bool isoNets = false;                                   // --iso-nets LEVEL[:ITERS]: level in voxels, relaxation steps
+    float isoLevel = 0.0f;
+    unsigned isoIterations = 0;
     bool help = false;
     // op = VOX::MorphOp, 4 / 5: offset / inset (dilate / erode through the distance transform), or -1: the interior fill, -2: largest
     // component, -3: minsize (value = V); conn = 6 / 26 for the last two
@@ -205,6 +216,14 @@ const char* kUsage =
     "      --mesh-sdf BAND   With -s: the narrow-band squared distance to the triangles of the mesh itself, BAND = 1..32 voxels wide,\n"
     "                        signed by the solid grid of the run, instead of the Jump Flooding field between voxels.  One mesh,\n"
     "                        no CSG, one device (extension)\n"
+    "      --iso-nets arg    With -s and -e: write out/iso_<type>_<output>, the iso-surface nets of the distance field (the Jump\n"
+    "                        Flooding field, --exact-sdf or --mesh-sdf) at the level <arg> = LEVEL[:ITERS]: LEVEL in voxels, any finite\n"
+    "                        decimal number (+ is inside: 0.5 shrinks, -0.5 grows the solid by half a voxel), ITERS = 0..64 relaxation\n"
+    "                        steps (default 0).  Vertices sit at the field's edge crossings, the mesh is closed, every vertex has a\n"
+    "                        normal from the field's gradient (vn, faces f a//a).  Not together with --surface-nets or --surface-only;\n"
+    "                        one device; the GPU types serve n <= 1024.  --mesh-sdf is signed by the solid grid's column rule, so its\n"
+    "                        iso surface can sit up to half a voxel off along x; the accuracy figures of DESIGN section 16 are for a\n"
+    "                        sign taken at the voxel centres (extension)\n"
     "  -h, --help            Print usage\n";
 
 // Minimal getopt-style parser: -x V, -xV, --long V, --long=V, boolean switches, positionals.
@@ -212,7 +231,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -264,6 +283,19 @@ Options Parse(int argc, char** argv)
                 const bool digits = !value.empty() && value.size() <= 2 && value.find_first_not_of("0123456789") == std::string::npos;
                 cpuAssert(digits && std::stoi(value) <= 64, "--surface-nets: '" + value + "' is not a number of relaxation steps in 0..64\n");
                 o.surfaceNets = std::stoi(value);
+                break;
+            }
+            case 'I': {
+                // LEVEL[:ITERS]: a decimal number (strtod reads all of it, finite as a float), then 0 .. 64
+                const size_t colon = value.find(':');
+                const std::string level = value.substr(0, colon), iters = colon == std::string::npos ? "0" : value.substr(colon + 1);
+                char* end = nullptr;
+                const double lv = level.empty() ? 0.0 : std::strtod(level.c_str(), &end);
+                const bool levelOk = !level.empty() && end == level.c_str() + level.size() && level.find_first_not_of("+-.0123456789eE") == std::string::npos &&
+                                     std::isfinite(static_cast<float>(lv));
+                const bool itersOk = !iters.empty() && iters.size() <= 2 && iters.find_first_not_of("0123456789") == std::string::npos && std::stoi(iters) <= 64;
+                cpuAssert(levelOk && itersOk, "--iso-nets: '" + value + "' is not LEVEL[:ITERS] with a finite level in voxels and 0..64 relaxation steps\n");
+                o.isoNets = true; o.isoLevel = static_cast<float>(lv); o.isoIterations = static_cast<unsigned>(std::stoi(iters));
                 break;
             }
             case 'R': o.morph = ParseMorph(value); cpuAssert(!o.morph.empty(), "--morph needs a list\n"); break;
@@ -367,6 +399,9 @@ int main(int argc, char** argv)
               "--mesh-sdf needs a single mesh without CSG (and no -m): the field of a CSG result is not the field of any one mesh\n");
     cpuAssert(!(opt.surfaceNets >= 0 && opt.surfaceOnly), "--surface-nets and --surface-only exclude each other: one mesh per grid file\n");
     cpuAssert(!(opt.surfaceNets >= 0 && opt.gpus > 1), "--surface-nets runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.isoNets && !opt.sdf), "--iso-nets needs -s: it meshes the distance field\n");
+    cpuAssert(!(opt.isoNets && (opt.surfaceNets >= 0 || opt.surfaceOnly)), "--iso-nets excludes --surface-nets and --surface-only: one kind of surface per run\n");
+    cpuAssert(!(opt.isoNets && opt.gpus > 1), "--iso-nets runs on one device: -g must be 1\n");
     cpuAssert(opt.multi == "ghost" || opt.multi == "halo" || opt.multi == "hybrid" || opt.multi == "transpose", "--multi must be ghost, halo, hybrid or transpose");
     if (GPU && opt.gpus > 1) {
         // Z-slabs over devices 0 .. G-1.  VPLIB_SHARE_GPU=1 (test rigs with fewer devices than slabs): the slabs share the devices
@@ -494,6 +529,14 @@ int main(int argc, char** argv)
                 if (GPU) VoxelsGridToPointCloudDevice(grids[0].View(), sdf.View(), outMesh); else VoxelsGridToPointCloud(grids[0].View(), sdf.View(), outMesh);
                 cpuAssert(ExportMesh("out/sdf_point_cloud_" + typeName + "_" + opt.output, outMesh),
                           "Error in " + opt.output + " export (sdf)");
+                if (opt.isoNets) {
+                    // the field is in squared world units, + on set voxels: the signed-square transform, the level in world units
+                    const IsoFrame frame{originX, originY, originZ, voxelSize};
+                    const float iso = opt.isoLevel * voxelSize;
+                    if (GPU) IsoSurfaceNetsDevice(sdf.View(), frame, IsoTransform::SIGNED_SQUARE, iso, opt.isoIterations, TYPE == Types::NAIVE ? VP_ALGO_NAIVE : VP_ALGO_TILED, outMesh);
+                    else IsoSurfaceNets(sdf.View(), frame, IsoTransform::SIGNED_SQUARE, iso, opt.isoIterations, outMesh);
+                    cpuAssert(ExportMesh("out/iso_" + typeName + "_" + opt.output, outMesh), "Error in " + opt.output + " export (iso-nets)");
+                }
             }
         }
     }

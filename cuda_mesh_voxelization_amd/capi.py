@@ -17,6 +17,7 @@ MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3     # vp_morph: 
 EDT_SEEDS_SET, EDT_SEEDS_UNSET, EDT_SEEDS_BORDER = 0, 1, 2              # vp_edt: which voxels the distances are measured to
 EDT_NONE = 0xFFFFFFFF                                               # vp_edt: "the grid has no seed"
 MESH_NONE = 0xFFFFFFFF                                              # vp_mesh_distance: "no triangle within the band"
+ISO_LINEAR, ISO_SIGNED_SQUARE = 0, 1                                # vp_isonets: the field as it is / sign(v) sqrt|v| (every sdf of the library)
 CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
 COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
@@ -63,7 +64,7 @@ SYMBOLS = [
     "vp_fill_interior", "vp_fill_interior_host",
     "vp_morph", "vp_morph_host",
     "vp_components_label", "vp_components_sizes", "vp_components_filter", "vp_components_label_host", "vp_components_filter_host",
-    "vp_surfnets_count", "vp_surfnets", "vp_surfnets_host",
+    "vp_surfnets_count", "vp_surfnets", "vp_surfnets_host", "vp_isonets", "vp_isonets_result", "vp_isonets_host",
     "vp_edt", "vp_edt_sdf", "vp_edt_morph", "vp_edt_host", "vp_edt_sdf_host", "vp_edt_morph_host",
     "vp_mesh_distance", "vp_mesh_distance_host", "vp_mesh_distance_stats",
 ]
@@ -179,6 +180,12 @@ def lib():
         "vp_surfnets": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp, _sz, _sz]),
         "vp_surfnets_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _sz, _sz,
                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_isonets": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_isonets_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_isonets_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz,
+                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "vp_edt": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
         "vp_edt_sdf": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_float, _vp, ctypes.c_int]),
         "vp_edt_morph": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
@@ -498,6 +505,24 @@ class Context:
         check(lib().vp_surfnets(self._h, ctypes.byref(frame), _vp(d_words), algo, iterations, _vp(d_cells or None), _vp(d_xyz or None),
                                 _vp(d_quads or None), vertex_capacity, quad_capacity))
 
+    def isonets(self, frame: Frame, d_field: int, transform: int = ISO_SIGNED_SQUARE, iso: float = 0.0, iterations: int = 0,
+                normals: bool = False, algo: int = ALGO_TILED):
+        """Surface nets of a float field (n^3 values, x fastest) at level `iso`, built into buffers the context owns: (V, Q).  Blocking;
+        drops a pending surfnets_count.  isonets_result() hands the buffers out."""
+        nv, nq = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().vp_isonets(self._h, ctypes.byref(frame), _vp(d_field or None), transform, iso, iterations, 1 if normals else 0, algo,
+                               ctypes.byref(nv), ctypes.byref(nq)))
+        return int(nv.value), int(nq.value)
+
+    def isonets_result(self):
+        """(d_cells, d_xyz, d_normals, d_quads, V, Q) of the last isonets(): device pointers as ints, 0 where there is none.  Valid until
+        the next isonets(), release() or close()."""
+        c, x, m, q = _vp(), _vp(), _vp(), _vp()
+        nv, nq = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().vp_isonets_result(self._h, ctypes.byref(c), ctypes.byref(x), ctypes.byref(m), ctypes.byref(q), ctypes.byref(nv),
+                                      ctypes.byref(nq)))
+        return c.value or 0, x.value or 0, m.value or 0, q.value or 0, int(nv.value), int(nq.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
     def voxelize_host(self, frame: Frame, h_words, h_xyz, h_tri, algo: int = ALGO_TILED):
         check(lib().vp_voxelize_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp),
@@ -559,6 +584,21 @@ class Context:
                                      xyz.ctypes.data_as(_vp), quads.ctypes.data_as(_vp), cells.size, quads.shape[0],
                                      ctypes.byref(nv), ctypes.byref(nq)))
         return cells, xyz, quads
+
+    def isonets_host(self, frame: Frame, h_field, transform: int = ISO_SIGNED_SQUARE, iso: float = 0.0, iterations: int = 0,
+                     normals: bool = False, algo: int = ALGO_TILED, counts_only: bool = False):
+        """numpy in, numpy out: (cells uint64[V], xyz float32[V, 3], normals float32[V, 3] or None, quads uint32[Q, 4]), or (V, Q)."""
+        np = __import__("numpy")
+        nv, nq = ctypes.c_uint64(), ctypes.c_uint64()
+        head = (self._h, ctypes.byref(frame), h_field.ctypes.data_as(_vp), transform, iso, iterations, algo)
+        check(lib().vp_isonets_host(*head, None, None, None, None, 0, 0, ctypes.byref(nv), ctypes.byref(nq)))
+        if counts_only:
+            return int(nv.value), int(nq.value)
+        cells, xyz, quads = np.empty(nv.value, np.uint64), np.empty((nv.value, 3), np.float32), np.empty((nq.value, 4), np.uint32)
+        nrm = np.empty((nv.value, 3), np.float32) if normals else None
+        check(lib().vp_isonets_host(*head, cells.ctypes.data_as(_vp), xyz.ctypes.data_as(_vp), nrm.ctypes.data_as(_vp) if normals else None,
+                                    quads.ctypes.data_as(_vp), cells.size, quads.shape[0], ctypes.byref(nv), ctypes.byref(nq)))
+        return cells, xyz, nrm, quads
 
     def csg_host(self, h_a, h_b, op: int):
         check(lib().vp_csg_host(self._h, h_a.ctypes.data_as(_vp), h_b.ctypes.data_as(_vp), h_a.size, op))

@@ -211,7 +211,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
                        &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp,
                        &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small,
                        &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz, &ctx->edt_mask, &ctx->edt_vol, &ctx->edt_vol2, &ctx->edt_tmp,
-                       &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list };
+                       &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list,
+                       &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -300,6 +301,9 @@ int vp_ctx_release(vp_ctx* ctx)
     release(ctx->edt_vol2);
     release(ctx->edt_tmp);
     for (Buffer* b : { &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list }) release(*b);   // vp_mesh_distance
+    for (Buffer* b : { &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads }) release(*b);      // vp_isonets: scratch and result
+    ctx->iso_vertices = ctx->iso_quad_count = 0;
+    ctx->iso_has_normals = false;
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -1090,6 +1094,48 @@ int vp_surfnets(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int alg
     return launch_surfnets_write(ctx, f->n, d_words, algo, iterations, d_cells, d_xyz, d_quads);
 }
 
+// ---- iso-surface nets --------------------------------------------------------------------------
+static int check_isonets(const vp_frame* f, const char* who, int transform, float iso, uint32_t iterations, int algo)
+{
+    VP_TRY(check_surfnets(f, who));
+    if (transform != VP_ISO_LINEAR && transform != VP_ISO_SIGNED_SQUARE) return set_error(VP_ERR_INVALID, "%s: unknown transform %d", who, transform);
+    VP_TRY(check_algo(who, algo));
+    if (!std::isfinite(iso)) return set_error(VP_ERR_INVALID, "%s: iso must be finite", who);
+    if (iterations > 64) return set_error(VP_ERR_INVALID, "%s: %u iterations (0 .. 64)", who, iterations);
+    return 0;
+}
+
+int vp_isonets(vp_ctx* ctx, const vp_frame* f, const float* d_field, int transform, float iso, uint32_t iterations, int want_normals,
+               int algo, uint64_t* h_vertices, uint64_t* h_quads)
+{
+    const char* who = "vp_isonets";
+    if (!ctx || !f || !d_field) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_isonets(f, who, transform, iso, iterations, algo));
+    VP_TRY(check_aligned(who, {d_field}));
+    const int rc = launch_isonets(ctx, f->n, d_field, transform, iso, iterations, want_normals != 0, algo);
+    // the context's own buffers are outputs like any other: whatever was recorded about their bytes is gone
+    for (Buffer* b : { &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads }) grid_written(ctx, b->ptr, b->bytes);
+    VP_TRY(rc);
+    if (h_vertices) *h_vertices = ctx->iso_vertices;
+    if (h_quads) *h_quads = ctx->iso_quad_count;
+    return 0;
+}
+
+int vp_isonets_result(vp_ctx* ctx, uint64_t** d_cells, float** d_xyz, float** d_normals, uint32_t** d_quads, uint64_t* h_vertices,
+                      uint64_t* h_quads)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_isonets_result: null ctx");
+    const bool any = ctx->iso_vertices != 0;                       // no vertex, hence no quad
+    if (d_cells) *d_cells = any ? (uint64_t*)ctx->iso_cells.ptr : nullptr;
+    if (d_xyz) *d_xyz = any ? (float*)ctx->iso_xyz.ptr : nullptr;
+    if (d_normals) *d_normals = any && ctx->iso_has_normals ? (float*)ctx->iso_normals.ptr : nullptr;
+    if (d_quads) *d_quads = any ? (uint32_t*)ctx->iso_quads.ptr : nullptr;
+    if (h_vertices) *h_vertices = ctx->iso_vertices;
+    if (h_quads) *h_quads = ctx->iso_quad_count;
+    return 0;
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1242,6 +1288,34 @@ int vp_surfnets_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, ui
         VP_TRY(vp_download(ctx, h_cells, dc, nv * 8));
         VP_TRY(vp_download(ctx, h_xyz, dx, nv * 12));
         VP_TRY(vp_download(ctx, h_quads, dq, nq * 16));
+    }
+    *h_vertices = nv; *h_quads_out = nq;
+    return 0;
+}
+
+int vp_isonets_host(vp_ctx* ctx, const vp_frame* f, const float* h_field, int transform, float iso, uint32_t iterations, int algo,
+                    uint64_t* h_cells, float* h_xyz, float* h_normals, uint32_t* h_quads, size_t vertex_capacity, size_t quad_capacity,
+                    uint64_t* h_vertices, uint64_t* h_quads_out)
+{
+    const char* who = "vp_isonets_host";
+    if (!ctx || !f || !h_field || !h_vertices || !h_quads_out) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_isonets(f, who, transform, iso, iterations, algo));
+    const bool counts_only = !h_cells && !h_xyz && !h_normals && !h_quads;
+    if (!counts_only && (!h_cells || !h_xyz || !h_quads)) return set_error(VP_ERR_INVALID, "%s: records, positions and quads go together", who);
+    void* df = nullptr;
+    const size_t fb = vp_grid_voxels(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, fb, &df));
+    VP_TRY(vp_upload(ctx, df, h_field, fb));
+    uint64_t nv = 0, nq = 0;
+    VP_TRY(vp_isonets(ctx, f, (const float*)df, transform, iso, iterations, h_normals != nullptr, algo, &nv, &nq));
+    if (!counts_only && (vertex_capacity < nv || quad_capacity < nq))
+        return set_error(VP_ERR_INVALID, "%s: capacity %zu vertices / %zu quads, the field has %llu / %llu", who, vertex_capacity, quad_capacity,
+                         (unsigned long long)nv, (unsigned long long)nq);
+    if (!counts_only && nv) {
+        VP_TRY(vp_download(ctx, h_cells, ctx->iso_cells.ptr, nv * 8));
+        VP_TRY(vp_download(ctx, h_xyz, ctx->iso_xyz.ptr, nv * 12));
+        if (h_normals) VP_TRY(vp_download(ctx, h_normals, ctx->iso_normals.ptr, nv * 12));
+        VP_TRY(vp_download(ctx, h_quads, ctx->iso_quads.ptr, nq * 16));
     }
     *h_vertices = nv; *h_quads_out = nq;
     return 0;

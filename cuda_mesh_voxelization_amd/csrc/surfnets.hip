@@ -346,7 +346,7 @@ int launch_surfnets_count(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int 
 }
 
 int launch_surfnets_write(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int algo, uint32_t iterations, uint64_t* d_cells, float* d_xyz,
-                          uint32_t* d_quads)
+                          uint32_t* d_quads, const IsoField* iso)
 {
     const Dim d = make_dim(n);
     const size_t units = unit_count(d, algo);
@@ -373,6 +373,7 @@ int launch_surfnets_write(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int 
             hipLaunchKernelGGL(sn_verts_tiled, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, d, d_words, (uint32_t)units, off_v, prefix,
                                (unsigned long long*)d_cells, cur, nv);
     }
+    if (iso) VP_TRY(launch_iso_place(ctx, n, algo, *iso, d_cells, rank0, cur, nv));      // vp_isonets: positions from the field, not the bits
     {
         ProfScope p(ctx, naive ? VP_K_SN_QUADS_NAIVE : VP_K_SN_QUADS);
         if (naive)

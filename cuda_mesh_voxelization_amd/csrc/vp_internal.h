@@ -119,6 +119,11 @@ struct vp_ctx {
     std::vector<hipEvent_t> prof_pool;
     double prof_ms[VP_K_ALL] = {};
     uint64_t prof_n[VP_K_ALL] = {};
+    // iso-surface nets (isonets.hip): the inside grid of the field (n^3 / 8 bytes) and the mesh of the last vp_isonets, which the context
+    // owns and vp_isonets_result hands out -- records, positions, normals (if asked for), quads; all five are freed by vp_ctx_release
+    vp::Buffer iso_words, iso_cells, iso_xyz, iso_normals, iso_quads;
+    uint64_t iso_vertices = 0, iso_quad_count = 0;
+    bool iso_has_normals = false;
 };
 
 namespace vp {
@@ -197,8 +202,14 @@ int launch_components_filter(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, u
 // surfnets.hip: count (blocking: V and Q go to the host) and write (vertices, quads, `iterations` relaxation steps; enqueues only, once the
 // context's buffers have grown) of the surface-nets mesh of a whole grid
 int launch_surfnets_count(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int algo, uint64_t* h_vertices, uint64_t* h_quads);
+// iso != nullptr: d_words is the inside grid of that field; launch_iso_place replaces the starting positions before the relaxation
+struct IsoField { const float* d_field; int transform; float iso; float* d_normals; };
 int launch_surfnets_write(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int algo, uint32_t iterations, uint64_t* d_cells, float* d_xyz,
-                          uint32_t* d_quads);
+                          uint32_t* d_quads, const IsoField* iso = nullptr);
+// isonets.hip: surface nets of a scalar field at an iso level into the context's own buffers (blocking), and its placement pass
+int launch_isonets(vp_ctx* ctx, uint32_t n, const float* d_field, int transform, float iso, uint32_t iterations, bool want_normals, int algo);
+int launch_iso_place(vp_ctx* ctx, uint32_t n, int algo, const IsoField& iso, const uint64_t* d_cells, const uint32_t* index, float* d_xyz,
+                     size_t nverts);
 int launch_csg(vp_ctx* ctx, uint32_t* d_a, const uint32_t* d_b, size_t nwords, int op);
 int launch_stream_copy(vp_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);   // 16 B per lane: the measured HBM copy rate
 // jfa_seed.hip

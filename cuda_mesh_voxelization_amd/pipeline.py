@@ -151,6 +151,26 @@ class Engine:
                           quads.data_ptr() if nq else 0, nv, nq)
         return cells, xyz, quads
 
+    def iso_nets(self, frame: Frame, field, iso: float = 0.0, transform: int = capi.ISO_SIGNED_SQUARE, iterations: int = 0,
+                 normals: bool = False, algo: int = ALGO_TILED):
+        """Surface nets of a float32 field tensor (n^3 values, x fastest; n <= 1024) at level `iso`: vertices at the field's edge crossings,
+        the topology of surface_nets() on the inside set {h >= +0}, h = field - iso (capi.ISO_LINEAR) or sign(field) sqrt|field| - iso
+        (capi.ISO_SIGNED_SQUARE, the convention of jfa() / edt_sdf() / mesh_distance()).  Returns (cells int64[V], xyz float32[V, 3],
+        normals float32[V, 3] or None, quads int32[Q, 4]): tensors of the caller, copied out of the context's buffers.  Blocking."""
+        nv, nq = self.ctx.isonets(frame, field.data_ptr(), transform, iso, iterations, normals, algo)
+        dc, dx, dn, dq, _, _ = self.ctx.isonets_result()
+        cells = torch.empty(nv, dtype=torch.int64, device=self.device)
+        xyz = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+        nrm = torch.empty((nv, 3), dtype=torch.float32, device=self.device) if normals else None
+        quads = torch.empty((nq, 4), dtype=torch.int32, device=self.device)
+        if nv:
+            self.ctx.memcpy_d2d(cells.data_ptr(), dc, nv * 8)
+            self.ctx.memcpy_d2d(xyz.data_ptr(), dx, nv * 12)
+            if normals:
+                self.ctx.memcpy_d2d(nrm.data_ptr(), dn, nv * 12)
+            self.ctx.memcpy_d2d(quads.data_ptr(), dq, nq * 16)
+        return cells, xyz, nrm, quads
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

@@ -55,5 +55,26 @@ template <VGType T> void SurfaceNetsLattice(const VoxelsGrid<T>& grid, uint32_t 
 template <VGType T> void SurfaceNetsLatticeDevice(const VoxelsGrid<T>& grid, uint32_t iterations, SurfaceNets& out);
 template <VGType T> bool VoxelsGridToSurfaceNets(const VoxelsGrid<T>& grid, uint32_t iterations, Mesh& mesh);
 template <VGType T> bool VoxelsGridToSurfaceNetsDevice(const VoxelsGrid<T>& grid, uint32_t iterations, Mesh& mesh);
+// host scan, second half: the quads (by owner cell, then axis) from the vertex-index volume of the (n+1)^3 cells, then `iterations` relaxation
+// steps on out.Xyz; out.Cells and out.Xyz hold the records and the starting positions
+void SurfaceNetsFinishHost(int64_t n, uint32_t iterations, const std::vector<uint32_t>& index, SurfaceNets& out);
+
+// Iso-surface nets (include/vphip.h, vp_isonets*): the surface-nets mesh of the inside set {h >= +0} of a float field, h = g - iso, with the
+// vertices at the field's edge crossings and normals from its gradient.  `field` holds n^3 values at the voxel centres, x fastest.
+//   IsoTransform::LINEAR          g = v
+//   IsoTransform::SIGNED_SQUARE   g = copysign(sqrt(|v|), v): every sdf of this library (JFA::Compute, JFA::ComputeExact, VOX::MeshDistance)
+// IsoSurfaceNetsLattice is the host restatement -- a straight scan over the cells, any n; the Device form goes through vp_isonets_host
+// (n % 32 == 0, n <= 1024; algo = VP_ALGO_NAIVE or VP_ALGO_TILED) and produces the same bytes.  IsoSurfaceNets emits the world mesh:
+// vertices origin + (p * voxel size), triangles (a, b, c) and (a, c, d) per quad, one normal per vertex (faces "f a//a" in the OBJ).
+enum class IsoTransform : int { LINEAR = 0, SIGNED_SQUARE = 1 };
+struct IsoNets : SurfaceNets {
+    std::vector<float> Normals;       // 3 V, of the unrelaxed cells; zero where the cell has a corner outside the grid
+};
+struct IsoFrame { float OriginX = 0.0f, OriginY = 0.0f, OriginZ = 0.0f, VoxelSize = 1.0f; };
+void IsoSurfaceNetsLattice(const Grid<float>& field, IsoTransform transform, float iso, uint32_t iterations, IsoNets& out);
+void IsoSurfaceNetsLatticeDevice(const Grid<float>& field, IsoTransform transform, float iso, uint32_t iterations, int algo, IsoNets& out);
+bool IsoSurfaceNets(const Grid<float>& field, const IsoFrame& frame, IsoTransform transform, float iso, uint32_t iterations, Mesh& mesh);
+bool IsoSurfaceNetsDevice(const Grid<float>& field, const IsoFrame& frame, IsoTransform transform, float iso, uint32_t iterations, int algo,
+                          Mesh& mesh);
 
 #endif

@@ -49,45 +49,7 @@ void HostLattice(const VoxelsGrid<T>& grid, uint32_t iterations, SurfaceNets& ou
                 for (int a = 0; a < 3; ++a)
                     out.Xyz.push_back((static_cast<float>(c3[a]) + 0.5f) + static_cast<float>(s[a]) / static_cast<float>(2 * m));
             }
-    // quads, by owner cell (= vertex order), then axis
-    // offsets, in the linear cell index, of the four cells around an owned x-, y- or z-edge, in the contract's order
-    const int64_t s1 = n1, s2 = n1 * n1;
-    const int64_t around[3][4] = {{-s1 - s2, -s2, 0, -s1}, {-1 - s2, -1, 0, -s2}, {-1 - s1, -s1, 0, -1}};
-    for (const uint64_t rec : out.Cells) {
-        const int64_t cell = static_cast<int64_t>(rec & kCellMask);
-        const unsigned mask = static_cast<unsigned>(rec >> 40);
-        for (int axis = 0; axis < 3; ++axis) {
-            if ((mask & 1u) == ((mask >> (1 << axis)) & 1u)) continue;      // corner 0 against corner 1, 2, 4
-            const bool lower = (mask & 1u) != 0u;                           // the lower voxel is the set one: normal along + axis
-            for (int t = 0; t < 4; ++t) out.Quads.push_back(index[static_cast<size_t>(cell + around[axis][lower ? t : 3 - t])]);
-        }
-    }
-    // relaxation
-    const size_t V = out.Cells.size();
-    std::vector<float> other(iterations ? out.Xyz.size() : 0);
-    const int64_t nstep[6] = {-1, 1, -n1, n1, -n1 * n1, n1 * n1};
-    for (uint32_t it = 0; it < iterations; ++it) {
-        for (size_t i = 0; i < V; ++i) {
-            const int64_t cell = static_cast<int64_t>(out.Cells[i] & kCellMask);
-            const unsigned mask = static_cast<unsigned>(out.Cells[i] >> 40);
-            const int64_t c3[3] = {cell % n1 - 1, (cell / n1) % n1 - 1, cell / (n1 * n1) - 1};
-            float acc[3] = {0.0f, 0.0f, 0.0f};
-            int deg = 0;
-            for (int f = 0; f < 6; ++f) {
-                const unsigned m = mask & kFaces[f];
-                if (m == 0u || m == kFaces[f]) continue;
-                const float* p = &out.Xyz[3 * static_cast<size_t>(index[static_cast<size_t>(cell + nstep[f])])];
-                for (int a = 0; a < 3; ++a) acc[a] = deg == 0 ? p[a] : acc[a] + p[a];
-                ++deg;
-            }
-            for (int a = 0; a < 3; ++a) {
-                const float q = acc[a] / static_cast<float>(deg);
-                const float lo = static_cast<float>(c3[a]) + 0.5625f, hi = static_cast<float>(c3[a]) + 1.4375f;
-                other[3 * i + a] = std::min(std::max(q, lo), hi);
-            }
-        }
-        out.Xyz.swap(other);
-    }
+    SurfaceNetsFinishHost(n, iterations, index, out);
 }
 
 template <VGType T>
@@ -135,6 +97,52 @@ void Emit(const VoxelsGrid<T>& grid, const SurfaceNets& sn, Mesh& mesh)
 }
 
 }  // namespace
+
+// the part of the host scan that knows the inside set only through the records: quads from the index volume, then the relaxation.  Shared
+// with the iso-surface nets (iso_nets.cpp), whose records come from a field.
+void SurfaceNetsFinishHost(int64_t n, uint32_t iterations, const std::vector<uint32_t>& index, SurfaceNets& out)
+{
+    const int64_t n1 = n + 1;
+    // quads, by owner cell (= vertex order), then axis
+    // offsets, in the linear cell index, of the four cells around an owned x-, y- or z-edge, in the contract's order
+    const int64_t s1 = n1, s2 = n1 * n1;
+    const int64_t around[3][4] = {{-s1 - s2, -s2, 0, -s1}, {-1 - s2, -1, 0, -s2}, {-1 - s1, -s1, 0, -1}};
+    for (const uint64_t rec : out.Cells) {
+        const int64_t cell = static_cast<int64_t>(rec & kCellMask);
+        const unsigned mask = static_cast<unsigned>(rec >> 40);
+        for (int axis = 0; axis < 3; ++axis) {
+            if ((mask & 1u) == ((mask >> (1 << axis)) & 1u)) continue;      // corner 0 against corner 1, 2, 4
+            const bool lower = (mask & 1u) != 0u;                           // the lower voxel is the set one: normal along + axis
+            for (int t = 0; t < 4; ++t) out.Quads.push_back(index[static_cast<size_t>(cell + around[axis][lower ? t : 3 - t])]);
+        }
+    }
+    // relaxation
+    const size_t V = out.Cells.size();
+    std::vector<float> other(iterations ? out.Xyz.size() : 0);
+    const int64_t nstep[6] = {-1, 1, -n1, n1, -n1 * n1, n1 * n1};
+    for (uint32_t it = 0; it < iterations; ++it) {
+        for (size_t i = 0; i < V; ++i) {
+            const int64_t cell = static_cast<int64_t>(out.Cells[i] & kCellMask);
+            const unsigned mask = static_cast<unsigned>(out.Cells[i] >> 40);
+            const int64_t c3[3] = {cell % n1 - 1, (cell / n1) % n1 - 1, cell / (n1 * n1) - 1};
+            float acc[3] = {0.0f, 0.0f, 0.0f};
+            int deg = 0;
+            for (int f = 0; f < 6; ++f) {
+                const unsigned m = mask & kFaces[f];
+                if (m == 0u || m == kFaces[f]) continue;
+                const float* p = &out.Xyz[3 * static_cast<size_t>(index[static_cast<size_t>(cell + nstep[f])])];
+                for (int a = 0; a < 3; ++a) acc[a] = deg == 0 ? p[a] : acc[a] + p[a];
+                ++deg;
+            }
+            for (int a = 0; a < 3; ++a) {
+                const float q = acc[a] / static_cast<float>(deg);
+                const float lo = static_cast<float>(c3[a]) + 0.5625f, hi = static_cast<float>(c3[a]) + 1.4375f;
+                other[3 * i + a] = std::min(std::max(q, lo), hi);
+            }
+        }
+        out.Xyz.swap(other);
+    }
+}
 
 template <VGType T> void SurfaceNetsLattice(const VoxelsGrid<T>& grid, uint32_t iterations, SurfaceNets& out) { HostLattice(grid, iterations, out); }
 template <VGType T> void SurfaceNetsLatticeDevice(const VoxelsGrid<T>& grid, uint32_t iterations, SurfaceNets& out) { DeviceLattice(grid, iterations, out); }

@@ -346,6 +346,64 @@ int vp_surfnets_count(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, i
 int vp_surfnets(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint32_t iterations, uint64_t* d_cells, float* d_xyz,
                 uint32_t* d_quads, size_t vertex_capacity, size_t quad_capacity);
 
+/* ---- iso-surface nets: surface nets of a scalar field at an iso level (no reference counterpart) ----------------
+ * The mesh of the surface-nets section above, taken from a float field instead of a bit grid: vertices are placed by the field's edge
+ * crossings (sub-voxel), normals come from its gradient.  Lattice coordinates, cells, corner masks, the record cell index | mask << 40,
+ * vertex order, quad ownership, order and winding, and the relaxation are EXACTLY those of the surface-nets section, applied to the
+ * INSIDE set defined below: the topology is that of a bit grid, so the mesh is always closed.  Only "inside", the starting positions
+ * and the normals are new.  Everything is float32; every operation written is one correctly rounded IEEE operation, in the association
+ * written, without contraction.
+ * Value.  d_field: n^3 floats, x fastest, the value v at each voxel centre.  transform = VP_ISO_LINEAR: g = v.  transform =
+ * VP_ISO_SIGNED_SQUARE: g = copysignf(sqrtf(fabsf(v)), v) -- the convention of every sdf of this library (squared world units, + on set
+ * voxels).  h = g - iso, one subtraction; iso must be finite.  A voxel outside the grid has h = NaN.
+ * Inside.  A voxel is inside iff the bit pattern of h, read as uint32, is <= 0x7F800000: +0 .. +inf.  -0, negatives and every NaN are
+ * outside.  So at iso 0 a field signed by a grid (+0.0f on set border voxels, -0.0f on unset ones) has exactly that grid as its inside set.
+ * Position.  The twelve edges of a cell are visited by axis x, y, z and per axis by the lower corners c = 0 .. 7 that have the axis bit
+ * clear, ascending.  For a crossing edge (its ends differ in "inside") with lower corner c and upper corner d:  t = h[c] / (h[c] - h[d]);
+ * if !(t >= 0 && t <= 1) then t = 0.5f (0/0, inf/inf, corners outside the grid).  The edge's point has coordinate t on its own axis and
+ * (float)((c >> a) & 1) on the other two.  Per component a: acc starts at +0.0f, the points of the crossing edges are added left to
+ * right; q = acc / (float)m with m the number of crossing edges; p_a = ((float)c_a + 0.5f) + q.  Every component lies in the closed
+ * interval [c_a + 0.5, c_a + 1.5].
+ * Normals (optional).  With h0 .. h7 the corner values:
+ *     G_x = ((h1-h0) + (h3-h2)) + ((h5-h4) + (h7-h6))
+ *     G_y = ((h2-h0) + (h3-h1)) + ((h6-h4) + (h7-h5))
+ *     G_z = ((h4-h0) + (h5-h1)) + ((h6-h2) + (h7-h3))
+ * L2 = (G_x G_x + G_y G_y) + G_z G_z.  If !(L2 > 0) or L2 is infinite the normal is (0, 0, 0) -- every cell with a corner outside the grid
+ * is such a cell.  Otherwise L = sqrtf(L2) and N_a = (-G_a) / L: inside is positive, so -G points outward.  Normals belong to the
+ * unrelaxed cell; the relaxation does not change them.
+ * Relaxation.  iterations = 0 .. 64 Jacobi steps of the surface-nets section, unchanged, with the same clamp; they start from the
+ * positions above.
+ * Degenerate facts.  A field that is +0.0f on the set and -0.0f on the unset voxels of a grid (or +inf / -inf likewise) gives, at iso 0,
+ * the BYTES of the surface nets of that grid for records, positions and quads: every t is 0.5 and every sum is exact.  A single inside
+ * voxel with h = +1 among h = -3 gives 8 vertices: every crossing lies 1/4 of an edge from the voxel, so each vertex sits (1/4 + 0 + 0) / 3 = 1/12 from the voxel centre
+ * per axis, where the bit grid puts it at 1/6.
+ *   vp_isonets          builds the whole mesh into grow-only buffers that the CONTEXT owns: records (8 V bytes), positions (12 V),
+ *                       normals (12 V, only if want_normals != 0) and quads (16 Q).  BLOCKING: V and Q are read back and returned
+ *                       (h_vertices / h_quads may be NULL).  The buffers stay valid until the next vp_isonets, vp_ctx_release or
+ *                       vp_ctx_destroy.  Scratch (rank lookup, second position buffer) is shared with the surface-nets calls, so the
+ *                       call DROPS a pending surface-nets count, as a second count would: the write call that follows is refused
+ *                       with VP_ERR_INVALID and never served from overwritten scratch.
+ *   vp_isonets_result   pointers and counts of the last build; any argument may be NULL.  Before any build, after a release and after a
+ *                       build that failed half way: V = Q = 0 and NULL pointers.  *d_normals is NULL when the build did not ask for normals.
+ *   vp_isonets_host     host in, host out, with the convention of the surface-nets host call: all four outputs NULL = counts only; a
+ *                       capacity below V / Q: VP_ERR_INVALID (found after the build: the context then holds the new mesh); h_normals alone may be
+ *                       NULL.  The field is staged through a workspace slot.
+ * Whole-grid frames only: a slab frame and n > 1024 return VP_ERR_UNSUPPORTED.  Null ctx / f / d_field, a field that is not 16-byte
+ * aligned, an unknown transform or algo, a non-finite iso and iterations > 64: VP_ERR_INVALID.  A refusal leaves the previous result and
+ * its counts as they were.
+ *   algo: VP_ALGO_TILED -- the field is streamed once into the inside grid (one ballot = 64 bits), the surface-nets launches run on that
+ *   grid, then one lane per vertex gathers its eight corner values and recomputes h (no n^3 float volume is kept); VP_ALGO_NAIVE -- one
+ *   thread per 32 voxels classifies them one by one, and one thread per cell places its vertex from its own eight field values through
+ *   the index volume.  Same bytes.  Timing: classification books under VP_K_SN_CELLS(_NAIVE), placement under VP_K_SN_VERTS(_NAIVE). */
+enum { VP_ISO_LINEAR = 0, VP_ISO_SIGNED_SQUARE = 1 };
+int vp_isonets(vp_ctx* ctx, const vp_frame* f, const float* d_field, int transform, float iso, uint32_t iterations,
+               int want_normals, int algo, uint64_t* h_vertices, uint64_t* h_quads);
+int vp_isonets_result(vp_ctx* ctx, uint64_t** d_cells, float** d_xyz, float** d_normals, uint32_t** d_quads,
+                      uint64_t* h_vertices, uint64_t* h_quads);
+int vp_isonets_host(vp_ctx* ctx, const vp_frame* f, const float* h_field, int transform, float iso, uint32_t iterations, int algo,
+                    uint64_t* h_cells, float* h_xyz, float* h_normals, uint32_t* h_quads, size_t vertex_capacity, size_t quad_capacity,
+                    uint64_t* h_vertices, uint64_t* h_quads_out);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
