@@ -22,6 +22,11 @@
 //                            a voxel is set iff its closed box overlaps a triangle (include/vphip.h, vp_voxelize_conservative) -- a
 //                            correct grid for open meshes and triangle soups, where the solid rule streaks; -p, -e, --surface-only,
 //                            -s, -m and -d work on it unchanged.  One device only (-g > 1 is refused)
+//         --winding [L[:B]]  (extension) replace the voxelization of every input mesh by the solid of its generalized winding number: a
+//                            voxel is set iff w(centre) >= L (include/vphip.h, vp_winding; default 0.5:2) -- exact at the voxel centre
+//                            for a closed mesh, and a sensible solid for an open mesh, a soup or overlapping shells (L = 1.5: where two
+//                            shells overlap).  B = 0 sums every triangle, 1..64 opens the far field.  --morph, --fill, CSG, -e and -s run
+//                            on its grids unchanged, and --mesh-sdf is then signed by it
 //         --fill             (extension) after each mesh's voxelization (solid or --conservative), fill its interior: every empty voxel
 //                            that no 6-connected path of empty voxels joins to the grid boundary is set (include/vphip.h,
 //                            vp_fill_interior).  Runs before export, CSG and sdf, so --conservative --fill gives the solid of an open
@@ -103,6 +108,8 @@ struct Options {
     bool surfaceOnly = false;
     int surfaceNets = -1;                                   // --surface-nets ITERS: relaxation steps, -1 = not asked for
     bool conservative = false;
+    bool winding = false;                                   // --winding [LEVEL[:BETA]]: solid from the generalized winding number
+    float windingLevel = 0.5f, windingBeta = 2.0f;
     bool fill = false;
     bool exactSdf = false;
     int meshSdf = 0;                                        // --mesh-sdf BAND: band in voxels, 0 = not asked for
@@ -193,6 +200,9 @@ const char* kUsage =
     "                        while every vertex stays inside its cell.  Not together with --surface-only; the GPU types serve n <= 1024\n"
     "      --verify          With -g > 1: run the job again on device 0 alone, compare grid and sdf bit for bit, print\n"
     "                        '# multi-gpu' lines (parity, bytes moved between devices); exit code 3 on a mismatch (extension)\n"
+    "      --winding [arg]   Solid voxelization by the generalized winding number: a voxel is set iff w(centre) >= LEVEL; arg =\n"
+    "                        LEVEL[:BETA], default 0.5:2 (BETA 0: every triangle exactly, 1..64: far field).  Any mesh: closed, open,\n"
+    "                        soups, overlapping shells; the sign --mesh-sdf then uses is exact at the voxel centres (extension)\n"
     "      --conservative    Surface voxelization: a voxel is set iff its closed box overlaps a triangle (any mesh, open or\n"
     "                        closed; the default solid rule needs closed meshes); CSG, export, sdf and dumps work on it unchanged.\n"
     "                        One device only: not with -g > 1 (extension)\n"
@@ -231,7 +241,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -250,6 +260,26 @@ Options Parse(int argc, char** argv)
             if (a.size() > 2) { value = a.substr(2); hasValue = true; }
         } else {
             o.filenames.push_back(a);
+            continue;
+        }
+        if (key == 'W') {
+            // the value is optional: the next argument is taken only if it reads as LEVEL[:BETA] -- strtod consumes all of a non-empty
+            // LEVEL that holds a digit, and what follows the colon is made of the characters of a number.  "-e", "-s", "-" are flags.
+            o.winding = true;
+            std::string v = hasValue ? value : (i + 1 < argc ? std::string(argv[i + 1]) : std::string());
+            const size_t colon = v.find(':');
+            const std::string level = v.substr(0, colon), beta = colon == std::string::npos ? "2" : v.substr(colon + 1);
+            char *e1 = nullptr, *e2 = nullptr;
+            const double lv = std::strtod(level.c_str(), &e1);
+            const bool looks = level.find_first_of("0123456789") != std::string::npos && level.find_first_not_of("+-.0123456789eE") == std::string::npos &&
+                               e1 == level.c_str() + level.size() && beta.find_first_not_of("+-.0123456789eE") == std::string::npos;
+            if (!hasValue && !looks) continue;
+            if (!hasValue) ++i;
+            const double bt = std::strtod(beta.c_str(), &e2);
+            const bool ok = looks && !beta.empty() && e2 == beta.c_str() + beta.size() && std::isfinite(static_cast<float>(lv)) &&
+                            (bt == 0.0 || (bt >= 1.0 && bt <= 64.0));
+            cpuAssert(ok, "--winding: '" + v + "' is not LEVEL[:BETA] with a finite level and beta 0 or 1..64\n");
+            o.windingLevel = static_cast<float>(lv); o.windingBeta = static_cast<float>(bt);
             continue;
         }
         const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X';
@@ -316,6 +346,12 @@ template <Types T>
 void VoxelizeConservative(unsigned blockSize, HostVoxelsGrid<gridType>& grid, const Mesh& mesh)
 {
     VOX::ComputeConservative<T>(blockSize, grid, mesh);
+}
+
+template <Types T>
+void VoxelizeWinding(float level, float beta, HostVoxelsGrid<gridType>& grid, const Mesh& mesh)
+{
+    VOX::ComputeWinding<T>(grid, mesh, level, beta);
 }
 
 template <Types T>
@@ -388,6 +424,8 @@ int main(int argc, char** argv)
     const bool GPU = TYPE == Types::NAIVE || TYPE == Types::TILED;      // exports: the walk over the grid runs on the device too
     cpuAssert(opt.gpus >= 1 && opt.gpus <= 64, "Number of GPUs must be 1..64");
     cpuAssert(!(opt.conservative && opt.gpus > 1), "--conservative runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.winding && opt.conservative), "--winding and --conservative exclude each other: one voxelization per mesh\n");
+    cpuAssert(!(opt.winding && opt.gpus > 1), "--winding runs on one device: -g must be 1\n");
     cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
     cpuAssert(!(opt.exactSdf && !opt.sdf), "--exact-sdf needs -s: it chooses how the distance field is computed\n");
@@ -444,7 +482,14 @@ int main(int argc, char** argv)
             HostVoxelsGrid<gridType>& grid = grids[i];
             grid = HostVoxelsGrid<gridType>(N, voxelSize);
             grid.View().SetOrigin(originX, originY, originZ);
-            if (opt.conservative) {
+            if (opt.winding) {
+                switch (TYPE) {
+                    case Types::SEQUENTIAL: VoxelizeWinding<Types::SEQUENTIAL>(opt.windingLevel, opt.windingBeta, grid, meshes[i]); break;
+                    case Types::OPENMP:     VoxelizeWinding<Types::OPENMP>(opt.windingLevel, opt.windingBeta, grid, meshes[i]); break;
+                    case Types::NAIVE:      VoxelizeWinding<Types::NAIVE>(opt.windingLevel, opt.windingBeta, grid, meshes[i]); break;
+                    case Types::TILED:      VoxelizeWinding<Types::TILED>(opt.windingLevel, opt.windingBeta, grid, meshes[i]); break;
+                }
+            } else if (opt.conservative) {
                 switch (TYPE) {
                     case Types::SEQUENTIAL: VoxelizeConservative<Types::SEQUENTIAL>(opt.blockSize, grid, meshes[i]); break;
                     case Types::OPENMP:     VoxelizeConservative<Types::OPENMP>(opt.blockSize, grid, meshes[i]); break;

@@ -67,6 +67,7 @@ SYMBOLS = [
     "vp_surfnets_count", "vp_surfnets", "vp_surfnets_host", "vp_isonets", "vp_isonets_result", "vp_isonets_host",
     "vp_edt", "vp_edt_sdf", "vp_edt_morph", "vp_edt_host", "vp_edt_sdf_host", "vp_edt_morph_host",
     "vp_mesh_distance", "vp_mesh_distance_host", "vp_mesh_distance_stats",
+    "vp_winding", "vp_winding_result", "vp_winding_host",
 ]
 
 
@@ -195,6 +196,10 @@ def lib():
         "vp_mesh_distance": (ctypes.c_int, [_vp, fp, _vp, _sz, _vp, _sz, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_int]),
         "vp_mesh_distance_host": (ctypes.c_int, [_vp, fp, _vp, _sz, _vp, _sz, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_int]),
         "vp_mesh_distance_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_winding": (ctypes.c_int, [_vp, fp, _vp, _sz, _vp, _sz, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_winding_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_winding_host": (ctypes.c_int, [_vp, fp, _vp, _sz, _vp, _sz, ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp, _vp,
+                                           ctypes.POINTER(ctypes.c_uint64)]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -523,7 +528,32 @@ class Context:
                                       ctypes.byref(nq)))
         return c.value or 0, x.value or 0, m.value or 0, q.value or 0, int(nv.value), int(nq.value)
 
+    def winding(self, frame: Frame, d_xyz: int, nverts: int, d_tri: int, ntris: int, beta: float = 2.0, level: float = 0.5,
+                algo: int = ALGO_TILED, count: bool = False):
+        """Generalized winding number of the mesh at the voxel centres and its inside grid (w >= level), built into buffers the context
+        owns; winding_result() hands them out.  beta = 0: brute force; 1 .. 64: the far-field opening parameter.  Enqueues only, unless
+        count=True: then it blocks and returns the number of inside voxels."""
+        c = ctypes.c_uint64()
+        check(lib().vp_winding(self._h, ctypes.byref(frame), _vp(d_xyz or None), nverts, _vp(d_tri or None), ntris, beta, level, algo,
+                               ctypes.byref(c) if count else None))
+        return int(c.value) if count else None
+
+    def winding_result(self):
+        """(d_w, d_inside, n) of the last winding(): device pointers as ints (0 where there is none) and the side they are for.  Valid until
+        the next winding(), release() or close()."""
+        w, g, n = _vp(), _vp(), ctypes.c_uint32()
+        check(lib().vp_winding_result(self._h, ctypes.byref(w), ctypes.byref(g), ctypes.byref(n)))
+        return w.value or 0, g.value or 0, int(n.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
+    def winding_host(self, frame: Frame, h_xyz, h_tri, beta: float = 2.0, level: float = 0.5, algo: int = ALGO_TILED):
+        """numpy in, numpy out: (w float32[n^3], inside words uint32[n^3 / 32], inside count)."""
+        np = __import__("numpy")
+        w, g, c = np.empty(frame.voxels, np.float32), np.empty(frame.voxels // 32, np.uint32), ctypes.c_uint64()
+        check(lib().vp_winding_host(self._h, ctypes.byref(frame), h_xyz.ctypes.data_as(_vp), h_xyz.shape[0], h_tri.ctypes.data_as(_vp),
+                                    h_tri.shape[0], beta, level, algo, w.ctypes.data_as(_vp), g.ctypes.data_as(_vp), ctypes.byref(c)))
+        return w, g, int(c.value)
+
     def voxelize_host(self, frame: Frame, h_words, h_xyz, h_tri, algo: int = ALGO_TILED):
         check(lib().vp_voxelize_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp),
                                      h_xyz.ctypes.data_as(_vp), h_xyz.shape[0], h_tri.ctypes.data_as(_vp),

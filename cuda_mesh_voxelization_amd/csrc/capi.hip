@@ -212,7 +212,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
                        &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small,
                        &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz, &ctx->edt_mask, &ctx->edt_vol, &ctx->edt_vol2, &ctx->edt_tmp,
                        &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list,
-                       &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads };
+                       &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads,
+                       &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -224,6 +225,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->fill_host) (void)hipHostFree(ctx->fill_host);
     if (ctx->comp_host) (void)hipHostFree(ctx->comp_host);
     if (ctx->md_host) (void)hipHostFree(ctx->md_host);
+    if (ctx->wn_host) (void)hipHostFree(ctx->wn_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -304,6 +306,8 @@ int vp_ctx_release(vp_ctx* ctx)
     for (Buffer* b : { &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads }) release(*b);      // vp_isonets: scratch and result
     ctx->iso_vertices = ctx->iso_quad_count = 0;
     ctx->iso_has_normals = false;
+    for (Buffer* b : { &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree }) release(*b);                                // vp_winding: scratch and result
+    ctx->wn_n = 0;
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -1136,6 +1140,45 @@ int vp_isonets_result(vp_ctx* ctx, uint64_t** d_cells, float** d_xyz, float** d_
     return 0;
 }
 
+// ---- generalized winding number ------------------------------------------------------------------
+// what vp_winding and its host form share: whole grids up to n = 1024, the algo, beta in {0} U [1, 64], a finite level
+static int check_winding(const vp_frame* f, const char* who, float beta, float level, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_whole(f, who));
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
+    VP_TRY(check_algo(who, algo));
+    if (!(beta == 0.0f || (beta >= 1.0f && beta <= 64.0f))) return set_error(VP_ERR_INVALID, "%s: beta %g (0, or 1 .. 64)", who, (double)beta);
+    if (!std::isfinite(level)) return set_error(VP_ERR_INVALID, "%s: level must be finite", who);
+    return 0;
+}
+
+int vp_winding(vp_ctx* ctx, const vp_frame* f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris, float beta,
+               float level, int algo, uint64_t* h_inside_count)
+{
+    const char* who = "vp_winding";
+    if (!ctx || !f) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_winding(f, who, beta, level, algo));
+    if (ntris && (!d_xyz || !d_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
+    if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "%s: too many triangles", who);
+    VP_TRY(check_aligned(who, {d_xyz, d_tri}));
+    const int rc = launch_winding(ctx, make_frame(f), d_xyz, nverts, d_tri, ntris, beta, level, algo, h_inside_count);
+    // the context's own buffers are outputs like any other: whatever was recorded about their bytes is gone
+    for (Buffer* b : { &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree }) grid_written(ctx, b->ptr, b->bytes);
+    return rc;
+}
+
+int vp_winding_result(vp_ctx* ctx, float** d_w, uint32_t** d_inside, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_winding_result: null ctx");
+    const bool any = ctx->wn_n != 0;
+    if (d_w) *d_w = any ? (float*)ctx->wn_w.ptr : nullptr;
+    if (d_inside) *d_inside = any ? (uint32_t*)ctx->wn_inside.ptr : nullptr;
+    if (h_n) *h_n = ctx->wn_n;
+    return 0;
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1238,6 +1281,23 @@ int vp_mesh_distance_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, si
     VP_TRY(vp_mesh_distance(ctx, f, (const float*)dx, nverts, (const uint32_t*)dt, ntris, (const uint32_t*)dw, band, (float*)dd, (uint32_t*)dn, algo));
     VP_TRY(vp_download(ctx, h_dist2, dd, vb));
     return h_nearest ? vp_download(ctx, h_nearest, dn, vb) : 0;
+}
+
+int vp_winding_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, size_t nverts, const uint32_t* h_tri, size_t ntris, float beta,
+                    float level, int algo, float* h_w, uint32_t* h_inside, uint64_t* h_inside_count)
+{
+    const char* who = "vp_winding_host";
+    if (!ctx || !f || (!h_w && !h_inside)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_winding(f, who, beta, level, algo));
+    if (ntris && (!h_xyz || !h_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
+    void *dx = nullptr, *dt = nullptr;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nverts * 12, &dx));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
+    VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
+    VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
+    VP_TRY(vp_winding(ctx, f, (const float*)dx, nverts, (const uint32_t*)dt, ntris, beta, level, algo, h_inside_count));
+    if (h_w) VP_TRY(vp_download(ctx, h_w, ctx->wn_w.ptr, vp_grid_voxels(f) * 4));
+    return h_inside ? vp_download(ctx, h_inside, ctx->wn_inside.ptr, vp_grid_words(f) * 4) : 0;
 }
 
 int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,

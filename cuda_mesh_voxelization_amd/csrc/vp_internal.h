@@ -124,6 +124,13 @@ struct vp_ctx {
     vp::Buffer iso_words, iso_cells, iso_xyz, iso_normals, iso_quads;
     uint64_t iso_vertices = 0, iso_quad_count = 0;
     bool iso_has_normals = false;
+    // generalized winding number (winding.hip): the result of the last vp_winding, which the context owns and vp_winding_result hands out
+    // -- the field w (4 n^3 bytes) and its inside grid (n^3 / 8 bytes) -- the triangle records sorted by leaf (48 B each) and the pyramid
+    // (counts, boxes, area sums, node records, leaf offsets, leaf keys); the pinned host word the inside count comes back through;
+    // wn_n = the side of the grid the result is for, 0: none.  The four buffers are freed by vp_ctx_release
+    vp::Buffer wn_w, wn_inside, wn_rec, wn_tree;
+    uint64_t* wn_host = nullptr;
+    uint32_t wn_n = 0;
 };
 
 namespace vp {
@@ -194,6 +201,10 @@ int launch_edt_morph(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint3
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,
                          const uint32_t* d_sign, uint32_t band, float* d_dist, uint32_t* d_nearest, int algo);
+// winding.hip: generalized winding number of a mesh at the centres of a whole grid and its inside grid, into the context's own buffers
+// (enqueues only once they have grown, unless h_inside_count asks for the count)
+int launch_winding(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris, float beta, float level,
+                   int algo, uint64_t* h_inside_count);
 // components.hip: labels, sizes and size filters of the connected components of a whole grid; all three are blocking (counts go to the host)
 int launch_components_label(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_labels, int conn, int algo, uint32_t* h_count);
 int launch_components_sizes(vp_ctx* ctx, uint32_t n, const uint32_t* d_labels, uint32_t count, uint32_t* d_sizes);

@@ -16,6 +16,14 @@ from . import capi
 from .capi import ALGO_NAIVE, ALGO_TILED, Frame  # noqa: F401
 
 
+class _DeviceView:
+    """A buffer of the context as an array for torch.as_tensor (no copy); `owner` keeps the engine alive with it."""
+
+    def __init__(self, ptr: int, count: int, typestr: str, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
+
+
 class Engine:
     def __init__(self, device: int = 0):
         if not torch.cuda.is_available():
@@ -170,6 +178,17 @@ class Engine:
                 self.ctx.memcpy_d2d(nrm.data_ptr(), dn, nv * 12)
             self.ctx.memcpy_d2d(quads.data_ptr(), dq, nq * 16)
         return cells, xyz, nrm, quads
+
+    def winding(self, frame: Frame, d_xyz, d_tri, beta: float = 2.0, level: float = 0.5, algo: int = ALGO_TILED):
+        """Generalized winding number of the mesh at the voxel centres (n <= 1024): returns (w, inside) -- a float32 tensor of n^3 values, x
+        fastest (1 inside a closed outward-oriented mesh, 0 outside, smooth through open boundaries), and the grid of the voxels with
+        w >= level in the library's bit layout, ready for mesh_distance(sign_words=...), csg(), morph(), surface_nets() ...  beta = 0 sums
+        every triangle exactly, beta = 1 .. 64 opens the far field (2 is the usual choice).  Both tensors are VIEWS of buffers the context
+        owns: they are overwritten by the next winding() and die with release() / close() -- clone() what has to live longer.  Enqueues only."""
+        self.ctx.winding(frame, d_xyz.data_ptr(), d_xyz.shape[0], d_tri.data_ptr(), d_tri.shape[0], beta, level, algo)
+        dw, dg, _ = self.ctx.winding_result()
+        return (torch.as_tensor(_DeviceView(dw, frame.voxels, "<f4", self), device=self.device),
+                torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device))
 
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)

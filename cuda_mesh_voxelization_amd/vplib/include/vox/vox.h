@@ -52,6 +52,12 @@ void MeshDistanceHost(bool parallel, const uint32_t* sign, size_t n, float voxel
                       float* dist2, uint32_t* nearest);
 void MeshDistanceDevice(int algo, const char* label, const uint32_t* sign, size_t n, float voxelSize, const float origin[3], const Mesh& mesh,
                         uint32_t band, float* dist2, uint32_t* nearest);
+// generalized winding number (winding.cpp): host restatement (pyramid by loops, one recursive walk per brick, one voxel at a time) and the
+// GPU marshalling; `w` (the field, n^3 floats) may be null
+void WindingHost(bool parallel, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh, float beta, float level,
+                 float* w);
+void WindingDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh, float beta,
+                   float level, float* w);
 // connected components (components.cpp): host restatement by a scan in index order with an explicit-stack flood per component, and the
 // GPU marshalling; the filters work in place
 struct ComponentStats { uint32_t count; uint64_t kept; };      // K components found, voxels kept
@@ -218,6 +224,31 @@ void MeshDistance(const HostVoxelsGrid<T>& grid, const Mesh& mesh, uint32_t band
     else
         detail::MeshDistanceDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveMeshDistance" : "TiledMeshDistance", words, n,
                                    v.VoxelSize(), origin, mesh, band, dist2.View().Data(), near);
+}
+
+// ComputeWinding: the SOLID grid of any mesh -- closed, open, a soup, self-intersecting -- from its generalized winding number (include/vphip.h,
+// vp_winding): voxel set iff w(centre) >= level, w = the sum of the signed solid angles of the triangles / 4 pi (1 inside a closed
+// outward-oriented mesh, 0 outside, k where k shells overlap: level 0.5 is the union, 1.5 the intersection of two).  The sign is exact at
+// the voxel CENTRE, which Compute's column rule is not.  beta = 0: every triangle exactly; 1 .. 64: far nodes of the brick pyramid as one
+// dipole each (2 is the usual choice).  Replaces the grid contents; `field` (optional) receives w and is resized to the grid.  No
+// reference counterpart.
+//   SEQUENTIAL / OPENMP   host restatement (OPENMP: bricks in parallel); any grid side that is a multiple of 8
+//   NAIVE / TILED         vp_winding_host with VP_ALGO_NAIVE / VP_ALGO_TILED (n % 32 == 0, n <= 1024)
+// Every variant produces the same bits.
+template <Types type, VGType T>
+void ComputeWinding(HostVoxelsGrid<T>& grid, const Mesh& mesh, float level = 0.5f, float beta = 2.0f, HostGrid<float>* field = nullptr)
+{
+    auto& v = grid.View();
+    const size_t n = v.VoxelsPerSide();
+    if (field && (field->View().SizeX() != n || field->View().SizeY() != n || field->View().SizeZ() != n)) *field = HostGrid<float>(n, 0.0f);
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    uint32_t* words = reinterpret_cast<uint32_t*>(v.Data());
+    float* w = field ? field->View().Data() : nullptr;
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        detail::WindingHost(type == Types::OPENMP, words, n, v.VoxelSize(), origin, mesh, beta, level, w);
+    else
+        detail::WindingDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveWinding" : "TiledWinding", words, n, v.VoxelSize(),
+                              origin, mesh, beta, level, w);
 }
 
 // LabelComponents / FilterComponents: connected components of the set voxels (include/vphip.h, vp_components_*).  conn = 6 (face

@@ -247,7 +247,8 @@ int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32
  * value, they only skip pairs that provably fail D2 < B2 as computed in float32.
  * THE SIGN is whatever grid the caller passes.  With vp_voxelize's grid it is the reference's column rule: a voxel is set from the cell
  * that CONTAINS the crossing, not from the first centre behind it, so along x a centre up to half a voxel outside the surface can carry +.
- * That is a property of the reference's solid rule, not of this field; a caller who needs a centre-exact sign passes a grid of their own.
+ * That is a property of the reference's solid rule, not of this field; a caller who needs a centre-exact sign passes a grid of their own
+ * (vp_winding below builds one from the mesh).
  *   algo: VP_ALGO_NAIVE -- one thread per triangle over the voxels of its band box, one 64-bit atomicMin per accepted pair on the key
  *   (D2 bits << 32) | index, then a streaming split; VP_ALGO_TILED -- triangles binned to 8 x 8 x 8-voxel bricks (count, scan, write; the
  *   brick rows of large triangles dealt to lanes), one workgroup per brick with the records staged through LDS, (D2, index) in registers,
@@ -403,6 +404,86 @@ int vp_isonets_result(vp_ctx* ctx, uint64_t** d_cells, float** d_xyz, float** d_
 int vp_isonets_host(vp_ctx* ctx, const vp_frame* f, const float* h_field, int transform, float iso, uint32_t iterations, int algo,
                     uint64_t* h_cells, float* h_xyz, float* h_normals, uint32_t* h_quads, size_t vertex_capacity, size_t quad_capacity,
                     uint64_t* h_vertices, uint64_t* h_quads_out);
+
+/* ---- generalized winding number: inside / outside from the mesh itself (no reference counterpart) ----------------
+ * w(p) = (1 / 4 pi) sum over the valid triangles t of the signed solid angle Omega_t(p) (Jacobson et al. 2013), with the dipole far field
+ * of Barill et al. 2018 over a pyramid of bricks.  w is 1 inside a closed mesh whose triangles are counter-clockwise seen from outside, 0
+ * outside it, k where k shells overlap, -1 inside an inverted shell, and varies smoothly through an open boundary.
+ * Everything below is float32 unless a cast says otherwise; every operation written is one correctly rounded IEEE operation in the
+ * association written, no contraction.  Dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;  max2(a, b) = a > b ? a : b.
+ *   sample point  p = the voxel centre as vp_voxelize forms it: p.a = o.a + (((float)i * vs) + (vs / 2.0f))
+ *   triangle      v0, v1, v2 in index order; valid as for vp_mesh_distance: every index < nverts, every coordinate finite, and
+ *                 nrm = Cross(e0, e1) != (0, 0, 0) with e0 = v1 - v0, e1 = v2 - v1 in the association of vp_voxelize_conservative.
+ *   exact term    a = v0 - p, b = v1 - p, c = v2 - p;  la = sqrtf(Dot(a, a)), lb, lc likewise;
+ *                 x = ((b.y c.z) - (b.z c.y), (b.z c.x) - (b.x c.z), (b.x c.y) - (b.y c.x));  det = Dot(a, x);
+ *                 den = ((((la lb) lc) + (Dot(a, b) lc)) + (Dot(b, c) la)) + (Dot(c, a) lb);  Omega = 2.0f * atan2w(det, den)
+ *                 (Van Oosterom & Strackee 1983).  A pair with det == 0, or with det or den not finite, contributes 0: p on a vertex, p in the
+ *                 triangle's plane -- the principal value, so a centre on the surface reads about 1/2.
+ *   atan2w(y, x)  the library's own, no libm: ax = fabsf(x), ay = fabsf(y);  t = min(ax, ay) / max(ax, ay);  s = t t;
+ *                 q = C9;  q = (q s) + C8;  ...  q = (q s) + C0  (VP_WN_ATAN_C* below);  r = q t;
+ *                 ay > ax: r = VP_WN_HALF_PI - r;  then x < 0: r = VP_WN_PI - r;  then y < 0: r = -r.
+ *   far term      of a node with centre c and area vector N:  d = c - p;  r2 = Dot(d, d);  Omega = Dot(d, N) / (r2 * sqrtf(r2)); dropped (0)
+ *                 if not finite.
+ *   sum           every term is quantised before it is added: q = llrint((double)Omega * 2^36) (round to nearest even), S = the sum of the q
+ *                 modulo 2^64, read as a two's complement int64;  w = (float)(((double)S * 2^-36) / VP_WN_FOUR_PI);  inside = (w >= level).
+ *                 Integer addition is associative: the result does not depend on the order of the triangles, on atomics or on lists.
+ *                 |Omega| < 2^3, so the sum of up to 2^24 terms cannot wrap; vp_winding admits up to (2^32 - 1) / 3 triangles, and above
+ *                 2^24 the forms still agree bit for bit (every form adds modulo 2^64), but w is meaningful only while the true sum
+ *                 stays below 2^63 -- always, for a mesh whose winding number is below 2^24 in absolute value.
+ * THE HIERARCHY decides which terms exist and is part of the contract.  nb = n / 8.
+ *   leaves        the 8 x 8 x 8-voxel bricks of vp_mesh_distance.  A valid triangle belongs to ONE leaf, that of its centroid:
+ *                 g.a = ((v0.a + v1.a) + v2.a) / 3.0f;  q.a = floorf(((g.a - o.a) / vs) / 8.0f);
+ *                 b.a = q.a >= (float)(nb - 1) ? nb - 1 : (q.a > 0 ? (int)q.a : 0)  -- clamped to the grid (a NaN gives 0), so a mesh scaled
+ *                 out of the frame is served; a node's box comes from its triangles, not from its cell, so the clamp costs no accuracy.
+ *   levels        level k has ceil(nb / 2^k) nodes per side, up to the level with one node (n = 96: 12, 6, 3, 2, 1); node (x, y, z) of level
+ *                 k + 1 has the children (2x + i, 2y + j, 2z + l), i, j, l in {0, 1}, that lie inside level k.
+ *   node          count = its triangles; box = per axis the minimum and maximum of their vertex coordinates in the INTEGER order of floats
+ *                 (-0 < +0);  h.a = (hi.a - lo.a) / 2.0f;  c.a = lo.a + h.a;  r = sqrtf(Dot(h, h));
+ *                 area vector: per triangle and axis  s = ((double)nrm.a * 2^23) / ((double)vs * (double)vs)  -- nrm / 2 in units of
+ *                 vs^2 2^-24 --, then s > 2^62: s = 2^62;  s < -2^62: s = -2^62;  s != s: s = 0;  A.a = llrint(s); the node's A = the sum of its
+ *                 triangles' modulo 2^64 (two's complement);  N.a = (float)((double)A.a * (((double)vs * (double)vs) * 2^-24)).
+ *                 A node without triangles contributes nothing.  Accuracy statements assume no wrap: the summed |area| of a node below
+ *                 2^38 voxel faces.
+ *   evaluation    per (brick of voxels B, node): lo.a / hi.a = the centres of the brick's first / last voxel along a;
+ *                 g.a = max2(0, max2(lo.a - c.a, c.a - hi.a));  br = beta * r;  FAR iff Dot(g, g) > br * br && beta > 0.
+ *                 From the root: a FAR node is one far term for each of the 512 voxels of B; otherwise a leaf contributes its triangles
+ *                 exactly and an inner node is descended into.
+ *   beta          0: no far field, the brute-force sum over all valid triangles (the accuracy anchor); 1 .. 64: the opening parameter.
+ *                 Anything else, or not finite: VP_ERR_INVALID.  level must be finite.  Only the dipole (Barill's order 1) is implemented.
+ *   vp_winding         builds w (4 n^3 bytes, x fastest) and the inside grid (n^3 / 8 bytes, the library's bit layout) into grow-only
+ *                      buffers that the CONTEXT owns; vp_ctx_release frees them.  Enqueues only, once the buffers have grown (nothing is
+ *                      read back); with h_inside_count != NULL it BLOCKS and stores the number of inside voxels.
+ *   vp_winding_result  pointers to the last result and the side it is for; any argument may be NULL.  Before a build and after a release:
+ *                      NULL pointers and side 0.  The inside grid is a grid like any other: vp_mesh_distance takes it as d_sign_words
+ *                      (the centre-exact sign), and vp_csg, vp_morph, vp_extract, vp_surfnets, vp_jfa, ... read it as their input.
+ *   vp_winding_host    host in, host out (mesh staged through workspace slots); h_w or h_inside may be NULL, not both.
+ * Whole-grid frames only: a slab frame and n > 1024 return VP_ERR_UNSUPPORTED.  Null ctx / f, null mesh arrays with ntris > 0, mesh arrays
+ * that are not 16-byte aligned, an unknown algo: VP_ERR_INVALID.  A refusal is decided before anything is touched and leaves the previous
+ * result as it was.
+ *   algo: VP_ALGO_TILED -- one workgroup per brick walks the pyramid once for its 512 voxels (the far test depends on the brick and the
+ *   node only), near leaves' records staged through LDS, two 64-bit accumulators per lane, inside bits by ballot; VP_ALGO_NAIVE -- one
+ *   thread per voxel walks the pyramid from global memory.  Same bytes.  Scratch of the context (grow-only, freed by vp_ctx_release): the
+ *   records sorted by leaf (48 B per triangle) and the pyramid (84 B per node + 4 B per leaf and per triangle).  Timing books under the keys
+ *   of the corresponding vp_mesh_distance stages: VP_K_MD_SETUP, _SCAN, _WRITE, _COUNT (the level reductions), _BRICK, _NAIVE, _SPLIT (the
+ *   inside count, when asked for). */
+#define VP_WN_ATAN_C0 0x1.000000p+0f
+#define VP_WN_ATAN_C1 -0x1.5554eep-2f
+#define VP_WN_ATAN_C2 0x1.9986eap-3f
+#define VP_WN_ATAN_C3 -0x1.23c878p-3f
+#define VP_WN_ATAN_C4 0x1.bd901cp-4f
+#define VP_WN_ATAN_C5 -0x1.506f4ap-4f
+#define VP_WN_ATAN_C6 0x1.c2c986p-5f
+#define VP_WN_ATAN_C7 -0x1.d2c990p-6f
+#define VP_WN_ATAN_C8 0x1.397f42p-7f
+#define VP_WN_ATAN_C9 -0x1.8ba540p-10f
+#define VP_WN_HALF_PI 0x1.921fb6p+0f
+#define VP_WN_PI 0x1.921fb6p+1f
+#define VP_WN_FOUR_PI 0x1.921fb54442d18p+3 /* double */
+int vp_winding(vp_ctx* ctx, const vp_frame* f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris, float beta,
+               float level, int algo, uint64_t* h_inside_count /* may be NULL */);
+int vp_winding_result(vp_ctx* ctx, float** d_w, uint32_t** d_inside, uint32_t* h_n);
+int vp_winding_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, size_t nverts, const uint32_t* h_tri, size_t ntris, float beta,
+                    float level, int algo, float* h_w, uint32_t* h_inside, uint64_t* h_inside_count /* may be NULL */);
 
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
