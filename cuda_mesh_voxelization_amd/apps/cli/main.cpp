@@ -27,6 +27,14 @@
 //                            for a closed mesh, and a sensible solid for an open mesh, a soup or overlapping shells (L = 1.5: where two
 //                            shells overlap).  B = 0 sums every triangle, 1..64 opens the far field.  --morph, --fill, CSG, -e and -s run
 //                            on its grids unchanged, and --mesh-sdf is then signed by it
+//         --thickness R[:W]  (extension) local thickness of the FINAL grid -- after the voxelization, --morph, --fill and CSG, before the CSG
+//                            export and -s: for every set voxel the squared radius T2 of the largest ball that fits inside the solid and
+//                            contains the voxel, in a band of R = 1 .. 32 voxels (include/vphip.h, vp_thickness; the thickness in voxels is
+//                            2 sqrt(T2), R^2 = thicker than 2 R).  Prints the smallest T2 over the set voxels and the histogram of T2; with W
+//                            (a thickness in whole voxels, 1 .. 2 R) also the number of thin voxels, 4 T2 < W^2.  -d PREFIX additionally
+//                            writes PREFIX.thick.u32 (n^3 values) and, with W, PREFIX.thin.u32 (a grid).  One device only (-g > 1 is refused)
+//         --thin-only        (extension, with --thickness R:W) the grid is replaced by the thin grid before the exports that follow and -s:
+//                            -e writes out/thin_<type>_<output>, cubes or --surface-nets, and -d PREFIX.grid.u32 holds it
 //         --fill             (extension) after each mesh's voxelization (solid or --conservative), fill its interior: every empty voxel
 //                            that no 6-connected path of empty voxels joins to the grid boundary is set (include/vphip.h,
 //                            vp_fill_interior).  Runs before export, CSG and sdf, so --conservative --fill gives the solid of an open
@@ -111,6 +119,8 @@ struct Options {
     bool winding = false;                                   // --winding [LEVEL[:BETA]]: solid from the generalized winding number
     float windingLevel = 0.5f, windingBeta = 2.0f;
     bool fill = false;
+    unsigned thickness = 0, thinWidth = 0;                  // --thickness RMAX[:W]: band in voxels, 0 = not asked for; W = 0: no thin grid
+    bool thinOnly = false;
     bool exactSdf = false;
     int meshSdf = 0;                                        // --mesh-sdf BAND: band in voxels, 0 = not asked for
     bool isoNets = false;                                   // --iso-nets LEVEL[:ITERS]: level in voxels, relaxation steps
@@ -203,6 +213,12 @@ const char* kUsage =
     "      --winding [arg]   Solid voxelization by the generalized winding number: a voxel is set iff w(centre) >= LEVEL; arg =\n"
     "                        LEVEL[:BETA], default 0.5:2 (BETA 0: every triangle exactly, 1..64: far field).  Any mesh: closed, open,\n"
     "                        soups, overlapping shells; the sign --mesh-sdf then uses is exact at the voxel centres (extension)\n"
+    "      --thickness arg   Local thickness of the final grid (after --morph, --fill and CSG): arg = RMAX[:W], RMAX = 1..32 voxels; prints\n"
+    "                        the smallest squared ball radius T2 over the set voxels (thickness = 2 sqrt(T2) voxels, RMAX^2 = saturated)\n"
+    "                        and the histogram of T2; with W = 1..2 RMAX also the number of voxels thinner than W voxels (4 T2 < W^2).\n"
+    "                        -d PREFIX adds PREFIX.thick.u32 and PREFIX.thin.u32.  One device only: not with -g > 1 (extension)\n"
+    "      --thin-only       With --thickness RMAX:W: replace the grid by the thin grid, so that -e (out/thin_<type>_<output>), -s and\n"
+    "                        -d see the thin regions (extension)\n"
     "      --conservative    Surface voxelization: a voxel is set iff its closed box overlaps a triangle (any mesh, open or\n"
     "                        closed; the default solid rule needs closed meshes); CSG, export, sdf and dumps work on it unchanged.\n"
     "                        One device only: not with -g > 1 (extension)\n"
@@ -241,7 +257,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -282,10 +298,10 @@ Options Parse(int argc, char** argv)
             o.windingLevel = static_cast<float>(lv); o.windingBeta = static_cast<float>(bt);
             continue;
         }
-        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X';
+        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X' || key == 'O';
         if (isSwitch) {
             const bool v = !hasValue || value == "true" || value == "1";
-            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else if (key == 'X') o.exactSdf = v; else o.help = v;
+            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else if (key == 'X') o.exactSdf = v; else if (key == 'O') o.thinOnly = v; else o.help = v;
             continue;
         }
         if (!hasValue) {
@@ -307,6 +323,18 @@ Options Parse(int argc, char** argv)
                 const bool digits = !value.empty() && value.size() <= 2 && value.find_first_not_of("0123456789") == std::string::npos;
                 cpuAssert(digits && std::stoi(value) >= 1 && std::stoi(value) <= 32, "--mesh-sdf: '" + value + "' is not a band of 1..32 voxels\n");
                 o.meshSdf = std::stoi(value);
+                break;
+            }
+            case 'T': {
+                // RMAX[:W]: 1 .. 32, then a thickness in whole voxels, 1 .. 2 RMAX
+                const size_t colon = value.find(':');
+                const std::string band = value.substr(0, colon), width = colon == std::string::npos ? "" : value.substr(colon + 1);
+                auto digits = [](const std::string& t) { return !t.empty() && t.size() <= 2 && t.find_first_not_of("0123456789") == std::string::npos; };
+                const bool bandOk = digits(band) && std::stoi(band) >= 1 && std::stoi(band) <= 32;
+                const bool widthOk = colon == std::string::npos || (bandOk && digits(width) && std::stoi(width) >= 1 && std::stoi(width) <= 2 * std::stoi(band));
+                cpuAssert(bandOk && widthOk, "--thickness: '" + value + "' is not RMAX[:W] with RMAX in 1..32 voxels and W in 1..2 RMAX\n");
+                o.thickness = static_cast<unsigned>(std::stoi(band));
+                o.thinWidth = colon == std::string::npos ? 0u : static_cast<unsigned>(std::stoi(width));
                 break;
             }
             case 'N': {
@@ -372,6 +400,27 @@ void MorphSteps(const std::vector<Options::MorphStep>& steps, HostVoxelsGrid<gri
     }
 }
 
+// --thickness: T2 of `grid` into `t2`, the thin grid into `thin` when a width was given; prints what the flag promises
+template <Types T>
+void Thickness(unsigned rmax, unsigned width, const HostVoxelsGrid<gridType>& grid, HostGrid<uint32_t>& t2, HostVoxelsGrid<gridType>& thin)
+{
+    const uint32_t thin2 = (width * width + 3u) / 4u;              // thin iff 4 T2 < W^2
+    const uint64_t count = VOX::LocalThickness<T>(grid, rmax, t2, thin2, width ? &thin : nullptr);
+    std::vector<uint64_t> hist(rmax * rmax + 1, 0);
+    const uint32_t* v = t2.View().Data();
+    for (size_t i = 0; i < t2.View().Size(); ++i) ++hist[v[i]];
+    uint64_t set = 0;
+    uint32_t least = 0;
+    for (uint32_t t = rmax * rmax; t >= 1; --t)
+        if (hist[t]) { set += hist[t]; least = t; }
+    std::printf("thickness: rmax %u, set voxels %llu, min T2 %u\n", rmax, static_cast<unsigned long long>(set), least);
+    std::printf("thickness histogram (T2: voxels):");
+    for (uint32_t t = 1; t <= rmax * rmax; ++t)
+        if (hist[t]) std::printf(" %u: %llu", t, static_cast<unsigned long long>(hist[t]));
+    std::printf("\n");
+    if (width) std::printf("thin voxels (thinner than %u voxels, T2 < %u): %llu\n", width, thin2, static_cast<unsigned long long>(count));
+}
+
 template <Types T>
 void Csg(CSG::Op op, HostVoxelsGrid<gridType>& a, HostVoxelsGrid<gridType>& b)
 {
@@ -427,6 +476,8 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.winding && opt.conservative), "--winding and --conservative exclude each other: one voxelization per mesh\n");
     cpuAssert(!(opt.winding && opt.gpus > 1), "--winding runs on one device: -g must be 1\n");
     cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.thickness && opt.gpus > 1), "--thickness runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.thinOnly && !(opt.thickness && opt.thinWidth)), "--thin-only needs --thickness RMAX:W: the thin grid is that of a width\n");
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
     cpuAssert(!(opt.exactSdf && !opt.sdf), "--exact-sdf needs -s: it chooses how the distance field is computed\n");
     cpuAssert(!(opt.exactSdf && opt.gpus > 1), "--exact-sdf runs on one device: -g must be 1\n");
@@ -474,6 +525,8 @@ int main(int argc, char** argv)
 
     HostVoxelsGrid<gridType> emptyGrid(N, voxelSize);       // benchmark-mode CSG operand (main.cpp:89,127)
     HostGrid<float> sdf;
+    HostGrid<uint32_t> thick;
+    HostVoxelsGrid<gridType> thinGrid;
     const std::string typeName = GetTypesString(TYPE);
     if (EXPORT) std::filesystem::create_directories("out");
 
@@ -536,6 +589,23 @@ int main(int argc, char** argv)
                 }
             }
             if (BENCHMARK) break;
+        }
+
+        if (opt.thickness) {
+            switch (TYPE) {
+                case Types::SEQUENTIAL: Thickness<Types::SEQUENTIAL>(opt.thickness, opt.thinWidth, grids[0], thick, thinGrid); break;
+                case Types::OPENMP:     Thickness<Types::OPENMP>(opt.thickness, opt.thinWidth, grids[0], thick, thinGrid); break;
+                case Types::NAIVE:      Thickness<Types::NAIVE>(opt.thickness, opt.thinWidth, grids[0], thick, thinGrid); break;
+                case Types::TILED:      Thickness<Types::TILED>(opt.thickness, opt.thinWidth, grids[0], thick, thinGrid); break;
+            }
+            if (opt.thinOnly) {
+                std::memcpy(grids[0].View().Data(), thinGrid.View().Data(), grids[0].View().StorageSize() * sizeof(gridType));
+                if (EXPORT) {
+                    Mesh outMesh;
+                    GridMesh(GPU, opt.surfaceOnly, opt.surfaceNets, grids[0].View(), outMesh);
+                    cpuAssert(ExportMesh("out/thin_" + typeName + "_" + opt.output, outMesh), "Error in " + opt.output + " export (thin)");
+                }
+            }
         }
 
         if (EXPORT && OPERATION != CSG::Op::VOID) {                                                     // main.cpp:192-197
@@ -619,6 +689,8 @@ int main(int argc, char** argv)
     if (!opt.dump.empty()) {
         WriteRaw(opt.dump + ".grid.u32", grids[0].View().Data(), grids[0].View().StorageSize() * sizeof(gridType));
         if (opt.sdf) WriteRaw(opt.dump + ".sdf.f32", sdf.View().Data(), sdf.View().Size() * sizeof(float));
+        if (opt.thickness) WriteRaw(opt.dump + ".thick.u32", thick.View().Data(), thick.View().Size() * sizeof(uint32_t));
+        if (opt.thickness && opt.thinWidth) WriteRaw(opt.dump + ".thin.u32", thinGrid.View().Data(), thinGrid.View().StorageSize() * sizeof(gridType));
     }
     return 0;
 }

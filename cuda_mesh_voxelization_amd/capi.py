@@ -68,6 +68,7 @@ SYMBOLS = [
     "vp_edt", "vp_edt_sdf", "vp_edt_morph", "vp_edt_host", "vp_edt_sdf_host", "vp_edt_morph_host",
     "vp_mesh_distance", "vp_mesh_distance_host", "vp_mesh_distance_stats",
     "vp_winding", "vp_winding_result", "vp_winding_host",
+    "vp_thickness", "vp_thickness_result", "vp_thickness_host",
 ]
 
 
@@ -200,6 +201,9 @@ def lib():
         "vp_winding_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32)]),
         "vp_winding_host": (ctypes.c_int, [_vp, fp, _vp, _sz, _vp, _sz, ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp, _vp,
                                            ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_thickness": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_thickness_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_thickness_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -545,7 +549,30 @@ class Context:
         check(lib().vp_winding_result(self._h, ctypes.byref(w), ctypes.byref(g), ctypes.byref(n)))
         return w.value or 0, g.value or 0, int(n.value)
 
+    def thickness(self, frame: Frame, d_words: int, rmax: int, thin2: int = 0, algo: int = ALGO_TILED, count: bool = False):
+        """Local thickness of a whole grid in a band of rmax = 1 .. 32 voxels -- T2, the squared radius of the largest inscribed ball through
+        every set voxel -- and the grid of the set voxels with T2 < thin2, built into buffers the context owns; thickness_result() hands
+        them out.  Enqueues only, unless count=True: then it blocks and returns the number of thin voxels."""
+        c = ctypes.c_uint64()
+        check(lib().vp_thickness(self._h, ctypes.byref(frame), _vp(d_words or None), rmax, thin2, algo, ctypes.byref(c) if count else None))
+        return int(c.value) if count else None
+
+    def thickness_result(self):
+        """(d_t2, d_thin, n) of the last thickness(): device pointers as ints (0 where there is none) and the side they are for.  Valid
+        until the next thickness(), release() or close()."""
+        t, g, n = _vp(), _vp(), ctypes.c_uint32()
+        check(lib().vp_thickness_result(self._h, ctypes.byref(t), ctypes.byref(g), ctypes.byref(n)))
+        return t.value or 0, g.value or 0, int(n.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
+    def thickness_host(self, frame: Frame, h_words, rmax: int, thin2: int = 0, algo: int = ALGO_TILED):
+        """numpy in, numpy out: (T2 uint32[n^3], thin words uint32[n^3 / 32], thin count)."""
+        np = __import__("numpy")
+        t, g, c = np.empty(frame.voxels, np.uint32), np.empty(frame.voxels // 32, np.uint32), ctypes.c_uint64()
+        check(lib().vp_thickness_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), rmax, thin2, algo, t.ctypes.data_as(_vp),
+                                      g.ctypes.data_as(_vp), ctypes.byref(c)))
+        return t, g, int(c.value)
+
     def winding_host(self, frame: Frame, h_xyz, h_tri, beta: float = 2.0, level: float = 0.5, algo: int = ALGO_TILED):
         """numpy in, numpy out: (w float32[n^3], inside words uint32[n^3 / 32], inside count)."""
         np = __import__("numpy")

@@ -213,7 +213,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
                        &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz, &ctx->edt_mask, &ctx->edt_vol, &ctx->edt_vol2, &ctx->edt_tmp,
                        &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list,
                        &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads,
-                       &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree };
+                       &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree,
+                       &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -226,6 +227,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->comp_host) (void)hipHostFree(ctx->comp_host);
     if (ctx->md_host) (void)hipHostFree(ctx->md_host);
     if (ctx->wn_host) (void)hipHostFree(ctx->wn_host);
+    if (ctx->th_host) (void)hipHostFree(ctx->th_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -308,6 +310,8 @@ int vp_ctx_release(vp_ctx* ctx)
     ctx->iso_has_normals = false;
     for (Buffer* b : { &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree }) release(*b);                                // vp_winding: scratch and result
     ctx->wn_n = 0;
+    for (Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum }) release(*b);                   // vp_thickness: scratch and result
+    ctx->th_n = 0;
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -1179,6 +1183,49 @@ int vp_winding_result(vp_ctx* ctx, float** d_w, uint32_t** d_inside, uint32_t* h
     return 0;
 }
 
+// ---- local thickness -------------------------------------------------------------------------------
+// what vp_thickness and its host form share: whole grids up to n = 1024, the algo, rmax in 1 .. 32, thin2 in 0 .. rmax^2
+static int check_thickness(const vp_frame* f, const char* who, uint32_t rmax, uint32_t thin2, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_whole(f, who));
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
+    VP_TRY(check_algo(who, algo));
+    if (rmax < 1 || rmax > 32) return set_error(VP_ERR_INVALID, "%s: rmax %u (1 .. 32)", who, rmax);
+    if (thin2 > rmax * rmax) return set_error(VP_ERR_INVALID, "%s: thin2 %u (0 .. rmax^2 = %u)", who, thin2, rmax * rmax);
+    return 0;
+}
+
+int vp_thickness(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t rmax, uint32_t thin2, int algo, uint64_t* h_thin_count)
+{
+    const char* who = "vp_thickness";
+    if (!ctx || !f || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_thickness(f, who, rmax, thin2, algo));
+    VP_TRY(check_aligned(who, {d_words}));
+    // the grid is read while every buffer of the call is written: it may lie in none of them (the last thin grid has to be copied first)
+    for (const Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum, &ctx->edt_vol, &ctx->edt_vol2 })
+        VP_TRY(check_disjoint(who, "a buffer of the context", d_words, vp_grid_words(f) * 4, b->ptr, b->bytes));
+    // the context's own buffers are outputs like any other: whatever was recorded about their bytes is gone -- about the bytes they
+    // hold now (a buffer that has to grow is freed first) and, after the launch, about the bytes they hold then
+    for (Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum, &ctx->edt_vol, &ctx->edt_vol2 })
+        grid_written(ctx, b->ptr, b->bytes);
+    const int rc = launch_thickness(ctx, make_frame(f), d_words, rmax, thin2, algo, h_thin_count);
+    for (Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum, &ctx->edt_vol, &ctx->edt_vol2 })
+        grid_written(ctx, b->ptr, b->bytes);
+    return rc;
+}
+
+int vp_thickness_result(vp_ctx* ctx, uint32_t** d_t2, uint32_t** d_thin, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_thickness_result: null ctx");
+    const bool any = ctx->th_n != 0;
+    if (d_t2) *d_t2 = any ? (uint32_t*)ctx->th_t2.ptr : nullptr;
+    if (d_thin) *d_thin = any ? (uint32_t*)ctx->th_thin.ptr : nullptr;
+    if (h_n) *h_n = ctx->th_n;
+    return 0;
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1298,6 +1345,20 @@ int vp_winding_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, size_t n
     VP_TRY(vp_winding(ctx, f, (const float*)dx, nverts, (const uint32_t*)dt, ntris, beta, level, algo, h_inside_count));
     if (h_w) VP_TRY(vp_download(ctx, h_w, ctx->wn_w.ptr, vp_grid_voxels(f) * 4));
     return h_inside ? vp_download(ctx, h_inside, ctx->wn_inside.ptr, vp_grid_words(f) * 4) : 0;
+}
+
+int vp_thickness_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t rmax, uint32_t thin2, int algo, uint32_t* h_t2,
+                      uint32_t* h_thin, uint64_t* h_thin_count)
+{
+    const char* who = "vp_thickness_host";
+    if (!ctx || !f || !h_words || (!h_t2 && !h_thin)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_thickness(f, who, rmax, thin2, algo));
+    void* dw = nullptr;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, vp_grid_words(f) * 4, &dw));
+    VP_TRY(vp_upload(ctx, dw, h_words, vp_grid_words(f) * 4));
+    VP_TRY(vp_thickness(ctx, f, (const uint32_t*)dw, rmax, thin2, algo, h_thin_count));
+    if (h_t2) VP_TRY(vp_download(ctx, h_t2, ctx->th_t2.ptr, vp_grid_voxels(f) * 4));
+    return h_thin ? vp_download(ctx, h_thin, ctx->th_thin.ptr, vp_grid_words(f) * 4) : 0;
 }
 
 int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,

@@ -203,6 +203,14 @@ int launch_edt(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int seeds, 
     return column_pass(ctx, n, d_dist, 2);
 }
 
+int launch_edt_thresh(vp_ctx* ctx, uint32_t n, const uint32_t* d_dist, uint32_t* d_out, uint32_t r2, int greater)
+{
+    ProfScope p(ctx, VP_K_EDT_THRESH);
+    hipLaunchKernelGGL(edt_thresh, dim3((unsigned)((size_t)n * n * n / 256)), dim3(256), 0, ctx->stream, d_dist, d_out, r2, greater);
+    VP_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_edt_sdf(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, float fill, float* d_sdf, int algo)
 {
     VP_TRY(launch_edt(ctx, f, d_words, VP_EDT_SEEDS_BORDER, reinterpret_cast<uint32_t*>(d_sdf), algo));

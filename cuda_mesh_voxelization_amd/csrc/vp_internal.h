@@ -131,6 +131,14 @@ struct vp_ctx {
     vp::Buffer wn_w, wn_inside, wn_rec, wn_tree;
     uint64_t* wn_host = nullptr;
     uint32_t wn_n = 0;
+    // local thickness (thickness.hip): the result of the last vp_thickness, which the context owns and vp_thickness_result hands out -- T2
+    // (4 n^3 bytes) and the thin grid (n^3 / 8 bytes) -- TILED's capped radii as uint16 (2 n^3 bytes), the grids of the saturated centres and
+    // of the saturated region (n^3 / 8 bytes each) and the thin count with the per-brick summaries; the pinned host word the count comes
+    // back through; th_n = the side of the grid the result is for, 0: none.  The five buffers are freed by vp_ctx_release (the distance
+    // volumes are edt_vol / edt_vol2)
+    vp::Buffer th_t2, th_thin, th_d16, th_sat, th_sum;
+    uint64_t* th_host = nullptr;
+    uint32_t th_n = 0;
 };
 
 namespace vp {
@@ -197,6 +205,11 @@ int launch_morph(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_o
 int launch_edt(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int seeds, uint32_t* d_dist, int algo);
 int launch_edt_sdf(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, float fill, float* d_sdf, int algo);
 int launch_edt_morph(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint32_t* d_out, int op, uint32_t radius, int algo);
+// the threshold pass of vp_edt_morph on its own: bit = D <= r2 (greater == 0) or D > r2, booked under VP_K_EDT_THRESH
+int launch_edt_thresh(vp_ctx* ctx, uint32_t n, const uint32_t* d_dist, uint32_t* d_out, uint32_t r2, int greater);
+// thickness.hip: local thickness of a whole grid -- T2 and the thin grid -- into the context's own buffers (enqueues only once they have
+// grown, unless h_thin_count asks for the count)
+int launch_thickness(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint32_t rmax, uint32_t thin2, int algo, uint64_t* h_thin_count);
 // meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,

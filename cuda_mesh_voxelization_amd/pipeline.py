@@ -190,6 +190,18 @@ class Engine:
         return (torch.as_tensor(_DeviceView(dw, frame.voxels, "<f4", self), device=self.device),
                 torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device))
 
+    def thickness(self, frame: Frame, words, rmax: int, thin2: int = 0, algo: int = ALGO_TILED):
+        """Local thickness of a grid (n <= 1024) in a band of rmax = 1 .. 32 voxels: returns (t2, thin) -- a tensor of n^3 values, x fastest,
+        the squared radius of the largest ball that fits inside the solid and contains the voxel (0 on unset voxels, rmax^2 where the part
+        is thicker than 2 rmax; the thickness in voxels is 2 sqrt(t2)), and the grid of the set voxels with t2 < thin2 in the library's bit
+        layout, ready for components(), morph(), surface_nets() ...  Pore or channel width is the same call on ~words.  Both tensors are
+        VIEWS of buffers the context owns: they are overwritten by the next thickness() and die with release() / close() -- clone() what
+        has to live longer (the thin grid too, before it goes back in as `words`).  Enqueues only."""
+        self.ctx.thickness(frame, words.data_ptr(), rmax, thin2, algo)
+        dt, dg, _ = self.ctx.thickness_result()
+        return (torch.as_tensor(_DeviceView(dt, frame.voxels, "<i4", self), device=self.device),
+                torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device))
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

@@ -58,6 +58,11 @@ void WindingHost(bool parallel, uint32_t* words, size_t n, float voxelSize, cons
                  float* w);
 void WindingDevice(int algo, const char* label, uint32_t* words, size_t n, float voxelSize, const float origin[3], const Mesh& mesh, float beta,
                    float level, float* w);
+// local thickness (thickness.cpp): host restatement (the definition by loops, one target plane at a time) and the GPU marshalling; `t2`
+// (n^3 values) is always written, `thin` (grid words) may be null; both return the number of thin voxels
+uint64_t ThicknessHost(bool parallel, const uint32_t* words, size_t n, uint32_t rmax, uint32_t thin2, uint32_t* t2, uint32_t* thin);
+uint64_t ThicknessDevice(int algo, const char* label, const uint32_t* words, size_t n, float voxelSize, const float origin[3], uint32_t rmax,
+                         uint32_t thin2, uint32_t* t2, uint32_t* thin);
 // connected components (components.cpp): host restatement by a scan in index order with an explicit-stack flood per component, and the
 // GPU marshalling; the filters work in place
 struct ComponentStats { uint32_t count; uint64_t kept; };      // K components found, voxels kept
@@ -249,6 +254,35 @@ void ComputeWinding(HostVoxelsGrid<T>& grid, const Mesh& mesh, float level = 0.5
     else
         detail::WindingDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveWinding" : "TiledWinding", words, n, v.VoxelSize(),
                               origin, mesh, beta, level, w);
+}
+
+// LocalThickness: for every set voxel the squared radius T2 of the largest ball that fits inside the solid and contains the voxel, in a band
+// of rmax = 1 .. 32 voxels (include/vphip.h, vp_thickness; Hildebrand & Ruegsegger 1997): t2(x, y, z) = max { D(c) : |p - c|^2 < D(c) } with
+// D = min(squared distance to the nearest unset voxel, squared distance to the nearest voxel outside the grid, rmax^2); 0 on unset voxels,
+// rmax^2 where the part is thicker than 2 rmax.  The thickness in voxels is 2 sqrt(t2).  `thin` (optional; replaced, keeps the frame of
+// `grid`) receives the set voxels with t2 < thin2 (0 .. rmax^2); the return value is their number.  `t2` is resized to the grid.  Pore or
+// channel width: the same call on the complemented grid (the frame's wall then acts as solid).  No reference counterpart.
+//   SEQUENTIAL / OPENMP   host restatement: the definition by loops (OPENMP: target planes in parallel); any grid side
+//   NAIVE / TILED         vp_thickness_host with VP_ALGO_NAIVE / VP_ALGO_TILED (n % 32 == 0, n <= 1024)
+// Every variant produces the same values and bits.
+template <Types type, VGType T>
+uint64_t LocalThickness(const HostVoxelsGrid<T>& grid, uint32_t rmax, HostGrid<uint32_t>& t2, uint32_t thin2 = 0, HostVoxelsGrid<T>* thin = nullptr)
+{
+    const auto& v = grid.View();
+    const size_t n = v.VoxelsPerSide();
+    if (t2.View().SizeX() != n || t2.View().SizeY() != n || t2.View().SizeZ() != n) t2 = HostGrid<uint32_t>(n, 0u);
+    const float origin[3] = {v.OriginX(), v.OriginY(), v.OriginZ()};
+    if (thin) {
+        *thin = HostVoxelsGrid<T>(n, v.VoxelSize());
+        thin->View().SetOrigin(origin[0], origin[1], origin[2]);
+    }
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(v.Data());
+    uint32_t* tw = thin ? reinterpret_cast<uint32_t*>(thin->View().Data()) : nullptr;
+    if constexpr (type == Types::SEQUENTIAL || type == Types::OPENMP)
+        return detail::ThicknessHost(type == Types::OPENMP, words, n, rmax, thin2, t2.View().Data(), tw);
+    else
+        return detail::ThicknessDevice(type == Types::NAIVE ? 1 : 2, type == Types::NAIVE ? "NaiveThickness" : "TiledThickness", words, n,
+                                       v.VoxelSize(), origin, rmax, thin2, t2.View().Data(), tw);
 }
 
 // LabelComponents / FilterComponents: connected components of the set voxels (include/vphip.h, vp_components_*).  conn = 6 (face

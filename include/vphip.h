@@ -485,6 +485,60 @@ int vp_winding_result(vp_ctx* ctx, float** d_w, uint32_t** d_inside, uint32_t* h
 int vp_winding_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, size_t nverts, const uint32_t* h_tri, size_t ntris, float beta,
                     float level, int algo, float* h_w, uint32_t* h_inside, uint64_t* h_inside_count /* may be NULL */);
 
+/* ---- local thickness: the largest inscribed ball through every voxel (no reference counterpart) ------------------
+ * For every set voxel the squared radius of the largest ball that fits inside the solid and contains the voxel (Hildebrand & Ruegsegger
+ * 1997, the "Local Thickness" of Fiji / BoneJ), exact in integers, in a band of rmax = 1 .. 32 voxels.  S = the set voxels of a whole-grid
+ * frame, n <= 1024, n % 32 == 0; voxel coordinates are integers, |p - c|^2 = dx^2 + dy^2 + dz^2.
+ *   capped inscribed radius   D(c) = min(E(c), W(c), rmax^2) for c in S, where
+ *                 E = vp_edt with VP_EDT_SEEDS_UNSET: the exact squared distance to the nearest unset voxel, VP_EDT_NONE on a grid
+ *                 without an unset voxel (the min takes care of that);
+ *                 W(c) = (1 + min(x, n-1-x, y, n-1-y, z, n-1-z))^2: the squared distance to the nearest voxel OUTSIDE the grid.
+ *                 OUTSIDE THE GRID COUNTS AS EMPTY HERE: the object ends at the frame's wall.  (vp_edt_morph's erode treats the
+ *                 outside as no seed, i.e. as solid; this operator does not.)  So every set voxel has 1 <= D <= rmax^2, and the open
+ *                 ball of squared radius D(c) around c holds set voxels only and stays inside the grid.
+ *   thickness     T2(p) = max { D(c) : c in S, |p - c|^2 < D(c) } for p in S, and 0 for p not in S.  The comparison is strict.  uint32, x
+ *                 fastest, 4 n^3 bytes, like d_dist2.  The local thickness in voxels is 2 sqrt(T2); callers multiply by the voxel size.
+ *                 A region thicker than 2 rmax reads rmax^2: saturated.  The operator is a band, like vp_mesh_distance.
+ *   thin grid     bit p = p in S && T2(p) < thin2, thin2 in 0 .. rmax^2 (0: the empty grid).  A grid like any other: vp_components_*,
+ *                 vp_morph, vp_extract, vp_surfnets, ... read it unchanged.  A thickness of W whole voxels is thin iff 4 T2 < W^2, i.e.
+ *                 thin2 = ceil(W^2 / 4).
+ * Integer arithmetic and a maximum over a set: numpy, the C++ host form, VP_ALGO_NAIVE and VP_ALGO_TILED give the same bytes whatever any
+ * of them culls.  Facts (tests/test_thickness_cpu.py holds them on hand cases and random grids):
+ *   slab read-out     a slab w voxels wide, far from the walls, reads T2 = ceil(w / 2)^2 (w = 1 .. 7: 1, 1, 4, 4, 9, 9, 16): the discrete
+ *                     read-out of a w-voxel wall is 2 ceil(w / 2).
+ *   bounds            T2 >= D pointwise; max T2 = max D; T2 = 0 exactly on the unset voxels.
+ *   saturation        {T2 = rmax^2} = {p : the VP_EDT_SEEDS_SET transform of the seed set {c in S : min(E, W) >= rmax^2} is < rmax^2 at
+ *                     p}: the saturated region is one more separable transform and needs no ball.
+ *   cap consistency   T2 at rmax <= min(T2 at r', rmax^2) for r' > rmax, with equality wherever T2 at r' < rmax^2; elsewhere the
+ *                     inequality can be strict (a ball larger than rmax, cut down to rmax, covers less).
+ *   opening           for every t that occurs as a value of D, every voxel of {VP_EDT_SEEDS_SET of {D >= t} < t} -- the opening by the
+ *                     open ball of squared radius t -- has T2 >= t.
+ * Gap or channel width is the same call on the complemented words; the frame's wall then acts as solid.
+ *   vp_thickness         builds T2 and the thin grid into grow-only buffers that the CONTEXT owns; vp_ctx_release frees them.  Enqueues
+ *                        only, once the buffers have grown; with h_thin_count != NULL it BLOCKS and stores the number of thin voxels.
+ *   vp_thickness_result  pointers to the last result and the side it is for; any argument may be NULL.  Before a build and after a
+ *                        release: NULL pointers and side 0.
+ *   vp_thickness_host    host in, host out (the grid staged through a workspace slot); h_t2 or h_thin may be NULL, not both.
+ * A slab frame and n > 1024: VP_ERR_UNSUPPORTED.  Null ctx / f / words, words that are not 16-byte aligned, d_words overlapping a buffer the
+ * context writes in this call (its result buffers among them: copy the last thin grid before measuring it), rmax outside 1 .. 32,
+ * thin2 > rmax^2, an unknown algo: VP_ERR_INVALID.  A refusal is decided before anything is touched and leaves the previous result as it
+ * was.  The result buffers are outputs like any other: a pending vp_jfa_start / vp_extract_count / vp_surfnets_count of a grid they
+ * overlap is dropped.
+ *   algo: VP_ALGO_NAIVE -- the UNSET transform, then one thread per set voxel c paints its ball with atomicMax(T2[p], D(c)), then a
+ *   streaming pass for the thin bits; its cost is the sum of the ball volumes: the check, not the product.  VP_ALGO_TILED -- the transform,
+ *   D as uint16 with a summary per 8 x 8 x 8 brick, the saturated region by the identity above, then one workgroup per brick that has a set,
+ *   unsaturated voxel gathers from the neighbour bricks within rmax - 1 voxels (bricks and candidates whose balls cannot reach the brick
+ *   are skipped; survivors go through an LDS batch), no atomics on the field; a streaming fill writes the other bricks.  Scratch of the
+ *   context (grow-only, freed by vp_ctx_release): the distance volume(s) of vp_edt_morph, 2 n^3 + n^3 / 4 bytes and 8 bytes per brick.
+ *   Timing books under existing keys: the transforms under VP_K_EDT_X / _Y / _Z (NAIVE: _Y_NAIVE / _Z_NAIVE), the cap, threshold and
+ *   thin-grid passes under VP_K_EDT_THRESH, the brick kernel under VP_K_MD_BRICK, the scatter under VP_K_MD_NAIVE, the fill under
+ *   VP_K_MD_FILL, the count under VP_K_MD_SPLIT. */
+int vp_thickness(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32_t rmax, uint32_t thin2, int algo,
+                 uint64_t* h_thin_count /* may be NULL; BLOCKS when given */);
+int vp_thickness_result(vp_ctx* ctx, uint32_t** d_t2, uint32_t** d_thin, uint32_t* h_n);
+int vp_thickness_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t rmax, uint32_t thin2, int algo,
+                      uint32_t* h_t2, uint32_t* h_thin /* either may be NULL, not both */, uint64_t* h_thin_count /* may be NULL */);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
