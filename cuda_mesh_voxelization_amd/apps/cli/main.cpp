@@ -35,6 +35,10 @@
 //                            writes PREFIX.thick.u32 (n^3 values) and, with W, PREFIX.thin.u32 (a grid).  One device only (-g > 1 is refused)
 //         --thin-only        (extension, with --thickness R:W) the grid is replaced by the thin grid before the exports that follow and -s:
 //                            -e writes out/thin_<type>_<output>, cubes or --surface-nets, and -d PREFIX.grid.u32 holds it
+//         --octree           (extension) sparse voxel octree of the FINAL grid -- where --thickness sits: after the voxelization, --morph, --fill,
+//                            CSG and --thin-only (include/vphip.h, vp_octree; vox/octree.h): writes out/<output stem>_<type>_out.svo, the
+//                            same bytes for every -t, and prints the nodes per level, the bytes and the ratio to the n^3 / 8 bytes of the
+//                            grid.  n % 32 == 0, n <= 1024.  One device only (-g > 1 is refused)
 //         --fill             (extension) after each mesh's voxelization (solid or --conservative), fill its interior: every empty voxel
 //                            that no 6-connected path of empty voxels joins to the grid boundary is set (include/vphip.h,
 //                            vp_fill_interior).  Runs before export, CSG and sdf, so --conservative --fill gives the solid of an open
@@ -91,6 +95,7 @@
 #include "mesh/mesh.h"
 #include "mesh/mesh_io.h"
 #include "proc_utils.h"
+#include "vox/octree.h"
 #include "vox/vox.h"
 #include "vp_runtime.h"
 
@@ -121,6 +126,7 @@ struct Options {
     bool fill = false;
     unsigned thickness = 0, thinWidth = 0;                  // --thickness RMAX[:W]: band in voxels, 0 = not asked for; W = 0: no thin grid
     bool thinOnly = false;
+    bool octree = false;                                    // --octree: out/<output stem>_<type>_out.svo of the final grid
     bool exactSdf = false;
     int meshSdf = 0;                                        // --mesh-sdf BAND: band in voxels, 0 = not asked for
     bool isoNets = false;                                   // --iso-nets LEVEL[:ITERS]: level in voxels, relaxation steps
@@ -219,6 +225,9 @@ const char* kUsage =
     "                        -d PREFIX adds PREFIX.thick.u32 and PREFIX.thin.u32.  One device only: not with -g > 1 (extension)\n"
     "      --thin-only       With --thickness RMAX:W: replace the grid by the thin grid, so that -e (out/thin_<type>_<output>), -s and\n"
     "                        -d see the thin regions (extension)\n"
+    "      --octree          Sparse voxel octree of the final grid (after --morph, --fill, CSG and --thin-only): writes\n"
+    "                        out/<output stem>_<type>_out.svo, the same bytes for every -t, and prints its size against the grid's.\n"
+    "                        n a multiple of 32 up to 1024.  One device only: not with -g > 1 (extension)\n"
     "      --conservative    Surface voxelization: a voxel is set iff its closed box overlaps a triangle (any mesh, open or\n"
     "                        closed; the default solid rule needs closed meshes); CSG, export, sdf and dumps work on it unchanged.\n"
     "                        One device only: not with -g > 1 (extension)\n"
@@ -257,7 +266,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -298,10 +307,10 @@ Options Parse(int argc, char** argv)
             o.windingLevel = static_cast<float>(lv); o.windingBeta = static_cast<float>(bt);
             continue;
         }
-        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X' || key == 'O';
+        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X' || key == 'O' || key == 'Y';
         if (isSwitch) {
             const bool v = !hasValue || value == "true" || value == "1";
-            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else if (key == 'X') o.exactSdf = v; else if (key == 'O') o.thinOnly = v; else o.help = v;
+            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else if (key == 'X') o.exactSdf = v; else if (key == 'O') o.thinOnly = v; else if (key == 'Y') o.octree = v; else o.help = v;
             continue;
         }
         if (!hasValue) {
@@ -421,6 +430,18 @@ void Thickness(unsigned rmax, unsigned width, const HostVoxelsGrid<gridType>& gr
     if (width) std::printf("thin voxels (thinner than %u voxels, T2 < %u): %llu\n", width, thin2, static_cast<unsigned long long>(count));
 }
 
+// --octree: the tree of `grid` to `path`; prints what the flag promises
+template <Types T>
+void OctreeOut(const HostVoxelsGrid<gridType>& grid, const std::string& path)
+{
+    const VOX::Octree tree = VOX::BuildOctree<T>(grid);
+    cpuAssert(VOX::WriteOctree(path, tree), "Error writing " + path + "\n");
+    const double gridBytes = static_cast<double>(tree.n) * tree.n * tree.n / 8.0;
+    std::printf("octree: n %u, P %u, nodes %zu, per level [", tree.n, tree.P, tree.NodeCount());
+    for (uint32_t l = 0; l < tree.L; ++l) std::printf("%s%u", l ? ", " : "", tree.levelOffset[l + 1] - tree.levelOffset[l]);
+    std::printf("], %zu bytes, grid %.0f bytes, ratio %.2f, %s\n", tree.Bytes(), gridBytes, gridBytes / static_cast<double>(tree.Bytes()), path.c_str());
+}
+
 template <Types T>
 void Csg(CSG::Op op, HostVoxelsGrid<gridType>& a, HostVoxelsGrid<gridType>& b)
 {
@@ -477,6 +498,8 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.winding && opt.gpus > 1), "--winding runs on one device: -g must be 1\n");
     cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
     cpuAssert(!(opt.thickness && opt.gpus > 1), "--thickness runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.octree && opt.gpus > 1), "--octree runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.octree && (opt.numVoxels % 32 != 0 || opt.numVoxels > 1024)), "--octree needs -n to be a multiple of 32 up to 1024\n");
     cpuAssert(!(opt.thinOnly && !(opt.thickness && opt.thinWidth)), "--thin-only needs --thickness RMAX:W: the thin grid is that of a width\n");
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
     cpuAssert(!(opt.exactSdf && !opt.sdf), "--exact-sdf needs -s: it chooses how the distance field is computed\n");
@@ -528,7 +551,7 @@ int main(int argc, char** argv)
     HostGrid<uint32_t> thick;
     HostVoxelsGrid<gridType> thinGrid;
     const std::string typeName = GetTypesString(TYPE);
-    if (EXPORT) std::filesystem::create_directories("out");
+    if (EXPORT || opt.octree) std::filesystem::create_directories("out");
 
     for (unsigned iter = 0; iter < opt.iterations; ++iter) {
         for (size_t i = 0; i < meshes.size(); ++i) {
@@ -605,6 +628,16 @@ int main(int argc, char** argv)
                     GridMesh(GPU, opt.surfaceOnly, opt.surfaceNets, grids[0].View(), outMesh);
                     cpuAssert(ExportMesh("out/thin_" + typeName + "_" + opt.output, outMesh), "Error in " + opt.output + " export (thin)");
                 }
+            }
+        }
+
+        if (opt.octree) {
+            const std::string path = "out/" + std::filesystem::path(opt.output).stem().string() + "_" + typeName + "_out.svo";
+            switch (TYPE) {
+                case Types::SEQUENTIAL: OctreeOut<Types::SEQUENTIAL>(grids[0], path); break;
+                case Types::OPENMP:     OctreeOut<Types::OPENMP>(grids[0], path); break;
+                case Types::NAIVE:      OctreeOut<Types::NAIVE>(grids[0], path); break;
+                case Types::TILED:      OctreeOut<Types::TILED>(grids[0], path); break;
             }
         }
 

@@ -69,6 +69,7 @@ SYMBOLS = [
     "vp_mesh_distance", "vp_mesh_distance_host", "vp_mesh_distance_stats",
     "vp_winding", "vp_winding_result", "vp_winding_host",
     "vp_thickness", "vp_thickness_result", "vp_thickness_host",
+    "vp_octree", "vp_octree_result", "vp_octree_expand", "vp_octree_expand_result", "vp_octree_host", "vp_octree_expand_host", "vp_octree_validate_host",
 ]
 
 
@@ -204,6 +205,13 @@ def lib():
         "vp_thickness": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
         "vp_thickness_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32)]),
         "vp_thickness_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_octree": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+        "vp_octree_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64), _vp, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_octree_expand": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint64, ctypes.c_int]),
+        "vp_octree_expand_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_octree_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _vp, _vp]),
+        "vp_octree_expand_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint64, ctypes.c_int, _vp]),
+        "vp_octree_validate_host": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint32]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -564,7 +572,58 @@ class Context:
         check(lib().vp_thickness_result(self._h, ctypes.byref(t), ctypes.byref(g), ctypes.byref(n)))
         return t.value or 0, g.value or 0, int(n.value)
 
+    def octree(self, frame: Frame, d_words: int, algo: int = ALGO_TILED) -> int:
+        """Sparse voxel octree of a whole grid (n <= 1024) into buffers the context owns; octree_result() hands them out.  Blocks once (the
+        node count is read back) and returns it."""
+        m = ctypes.c_uint64()
+        check(lib().vp_octree(self._h, ctypes.byref(frame), _vp(d_words or None), algo, ctypes.byref(m)))
+        return int(m.value)
+
+    def octree_result(self):
+        """(d_nodes, M, level_offset, full_leaves, n) of the last octree(): the device pointer as an int (0 where there is none), the node
+        count, two lists of 11 and the side they are for.  Valid until the next octree(), release() or close()."""
+        d, m, n = _vp(), ctypes.c_uint64(), ctypes.c_uint32()
+        lo, fl = (ctypes.c_uint32 * 11)(), (ctypes.c_uint32 * 11)()
+        check(lib().vp_octree_result(self._h, ctypes.byref(d), ctypes.byref(m), lo, fl, ctypes.byref(n)))
+        return d.value or 0, int(m.value), list(lo), list(fl), int(n.value)
+
+    def octree_expand(self, frame: Frame, d_nodes: int, nodes: int, algo: int = ALGO_TILED):
+        """A tree of `nodes` records back into the bit grid of the frame, a grid the context owns; octree_expand_result() hands it out.
+        Enqueues only, once the grid has grown."""
+        check(lib().vp_octree_expand(self._h, ctypes.byref(frame), _vp(d_nodes or None), nodes, algo))
+
+    def octree_expand_result(self):
+        """(d_words, n) of the last octree_expand(): the device pointer as an int (0 where there is none) and the side it is for"""
+        d, n = _vp(), ctypes.c_uint32()
+        check(lib().vp_octree_expand_result(self._h, ctypes.byref(d), ctypes.byref(n)))
+        return d.value or 0, int(n.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
+    def octree_host(self, frame: Frame, h_words, algo: int = ALGO_TILED, capacity=None):
+        """numpy in, numpy out: (nodes uint32[M, 2], level_offset uint32[11], full_leaves uint32[11]).  The first call asks for the count
+        (capacity 0 is refused with the count stored); `capacity` overrides the second call's room."""
+        np = __import__("numpy")
+        m = ctypes.c_uint64()
+        lo, fl = np.zeros(11, np.uint32), np.zeros(11, np.uint32)
+        if capacity is None:
+            rc = lib().vp_octree_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), algo, None, 0, ctypes.byref(m), None, None)
+            if rc != 10001 or m.value == 0:                     # VP_ERR_INVALID with the count stored: the capacity
+                check(rc)
+            capacity = int(m.value)
+        nodes = np.zeros((capacity, 2), np.uint32)
+        check(lib().vp_octree_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), algo, nodes.ctypes.data_as(_vp), capacity,
+                                   ctypes.byref(m), lo.ctypes.data_as(_vp), fl.ctypes.data_as(_vp)))
+        return nodes[:int(m.value)], lo, fl
+
+    def octree_expand_host(self, frame: Frame, h_nodes, algo: int = ALGO_TILED):
+        """numpy in, numpy out: the grid words of the frame; the tree is validated on the host first."""
+        np = __import__("numpy")
+        h_nodes = np.ascontiguousarray(h_nodes, np.uint32)
+        words = np.empty(frame.voxels // 32, np.uint32)
+        check(lib().vp_octree_expand_host(self._h, ctypes.byref(frame), h_nodes.ctypes.data_as(_vp), h_nodes.size // 2, algo,
+                                          words.ctypes.data_as(_vp)))
+        return words
+
     def thickness_host(self, frame: Frame, h_words, rmax: int, thin2: int = 0, algo: int = ALGO_TILED):
         """numpy in, numpy out: (T2 uint32[n^3], thin words uint32[n^3 / 32], thin count)."""
         np = __import__("numpy")

@@ -214,7 +214,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
                        &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list,
                        &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads,
                        &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree,
-                       &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum };
+                       &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum,
+                       &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt, &ctx->oc_grid };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -228,6 +229,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->md_host) (void)hipHostFree(ctx->md_host);
     if (ctx->wn_host) (void)hipHostFree(ctx->wn_host);
     if (ctx->th_host) (void)hipHostFree(ctx->th_host);
+    if (ctx->oc_host) (void)hipHostFree(ctx->oc_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -312,6 +314,10 @@ int vp_ctx_release(vp_ctx* ctx)
     ctx->wn_n = 0;
     for (Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum }) release(*b);                   // vp_thickness: scratch and result
     ctx->th_n = 0;
+    for (Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt }) release(*b);                   // vp_octree: scratch and result
+    release(ctx->oc_grid);                                         // vp_octree_expand: result
+    ctx->oc_n = ctx->oc_grid_n = 0;
+    ctx->oc_count = 0;
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -1226,6 +1232,77 @@ int vp_thickness_result(vp_ctx* ctx, uint32_t** d_t2, uint32_t** d_thin, uint32_
     return 0;
 }
 
+// ---- sparse voxel octree ---------------------------------------------------------------------------
+// what the octree calls share: whole grids up to n = 1024 and the algo
+static int check_octree(const vp_frame* f, const char* who, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_whole(f, who));
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
+    return check_algo(who, algo);
+}
+
+int vp_octree(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint64_t* h_nodes)
+{
+    const char* who = "vp_octree";
+    if (!ctx || !f || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_octree(f, who, algo));
+    VP_TRY(check_aligned(who, {d_words}));
+    // the grid is read while every buffer of the call is written: it may lie in none of them (the context's own nodes among them)
+    for (const Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt })
+        VP_TRY(check_disjoint(who, "a buffer of the context", d_words, vp_grid_words(f) * 4, b->ptr, b->bytes));
+    // the context's own buffers are outputs like any other: what was recorded about their bytes is gone, before and after they grow
+    for (Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt }) grid_written(ctx, b->ptr, b->bytes);
+    const int rc = launch_octree(ctx, make_frame(f), d_words, algo, h_nodes);
+    for (Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt }) grid_written(ctx, b->ptr, b->bytes);
+    return rc;
+}
+
+int vp_octree_result(vp_ctx* ctx, uint32_t** d_nodes, uint64_t* h_nodes, uint32_t* h_level_offset, uint32_t* h_full_leaves, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_octree_result: null ctx");
+    const bool any = ctx->oc_n != 0;
+    if (d_nodes) *d_nodes = any ? (uint32_t*)ctx->oc_nodes.ptr : nullptr;
+    if (h_nodes) *h_nodes = any ? ctx->oc_count : 0;
+    for (int l = 0; l < 11; ++l) {
+        if (h_level_offset) h_level_offset[l] = any ? ctx->oc_level_offset[l] : 0u;
+        if (h_full_leaves) h_full_leaves[l] = any ? ctx->oc_full_leaves[l] : 0u;
+    }
+    if (h_n) *h_n = ctx->oc_n;
+    return 0;
+}
+
+int vp_octree_expand(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_nodes, uint64_t nodes, int algo)
+{
+    const char* who = "vp_octree_expand";
+    if (!ctx || !f || !d_nodes) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_octree(f, who, algo));
+    if (nodes < 1 || nodes >= (1ull << 28)) return set_error(VP_ERR_INVALID, "%s: %llu nodes (1 .. 2^28 - 1)", who, (unsigned long long)nodes);
+    VP_TRY(check_aligned(who, {d_nodes}));
+    // the nodes are read while the context's grid is written: they may not lie in it
+    if (overlaps(d_nodes, nodes * 8, ctx->oc_grid.ptr, ctx->oc_grid.bytes)) return set_error(VP_ERR_INVALID, "%s: d_nodes overlaps the context's grid", who);
+    // the context's own grid is an output like any other: what was recorded about its bytes is gone, before and after it grows
+    grid_written(ctx, ctx->oc_grid.ptr, ctx->oc_grid.bytes);
+    ctx->oc_grid_n = 0;
+    VP_TRY(reserve(ctx, ctx->oc_grid, vp_grid_words(f) * 4, false));
+    grid_written(ctx, ctx->oc_grid.ptr, ctx->oc_grid.bytes);
+    VP_TRY(launch_octree_expand(ctx, make_frame(f), d_nodes, nodes, (uint32_t*)ctx->oc_grid.ptr, algo));
+    ctx->oc_grid_n = f->n;
+    return 0;
+}
+
+int vp_octree_expand_result(vp_ctx* ctx, uint32_t** d_words, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_octree_expand_result: null ctx");
+    if (d_words) *d_words = ctx->oc_grid_n ? (uint32_t*)ctx->oc_grid.ptr : nullptr;
+    if (h_n) *h_n = ctx->oc_grid_n;
+    return 0;
+}
+
+int vp_octree_validate_host(const uint32_t* h_nodes, uint64_t nodes, uint32_t n) { return octree_validate(h_nodes, nodes, n); }
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1359,6 +1436,35 @@ int vp_thickness_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, u
     VP_TRY(vp_thickness(ctx, f, (const uint32_t*)dw, rmax, thin2, algo, h_thin_count));
     if (h_t2) VP_TRY(vp_download(ctx, h_t2, ctx->th_t2.ptr, vp_grid_voxels(f) * 4));
     return h_thin ? vp_download(ctx, h_thin, ctx->th_thin.ptr, vp_grid_words(f) * 4) : 0;
+}
+
+int vp_octree_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int algo, uint32_t* h_nodes, uint64_t capacity, uint64_t* h_count,
+                   uint32_t* h_level_offset, uint32_t* h_full_leaves)
+{
+    const char* who = "vp_octree_host";
+    if (!ctx || !f || !h_words || !h_count || (!h_nodes && capacity)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_octree(f, who, algo));
+    void* dw = nullptr;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, vp_grid_words(f) * 4, &dw));
+    VP_TRY(vp_upload(ctx, dw, h_words, vp_grid_words(f) * 4));
+    VP_TRY(vp_octree(ctx, f, (const uint32_t*)dw, algo, h_count));
+    VP_TRY(vp_octree_result(ctx, nullptr, nullptr, h_level_offset, h_full_leaves, nullptr));
+    if (*h_count > capacity) return set_error(VP_ERR_INVALID, "%s: capacity %llu below the %llu nodes of the tree", who,
+                                              (unsigned long long)capacity, (unsigned long long)*h_count);
+    return vp_download(ctx, h_nodes, ctx->oc_nodes.ptr, *h_count * 8);
+}
+
+int vp_octree_expand_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_nodes, uint64_t nodes, int algo, uint32_t* h_words)
+{
+    const char* who = "vp_octree_expand_host";
+    if (!ctx || !f || !h_nodes || !h_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_octree(f, who, algo));
+    VP_TRY(octree_validate(h_nodes, nodes, f->n));                 // nothing that fails the check reaches the device
+    void* dn = nullptr;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, nodes * 8, &dn));
+    VP_TRY(vp_upload(ctx, dn, h_nodes, nodes * 8));
+    VP_TRY(vp_octree_expand(ctx, f, (const uint32_t*)dn, nodes, algo));
+    return vp_download(ctx, h_words, ctx->oc_grid.ptr, vp_grid_words(f) * 4);
 }
 
 int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,

@@ -139,6 +139,19 @@ struct vp_ctx {
     vp::Buffer th_t2, th_thin, th_d16, th_sat, th_sum;
     uint64_t* th_host = nullptr;
     uint32_t th_n = 0;
+    // sparse voxel octree (octree.hip): the nodes of the last vp_octree (8 bytes each, sized from the count), which the context owns and
+    // vp_octree_result hands out; the device summary (level_offset | full_leaves | nodes per level), the state bytes and ranks of the levels
+    // (NAIVE: all of them; TILED: those above the 32^3 blocks) and TILED's per-block counts and offsets; the pinned host words the summary
+    // comes back through and its copy; oc_n = the side of the grid the result is for, 0: none.  The five buffers are freed by vp_ctx_release
+    vp::Buffer oc_nodes, oc_sum, oc_state, oc_rank, oc_cnt;
+    // the grid of the last vp_octree_expand (n^3 / 8 bytes), which the context owns and vp_octree_expand_result hands out; oc_grid_n = its
+    // side, 0: none.  Freed by vp_ctx_release
+    vp::Buffer oc_grid;
+    uint32_t oc_grid_n = 0;
+    uint32_t* oc_host = nullptr;
+    uint32_t oc_n = 0;
+    uint64_t oc_count = 0;
+    uint32_t oc_level_offset[11] = {}, oc_full_leaves[11] = {};
 };
 
 namespace vp {
@@ -210,6 +223,11 @@ int launch_edt_thresh(vp_ctx* ctx, uint32_t n, const uint32_t* d_dist, uint32_t*
 // thickness.hip: local thickness of a whole grid -- T2 and the thin grid -- into the context's own buffers (enqueues only once they have
 // grown, unless h_thin_count asks for the count)
 int launch_thickness(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint32_t rmax, uint32_t thin2, int algo, uint64_t* h_thin_count);
+// octree.hip: the sparse voxel octree of a whole grid into the context's own buffers (blocks once: the node count is read back), a tree back
+// into a grid (enqueues only) and the structural check of a tree on the host
+int launch_octree(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int algo, uint64_t* h_nodes);
+int launch_octree_expand(vp_ctx* ctx, const Frame& f, const uint32_t* d_nodes, uint64_t nodes, uint32_t* d_words, int algo);
+int octree_validate(const uint32_t* h_nodes, uint64_t nodes, uint32_t n);
 // meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,

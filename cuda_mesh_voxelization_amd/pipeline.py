@@ -202,6 +202,24 @@ class Engine:
         return (torch.as_tensor(_DeviceView(dt, frame.voxels, "<i4", self), device=self.device),
                 torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device))
 
+    def octree(self, frame: Frame, words, algo: int = ALGO_TILED):
+        """Sparse voxel octree of a grid (n <= 1024): returns (nodes, level_offset, full_leaves) -- an int32 tensor of M x 2 words, the
+        records (valid | full << 8, index of the first mixed child) breadth-first and in Morton order within a level, and two lists of 11:
+        the running sums of the per-level node counts and the full children per level (include/vphip.h, vp_octree).  `nodes` is a VIEW of
+        a buffer the context owns: it is overwritten by the next octree() and dies with release() / close() -- clone() what has to live
+        longer.  Blocks once: the node count is read back."""
+        m = self.ctx.octree(frame, words.data_ptr(), algo)
+        d, _, lo, fl, _ = self.ctx.octree_result()
+        return torch.as_tensor(_DeviceView(d, 2 * m, "<i4", self), device=self.device).view(m, 2), lo, fl
+
+    def octree_expand(self, frame: Frame, nodes, algo: int = ALGO_TILED):
+        """The bit grid of the frame from a tree (a tensor of M x 2 words, as octree() returns it or uploaded from a validated file), ready
+        for components(), morph(), surface_nets() ...  A VIEW of a grid the context owns: it is overwritten by the next octree_expand() and
+        dies with release() / close() -- clone() what has to live longer.  Enqueues only."""
+        self.ctx.octree_expand(frame, nodes.data_ptr(), nodes.numel() // 2, algo)
+        d, _ = self.ctx.octree_expand_result()
+        return torch.as_tensor(_DeviceView(d, frame.voxels // 32, "<i4", self), device=self.device)
+
     def csg(self, a, b, op: int):
         self.ctx.csg(a.data_ptr(), b.data_ptr(), a.numel(), op)
         return a

@@ -539,6 +539,69 @@ int vp_thickness_result(vp_ctx* ctx, uint32_t** d_t2, uint32_t** d_thin, uint32_
 int vp_thickness_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t rmax, uint32_t thin2, int algo,
                       uint32_t* h_t2, uint32_t* h_thin /* either may be NULL, not both */, uint64_t* h_thin_count /* may be NULL */);
 
+/* ---- sparse voxel octree: build from any grid, expand back (no reference counterpart) ---------------------------
+ * The compact, hierarchical form of a bit grid.  Whole-grid frames, n % 32 == 0, n <= 1024; any grid of this library goes in.
+ *   geometry      The tree covers the cube of side P = NextPow2(n), L = log2 P levels, 5 <= L <= 10.  Voxels outside the grid are empty
+ *                 (n = 96: P = 128; n = 160: P = 256).  A level-l cell, l = 0 .. L, has side P >> l.  A cell is EMPTY if it has no set
+ *                 voxel, FULL if all of its voxels are set (possible only for a cell inside the grid), else MIXED.
+ *   stored nodes  one for the root, always, and one for every mixed cell of the levels 1 .. L - 1.  Full and empty cells are never stored:
+ *                 full subtrees are pruned.
+ *   order         breadth-first, level by level; within a level in ascending Morton code of the cell coordinates (bit i of x -> bit 3 i,
+ *                 of y -> 3 i + 1, of z -> 3 i + 2).  Child index c = x + 2 y + 4 z, so the children of a node are consecutive and in c
+ *                 order.  The order is unique: two trees of the same grid are the same bytes.
+ *   record        two uint32, 8 bytes.  masks: bits 0 .. 7 `valid` (child c is not empty), bits 8 .. 15 `full` (child c is full), full a
+ *                 subset of valid, the upper 16 bits 0.  child: the absolute index of the first stored (mixed) child, 0 when there is none
+ *                 (index 0 is the root and never a child).  The stored children are the set bits of valid & ~full, found at child + rank.
+ *                 At level L - 1 the children are voxels: valid == full == the 2 x 2 x 2 bits and child == 0.
+ *   summary       uint32 level_offset[11]: entries 0 .. L are the running sums of the per-level node counts, the rest repeat M, the total.
+ *                 uint32 full_leaves[11]: the full children counted per level of their parent, so that the sum over l of
+ *                 full_leaves[l] * (P >> (l + 1))^3 is the number of set voxels.  M < 2^28.
+ * Facts (tests/test_octree_cpu.py): the empty grid is one node with masks 0; the full 32^3 or 64^3 grid one node with masks 0xFFFF; the
+ * full 96^3 grid has the levels [1, 7, 0, 0, 0, 0, 0]; expand(build(g)) == g; build is injective; a grid placed in a larger frame with the
+ * same P has the same tree.  Worst case (noise): M <= (8^L - 1) / 7 nodes, about 1.14 P^3 bytes -- the node buffer is sized from the count.
+ *   vp_octree               builds the tree into grow-only buffers that the CONTEXT owns; vp_ctx_release frees them.  BLOCKS once: the
+ *                           summary is read back and the node buffer sized exactly.  h_nodes (may be NULL) receives M.
+ *   vp_octree_result        the last result: the device nodes, M, the two summaries (11 entries each) and the side it is for; any argument
+ *                           may be NULL.  Before a build and after a release: NULL, 0, zeros and side 0.
+ *   vp_octree_expand        a tree back into a bit grid of side f->n (P from f->n: a tree built at n = 96 expands into n = 128 as the
+ *                           zero-padded grid), into a grow-only grid that the CONTEXT owns, like the nodes (every output of this
+ *                           section is the context's; vp_ctx_release frees it).  Overwrites every word; enqueues only, once the grid
+ *                           has grown.
+ *   vp_octree_expand_result the grid of the last vp_octree_expand and its side; either argument may be NULL.  Before an expand and after
+ *                           a release: NULL and side 0.  A grid like any other: copy it before the next expand overwrites it.  The kernels read a child only if its index is below
+ *                           `nodes` (anything else counts as empty) and descend L levels at most: whatever the bytes are, they neither
+ *                           read outside the buffer nor loop.  What they produce from bytes that are not a tree is unspecified.
+ *   vp_octree_host          host in, host out (the grid staged through a workspace slot).  *h_count receives M; a capacity below M returns
+ *                           VP_ERR_INVALID without writing h_nodes (call again with room for *h_count records).
+ *   vp_octree_expand_host   validates (below) before anything goes to the device, then expands.
+ *   vp_octree_validate_host pure CPU, no context: 0 for a well-formed tree of a grid of side n, else VP_ERR_INVALID (vp_last_error says
+ *                           which node): upper mask bits, full not within valid, a stored cell of a level >= 1 that is empty or full, a
+ *                           mixed "voxel", a child that is not exactly the running sum of the stored children so far (out of range included),
+ *                           levels that do not end exactly at M, a full child that pokes out of the grid, a valid child outside it.
+ *                           Everything that comes from a file goes through it before it may reach a device.
+ * A slab frame and n > 1024: VP_ERR_UNSUPPORTED.  Null ctx / f / pointers, buffers that are not 16-byte aligned, an unknown algo, d_words
+ * overlapping a buffer the context writes in vp_octree (its own nodes among them: copy them first), d_nodes overlapping the context's
+ * grid in vp_octree_expand, nodes outside 1 .. 2^28 - 1: VP_ERR_INVALID.  A refusal is decided before anything is touched and leaves the previous
+ * result as it was.
+ *   algo: VP_ALGO_NAIVE -- a state byte per cell of every level in Morton order, filled bottom-up by one thread per cell, per level a
+ *   one-workgroup scan of the stored flags, then one thread per cell writes the record of a stored one; memory about 5.7 bytes per side-2
+ *   cell (0.7 P^3).  VP_ALGO_TILED -- one workgroup per 32^3 block of bits staged in LDS reduces the five levels inside the block (sides 2
+ *   .. 32) from any / all bits; a count launch, one workgroup for the levels above the blocks and every scan, a write launch that repeats
+ *   the reduction and stores each record at level_offset + block offset + rank; no atomics.  Expand: NAIVE one thread per voxel, TILED
+ *   one lane per word (the walk to the side-32 cell, then at most 31 node visits along x).
+ *   Timing books under existing keys (vp_prof_select's mask is full): TILED count under VP_K_MD_COUNT, the upper levels and every scan
+ *   under VP_K_MD_SCAN, the writes under VP_K_MD_WRITE; NAIVE state volumes under VP_K_MD_PREFILL, its scans under VP_K_MD_SCAN, its
+ *   writes under VP_K_MD_NAIVE; expand (both) under VP_K_MD_FILL. */
+int vp_octree(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint64_t* h_nodes /* may be NULL */);
+int vp_octree_result(vp_ctx* ctx, uint32_t** d_nodes, uint64_t* h_nodes, uint32_t* h_level_offset /* 11 */, uint32_t* h_full_leaves /* 11 */,
+                     uint32_t* h_n);
+int vp_octree_expand(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_nodes, uint64_t nodes, int algo);
+int vp_octree_expand_result(vp_ctx* ctx, uint32_t** d_words, uint32_t* h_n);
+int vp_octree_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int algo, uint32_t* h_nodes, uint64_t capacity,
+                   uint64_t* h_count, uint32_t* h_level_offset /* 11, may be NULL */, uint32_t* h_full_leaves /* 11, may be NULL */);
+int vp_octree_expand_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_nodes, uint64_t nodes, int algo, uint32_t* h_words);
+int vp_octree_validate_host(const uint32_t* h_nodes, uint64_t nodes, uint32_t n);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
