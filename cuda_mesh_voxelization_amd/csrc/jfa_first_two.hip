@@ -1,4 +1,9 @@
-// jfa_first_two.hip -- the passes k = n/2 and k = n/4 of a whole grid in ONE launch, straight from the border bitmask (see the kernel).
+// jfa_first_two.hip -- the passes k = n/2 and k = n/4 of a whole grid in ONE launch, straight from the border bitmask.  Two kernels:
+//   jfa_first_two_rows   whole grids whose side is a power of two from 128 to 1024 (4-byte ids): tiles of whole rows, the answer taken per
+//                        lattice from a bitwise census of the border words, only the lattices where seeds compete evaluated
+//   jfa_first_two        every other caller -- the cyclic distribution, the compact ids above n = 1024, sides off the powers of two, n < 128:
+//                        tiles of 4 x 4 x 4 chain positions x 16 / 32 residues, seeds proposing themselves through LDS keys
+// (launch_win_first_two at the end of the file chooses.)
 #include "jfa_common.h"
 
 namespace vp {
@@ -330,6 +335,215 @@ jfa_first_two(Frame f, const uint32_t* __restrict__ border, typename ID::T* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------ whole-row tiles (powers of two, 4-byte ids)
+// The same two passes on a tile of WHOLE ROWS: one residue pair (ry, rz) mod k = n/4 -- the 16 rows y = ry + b k, z = rz + c k, each n voxels
+// wide, that is the k lattices (x mod k) x (ry, rz) -- and the answer taken per LATTICE instead of per tile:
+//   census    bitwise on the border words: for 32 residues at a time the 64 words (16 rows x 4 segments) that hold their bits are folded
+//             with two saturating masks (two |= one & w, one |= w) by a wave whose lane is the chain position, six cross-lane steps.
+//             `one & ~two` = lattices of a single border voxel, whose answer is that voxel's id in all 64 voxels (see jfa_first_two):
+//             the lanes whose word holds the bit write it to latId[residue]; empty lattices get "none".
+//   contested `two`: the lattices of two or more border voxels get both passes evaluated exactly, one wave per lattice, lane = chain
+//             position c b a: pass n/2 over the <= 8 candidates {a, a ^ 2} x .. (their border bits are one ballot), pass n/4 over the <= 27,
+//             the neighbours' pass-1 seeds read from LDS; own state first, then the reference's scan order and strict '<' -- pass 1 as the
+//             minimum over (distance, scan index), pass 2 as the scan itself.  The 64 ids go to a patch buffer of kRowsPatchLattices lattices.
+//   output    a thread owns four consecutive residues of a segment: one 16-byte read of latId, stored (nt) to each of its rows, the
+//             contested residues of the quad replaced from the patch buffer: every voxel is written once, in whole contiguous rows.
+// A tile of more contested lattices than the patch buffer holds takes several rounds over windows of the contested list that overlap by
+// three entries, so that the (consecutive) entries of one quad always lie inside one window; a quad is stored in the first round that
+// holds them all.  No grid takes another path.  latId of a contested lattice holds its index in the contested list.
+// Measured against jfa_first_two on the headline mesh, interleaved on one box (profiles/r18/ab_first_rows_*.txt): 0.21 -> 0.125 .. 0.135 ms at
+// n = 512, 1.5 -> 0.83 ms at n = 1024, lower in every pair; vector instructions 90.8 M -> 51.2 M, scalar 83.5 M -> 25.5 M at n = 512
+// (pmc_first_two_*.summary.txt).  Measured and dropped:
+//   - every contested lattice through the neighbour scan below, ~850 instructions each: 0.232 ms at n = 512 (ab_first_rows_scan_only.txt) --
+//     8.9 contested lattices per tile x 850 is more than jfa_first_two issues; hence the loops over seeds;
+//   - every index product as a shift, the border words by two guarded loads, the scan form's lane constants made inside its branch: 48
+//     instead of 74 VGPRs, eight instead of six waves per SIMD, ~200 vector instructions fewer per wave -- and 0.141 against 0.125 ms at
+//     n = 512, 0.836 against 0.827 at n = 1024 (ab_first_rows_variants.txt).
+constexpr int kRowsPatchLattices = 24;                             // (tests/test_first_two_rows_gpu.py mirrors it)
+constexpr int kRowsSeedLoopMax = 8;                                // border voxels of a lattice up to which the passes loop over seeds (~50 instructions each
+                                                                   // against ~850 for the scan over neighbours)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <class ID, int NT>
+__global__ void __launch_bounds__(NT, 6)
+jfa_first_two_rows(Frame f, const uint32_t* __restrict__ border, uint32_t* __restrict__ out, uint32_t kshift)
+{
+    static_assert(std::is_same<typename ID::T, uint32_t>::value, "4-byte ids");
+    constexpr uint32_t NW = NT / 64, CAP = kRowsPatchLattices, STRIDE = CAP - 3, KMAX = 256;     // n <= 1024
+    static_assert(NT >= (int)KMAX, "a row of n / 4 quads per sweep of the workgroup");
+    __shared__ uint32_t bw[16 * (KMAX / 8)];                       // border words [row c b][n / 32]
+    __shared__ __attribute__((aligned(16))) uint32_t latId[KMAX];
+    __shared__ uint32_t clist[KMAX];                               // residues of the contested lattices
+    __shared__ uint32_t twoMask[KMAX / 32];
+    __shared__ uint32_t nCont;
+    __shared__ float posY[4], posZ[4];
+    __shared__ f32x4 cand[NW][64];                                 // per wave: position of the pass-1 seed of each chain position, its id
+    __shared__ uint32_t patch[CAP][64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, N = f.n, k = N >> 2, W = f.w, G = k >> 5;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t ry = blockIdx.x & (k - 1u), rz = blockIdx.x >> kshift;       // ry fastest: consecutive tiles write adjacent rows
+    for (uint32_t i = tid; i < 16u * W; i += NT) {
+        const uint32_t row = i >> (kshift - 3u), wi = i & (W - 1u);            // W = k / 8
+        bw[i] = border[((rz + (row >> 2) * k) * N + ry + (row & 3u) * k) * W + wi];
+    }
+    if (tid == 0) nCont = 0;
+    if (tid < 4) posY[tid] = axis_pos(f.oy, ry + tid * k, f.vs);
+    else if (tid < 8) posZ[tid - 4u] = axis_pos(f.oz, rz + (tid - 4u) * k, f.vs);
+    __syncthreads();
+    const uint32_t ca = lane & 3u, cb = (lane >> 2) & 3u, cc = lane >> 4;       // chain position of a lane
+    unsigned long long nbr;                                        // the lanes within one chain position along every axis, the lane itself included
+    {
+        const uint32_t ma = ((7u << ca) >> 1) & 15u, mb = ((7u << cb) >> 1) & 15u, mc = ((7u << cc) >> 1) & 15u;
+        const uint32_t plane = ma * ((mb & 1u) | ((mb & 2u) << 3) | ((mb & 4u) << 6) | ((mb & 8u) << 9));
+        nbr = (unsigned long long)(((mc & 1u) ? plane : 0u) | ((mc & 2u) ? plane << 16 : 0u))
+            | ((unsigned long long)(((mc & 4u) ? plane : 0u) | ((mc & 8u) ? plane << 16 : 0u)) << 32);
+    }
+    // ---- census
+    for (uint32_t g = wave; g < G; g += NW) {
+        const uint32_t w = bw[(lane >> 2) * W + ca * G + g];
+        uint32_t one = w, two = 0;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const uint32_t o2 = (uint32_t)__shfl_xor((int)one, m), t2 = (uint32_t)__shfl_xor((int)two, m);
+            two |= t2 | (one & o2);
+            one |= o2;
+        }
+        one = (uint32_t)__builtin_amdgcn_readfirstlane((int)one);
+        two = (uint32_t)__builtin_amdgcn_readfirstlane((int)two);
+        if (lane < 32) latId[g * 32u + lane] = ID::none();
+        for (uint32_t mine = w & one & ~two; mine; mine &= mine - 1u) {           // 0.7 % of the voxels on the headline mesh
+            const uint32_t res = g * 32u + (uint32_t)__builtin_ctz(mine);
+            latId[res] = ID::pack(res + ca * k, ry + cb * k, rz + cc * k);
+        }
+        if (two) {                                                 // uniform
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(&nCont, (uint32_t)__popc(two));
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            if (lane < 32 && ((two >> lane) & 1u)) {
+                const uint32_t ci = base + (uint32_t)__popc(two & ((1u << lane) - 1u));
+                clist[ci] = g * 32u + lane;
+                latId[g * 32u + lane] = ci;
+            }
+        }
+        if (lane == 0) twoMask[g] = two;
+    }
+    __syncthreads();
+    // ---- the thread's quad: residues 4 q .. 4 q + 3 of segment qa, in rows row0, row0 + RPI, ..
+    const uint32_t nL = nCont;
+    const uint32_t rounds = nL <= CAP ? 1u : (nL - CAP + STRIDE - 1u) / STRIDE + 1u;
+    const uint32_t qr = tid & (k - 1u), row0 = tid >> kshift, RPI = (uint32_t)NT >> kshift;     // a row has k quads
+    const uint32_t qa = qr >> (kshift - 2u), res0 = (qr & ((k >> 2) - 1u)) * 4u;
+    const uint32_t nib = (twoMask[res0 >> 5] >> (res0 & 31u)) & 15u;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(&latId[res0]);
+    uint32_t myRound = 0;
+    if (nib) {
+        const uint32_t hi = v[31 - __builtin_clz(nib)];            // the contested entries of a quad are consecutive and ascending
+        if (hi >= CAP) myRound = (hi - CAP) / STRIDE + 1u;
+    }
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint32_t base = r * STRIDE, end = min(base + CAP, nL);
+        if (r) __syncthreads();                                    // the patch buffer has been read
+        // ---- contested lattices: one wave each
+        for (uint32_t e = base + wave; e < end; e += NW) {
+            const uint32_t res = clist[e];
+            const bool mine = (bw[(lane >> 2) * W + ca * G + (res >> 5)] >> (res & 31u)) & 1u;
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(mine);
+            const float px = axis_pos(f.ox, res + ca * k, f.vs), py = posY[cb], pz = posZ[cc];
+            auto seed_id = [&](uint32_t s) { return ID::pack(res + (s & 3u) * k, ry + ((s >> 2) & 3u) * k, rz + (s >> 4) * k); };
+            auto lane_of = [](float v, int s) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), s)); };      // s uniform
+            uint32_t id;
+            if (__popcll(bal) <= kRowsSeedLoopMax) {               // uniform
+                // FEW border voxels (2.2 per contested lattice on the headline mesh): both passes as loops over the SEEDS, whose position is
+                // then uniform.  Lane order IS the scan order (c b a = z y x, outer to inner), so the seeds come in the reference's order.
+                // pass n/2: seed s reaches the lanes that differ from it by two chain positions along any axes (lane ^ s within 2 | 8 | 32;
+                // the difference along an axis they share is exactly 0, and x + 0 = x); the own state (distance 0) is never beaten
+                float best = mine ? 0.0f : __builtin_inff();
+                uint32_t s1 = mine ? lane : 64u;
+                for (unsigned long long rem = bal; rem; rem &= rem - 1ull) {
+                    const int s = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rem));
+                    const float ex = lane_of(px, s) - px, ey = lane_of(py, s) - py, ez = lane_of(pz, s) - pz;
+                    const float d = ((ex * ex) + (ey * ey)) + (ez * ez);
+                    if (((lane ^ (uint32_t)s) & ~42u) == 0u && d < best) { best = d; s1 = (uint32_t)s; }
+                }
+                // pass n/4: seed s is offered by the neighbours that hold it after pass n/2 (a ballot against the lane's neighbourhood mask).
+                // Between two seeds of equal distance the one whose first holder comes first in the scan wins, the voxel's own state before all.
+                best = __builtin_inff();
+                uint32_t bestFirst = 64u;
+                id = ID::none();
+                for (unsigned long long rem = bal; rem; rem &= rem - 1ull) {
+                    const int s = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rem));
+                    const bool own = s1 == (uint32_t)s;
+                    const unsigned long long reach = __builtin_amdgcn_ballot_w64(own) & nbr;
+                    const uint32_t first = own ? 0u : 1u + (uint32_t)__builtin_ctzll(reach | (1ull << 63));
+                    const float ex = lane_of(px, s) - px, ey = lane_of(py, s) - py, ez = lane_of(pz, s) - pz;
+                    const float d = ((ex * ex) + (ey * ey)) + (ez * ez);
+                    if (reach != 0ull && (d < best || (d == best && first < bestFirst))) { best = d; bestFirst = first; id = seed_id((uint32_t)s); }
+                }
+            } else {
+                // MANY: pass n/2 over the voxel's own state and the <= 7 partners two chain positions away (position ^ 2: the only one in the
+                // grid along an axis) as the minimum over (distance, scan index), pass n/4 as the reference's scan over the 27 neighbours
+                const float ex = __shfl_xor(px, 2) - px, ey = __shfl_xor(py, 8) - py, ez = __shfl_xor(pz, 32) - pz;
+                const float d2[3] = {ex * ex, ey * ey, ez * ez};
+                const int sg[3] = {ca < 2u ? 1 : -1, cb < 2u ? 3 : -3, cc < 2u ? 9 : -9};       // the partner's place in the scan
+                float bestD = mine ? 0.0f : __builtin_inff();
+                int bestRank = -100;                                   // the own state wins every tie
+                uint32_t s1 = mine ? lane : 64u;
+#pragma unroll
+                for (int m = 1; m < 8; ++m) {
+                    const uint32_t nb = lane ^ ((m & 1) ? 2u : 0u) ^ ((m & 2) ? 8u : 0u) ^ ((m & 4) ? 32u : 0u);
+                    float d = 0.0f;                                    // (dx2 + dy2) + dz2 with the zero terms left out: x + 0 = x
+                    bool first = true;
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax)
+                        if ((m >> ax) & 1) { d = first ? d2[ax] : d + d2[ax]; first = false; }
+                    const int rank = ((m & 1) ? sg[0] : 0) + ((m & 2) ? sg[1] : 0) + ((m & 4) ? sg[2] : 0);
+                    const bool has = (bal >> nb) & 1ull;
+                    if (has && (d < bestD || (d == bestD && rank < bestRank))) { bestD = d; bestRank = rank; s1 = nb; }
+                }
+                const bool none1 = s1 == 64u;
+                const float sx = none1 ? __builtin_inff() : __shfl(px, (int)(s1 & 63u));
+                const float sy = __shfl(py, (int)(s1 & 63u)), sz = __shfl(pz, (int)(s1 & 63u));
+                const uint32_t id1 = none1 ? ID::none() : seed_id(s1);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // cand of the lattice before has been read
+                cand[wave][lane] = f32x4{sx, sy, sz, __uint_as_float(id1)};
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                float best = ((sx - px) * (sx - px)) + ((sy - py) * (sy - py)) + ((sz - pz) * (sz - pz));
+                id = id1;
+                // (plane by plane: unrolled over all 27 the reads are hoisted and do not fit the registers of six waves per SIMD.  The voxel
+                // itself is scanned too: its distance is never '<' the best)
+#pragma unroll 1
+                for (int tz = -1; tz <= 1; ++tz)
+#pragma unroll
+                    for (int ty = -1; ty <= 1; ++ty)
+#pragma unroll
+                        for (int tx = -1; tx <= 1; ++tx) {
+                            const bool valid = ca + (uint32_t)tx <= 3u && cb + (uint32_t)ty <= 3u && cc + (uint32_t)tz <= 3u;
+                            const f32x4 c4 = cand[wave][valid ? lane + (uint32_t)(tx + 4 * ty + 16 * tz) : lane];
+                            const float d = ((c4[0] - px) * (c4[0] - px)) + ((c4[1] - py) * (c4[1] - py)) + ((c4[2] - pz) * (c4[2] - pz));
+                            if (d < best) { best = d; id = __float_as_uint(c4[3]); }
+                        }
+            }
+            patch[e - base][lane] = id;
+        }
+        __syncthreads();
+        // ---- output
+        if (myRound == r) {
+            for (uint32_t row = row0; row < 16u; row += RPI) {
+                u32x4 val = v;
+                if (nib) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if ((nib >> j) & 1u) val[j] = patch[v[j] - base][row * 4u + qa];
+                }
+                uint32_t* p = out + (size_t)((rz + (row >> 2) * k) * N + ry + (row & 3u) * k) * N + 4u * qr;
+                __builtin_nontemporal_store(val, reinterpret_cast<u32x4*>(p));
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // Passes k = n/2 and k = n/4 of a whole grid from its border mask in one launch; timed as the first pass.
@@ -359,6 +573,15 @@ int launch_win_first_two(vp_ctx* ctx, const Frame& f, const uint32_t* d_border, 
         VP_HIP(hipGetLastError());
         return 0;
     }
+    char* w = win_words(out, f.n, 0);
+    // Powers of two from 128 to 1024 (n/4 a multiple of 32, 4-byte ids): whole-row tiles, one workgroup each (see jfa_first_two_rows).
+    if ((f.n & (f.n - 1)) == 0 && k % 32 == 0 && !win_compact(f.n) && (reinterpret_cast<uintptr_t>(w) & 15u) == 0) {
+        const uint32_t kshift = (uint32_t)__builtin_ctz(k);
+        if (f.n <= 512) hipLaunchKernelGGL((jfa_first_two_rows<Id9, 256>), dim3(k * k), dim3(256), 0, ctx->stream, f, d_border, (uint32_t*)w, kshift);
+        else            hipLaunchKernelGGL((jfa_first_two_rows<Id10, 256>), dim3(k * k), dim3(256), 0, ctx->stream, f, d_border, (uint32_t*)w, kshift);
+        VP_HIP(hipGetLastError());
+        return 0;
+    }
     // tile = 4 x 4 x 4 chain positions x XR residues.  Measured (profiles/r02/ab33.txt, r04/ab_ftxr_*.txt): 16 residues x 256 threads is the
     // best shape at n <= 512, 32 x 512 above.  A workgroup takes kTilesPerWg consecutive tiles.
     const bool small = f.n <= 512;
@@ -367,7 +590,6 @@ int launch_win_first_two(vp_ctx* ctx, const Frame& f, const uint32_t* d_border, 
     const dim3 grid((tiles + kTilesPerWg - 1) / kTilesPerWg);
     auto pow2 = [](uint32_t v) { return v != 0 && (v & (v - 1)) == 0; };
     const uint32_t shifts = (pow2(tilesX) && pow2(k)) ? ((uint32_t)__builtin_ctz(tilesX) | ((uint32_t)__builtin_ctz(k) << 8) | (1u << 16)) : 0u;
-    char* w = win_words(out, f.n, 0);
     unsigned char* b = (unsigned char*)win_bytes_plane(out, f.n, 0);
     if (win_compact(f.n)) hipLaunchKernelGGL((jfa_first_two<Id64, 32, 512, kTilesPerWg, true>), grid, dim3(512), 0, ctx->stream, f, d_border, (uint2*)w, b, tilesX, tiles, shifts, make_fastdiv(tilesX), make_fastdiv(k), 0u);
     else if (small) hipLaunchKernelGGL((jfa_first_two<Id9, 16, 256, kTilesPerWg>), grid, dim3(256), 0, ctx->stream, f, d_border, (uint32_t*)w, nullptr, tilesX, tiles, shifts, make_fastdiv(tilesX), make_fastdiv(k), 0u);

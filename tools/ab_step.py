@@ -1,5 +1,7 @@
 """Dev tool: A/B of the whole JFA (vp_jfa) per kernel between builds of libvphip.so, interleaved; prints per-kernel mean ms.
-  python tools/ab_step.py --n 512 --libs a.so,b.so"""
+  python tools/ab_step.py --n 512 --libs a.so,b.so [--pairs KERNEL]
+--pairs KERNEL: also print KERNEL and the sum of all kernels round by round (every round runs each build once: a pair), and whether the
+last build is below the first in every round."""
 import sys, os, math, argparse, ctypes, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -8,6 +10,7 @@ from cuda_mesh_voxelization_amd.capi import Frame
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=512); ap.add_argument("--refine", type=int, default=24)
 ap.add_argument("--libs", required=True); ap.add_argument("--rounds", type=int, default=7)
+ap.add_argument("--pairs", default="")
 a = ap.parse_args()
 _vp, _sz, fp = ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Frame)
 n = a.n
@@ -51,3 +54,11 @@ print("%-12s" % "kernel" + "".join("%12s" % nm for nm, _, _ in libs) + "   (medi
 for k in keys:
     print("%-12s" % k + "".join("%12.4f" % statistics.median(res[nm].get(k, [0])) for nm, _, _ in libs))
 print("%-12s" % "sum" + "".join("%12.4f" % sum(statistics.median(v) for v in res[nm].values()) for nm, _, _ in libs))
+if a.pairs:
+    names = [nm for nm, _, _ in libs]
+    rows = {nm: list(zip(res[nm][a.pairs], [sum(v[r] for v in res[nm].values()) for r in range(a.rounds)])) for nm in names}
+    print("round   " + "".join("%24s" % (nm + ": " + a.pairs + " / sum") for nm in names))
+    for r in range(a.rounds):
+        print("%-8d" % (r + 1) + "".join("%14.4f /%8.4f" % rows[nm][r] for nm in names))
+    first, last = rows[names[0]], rows[names[-1]]
+    print("%s below %s in every round: %s %s, sum %s" % (names[-1], names[0], a.pairs, all(l[0] < f[0] for f, l in zip(first, last)), all(l[1] < f[1] for f, l in zip(first, last))))
