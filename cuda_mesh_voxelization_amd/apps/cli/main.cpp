@@ -35,8 +35,16 @@
 //                            writes PREFIX.thick.u32 (n^3 values) and, with W, PREFIX.thin.u32 (a grid).  One device only (-g > 1 is refused)
 //         --thin-only        (extension, with --thickness R:W) the grid is replaced by the thin grid before the exports that follow and -s:
 //                            -e writes out/thin_<type>_<output>, cubes or --surface-nets, and -d PREFIX.grid.u32 holds it
+//         --skeleton M[:I]   (extension) topological thinning of the FINAL grid -- where --thickness sits, after it and --thin-only: M = curve (the
+//                            one-voxel-wide centre line; line ends stay) or kernel (the homotopy kernel: a ball shrinks to one voxel, a torus
+//                            to a loop), I = at most that many iterations (0 or absent: until nothing is deleted; include/vphip.h, vp_skeleton;
+//                            vox/skeleton.h).  Prints "skeleton: V voxels, I iterations, D deleted"; with --thickness R, measured on the solid
+//                            first, also the min / mean / max of the thickness 2 sqrt(T2) over the skeleton voxels.  -d PREFIX additionally
+//                            writes PREFIX.skel.u32 (a grid).  One device only (-g > 1 is refused)
+//         --skeleton-only    (extension, with --skeleton) the grid is replaced by the skeleton before the exports that follow, --octree and
+//                            -s: -e writes out/skel_<type>_<output>, and -d PREFIX.grid.u32 holds it
 //         --octree           (extension) sparse voxel octree of the FINAL grid -- where --thickness sits: after the voxelization, --morph, --fill,
-//                            CSG and --thin-only (include/vphip.h, vp_octree; vox/octree.h): writes out/<output stem>_<type>_out.svo, the
+//                            CSG, --thin-only and --skeleton-only (include/vphip.h, vp_octree; vox/octree.h): writes out/<output stem>_<type>_out.svo, the
 //                            same bytes for every -t, and prints the nodes per level, the bytes and the ratio to the n^3 / 8 bytes of the
 //                            grid.  n % 32 == 0, n <= 1024.  One device only (-g > 1 is refused)
 //         --fill             (extension) after each mesh's voxelization (solid or --conservative), fill its interior: every empty voxel
@@ -96,6 +104,7 @@
 #include "mesh/mesh_io.h"
 #include "proc_utils.h"
 #include "vox/octree.h"
+#include "vox/skeleton.h"
 #include "vox/vox.h"
 #include "vp_runtime.h"
 
@@ -126,6 +135,9 @@ struct Options {
     bool fill = false;
     unsigned thickness = 0, thinWidth = 0;                  // --thickness RMAX[:W]: band in voxels, 0 = not asked for; W = 0: no thin grid
     bool thinOnly = false;
+    int skeleton = -1;                                      // --skeleton curve|kernel[:ITERS]: VOX::SkeletonMode, -1 = not asked for
+    unsigned skeletonIters = 0;
+    bool skeletonOnly = false;
     bool octree = false;                                    // --octree: out/<output stem>_<type>_out.svo of the final grid
     bool exactSdf = false;
     int meshSdf = 0;                                        // --mesh-sdf BAND: band in voxels, 0 = not asked for
@@ -225,7 +237,13 @@ const char* kUsage =
     "                        -d PREFIX adds PREFIX.thick.u32 and PREFIX.thin.u32.  One device only: not with -g > 1 (extension)\n"
     "      --thin-only       With --thickness RMAX:W: replace the grid by the thin grid, so that -e (out/thin_<type>_<output>), -s and\n"
     "                        -d see the thin regions (extension)\n"
-    "      --octree          Sparse voxel octree of the final grid (after --morph, --fill, CSG and --thin-only): writes\n"
+    "      --skeleton arg    Topological thinning of the final grid (after --morph, --fill, CSG, --thickness): arg = curve[:ITERS] (the\n"
+    "                        centre line) or kernel[:ITERS] (the homotopy kernel); ITERS = at most that many iterations, 0 = to the end.\n"
+    "                        Prints the voxels left, the iterations and the voxels deleted; with --thickness also the thickness along\n"
+    "                        the skeleton.  -d PREFIX adds PREFIX.skel.u32.  One device only: not with -g > 1 (extension)\n"
+    "      --skeleton-only   With --skeleton: replace the grid by the skeleton, so that -e (out/skel_<type>_<output>), --octree, -s\n"
+    "                        and -d see it (extension)\n"
+    "      --octree          Sparse voxel octree of the final grid (after --morph, --fill, CSG, --thin-only and --skeleton-only): writes\n"
     "                        out/<output stem>_<type>_out.svo, the same bytes for every -t, and prints its size against the grid's.\n"
     "                        n a multiple of 32 up to 1024.  One device only: not with -g > 1 (extension)\n"
     "      --conservative    Surface voxelization: a voxel is set iff its closed box overlaps a triangle (any mesh, open or\n"
@@ -266,7 +284,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"skeleton", 'K'}, {"skeleton-only", 'Q'},{"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -307,10 +325,10 @@ Options Parse(int argc, char** argv)
             o.windingLevel = static_cast<float>(lv); o.windingBeta = static_cast<float>(bt);
             continue;
         }
-        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X' || key == 'O' || key == 'Y';
+        const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X' || key == 'O' || key == 'Y' || key == 'Q';
         if (isSwitch) {
             const bool v = !hasValue || value == "true" || value == "1";
-            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else if (key == 'X') o.exactSdf = v; else if (key == 'O') o.thinOnly = v; else if (key == 'Y') o.octree = v; else o.help = v;
+            if (key == 'e') o.doExport = v; else if (key == 's') o.sdf = v; else if (key == 'V') o.verify = v; else if (key == 'S') o.surfaceOnly = v; else if (key == 'C') o.conservative = v; else if (key == 'F') o.fill = v; else if (key == 'X') o.exactSdf = v; else if (key == 'O') o.thinOnly = v; else if (key == 'Y') o.octree = v; else if (key == 'Q') o.skeletonOnly = v; else o.help = v;
             continue;
         }
         if (!hasValue) {
@@ -332,6 +350,16 @@ Options Parse(int argc, char** argv)
                 const bool digits = !value.empty() && value.size() <= 2 && value.find_first_not_of("0123456789") == std::string::npos;
                 cpuAssert(digits && std::stoi(value) >= 1 && std::stoi(value) <= 32, "--mesh-sdf: '" + value + "' is not a band of 1..32 voxels\n");
                 o.meshSdf = std::stoi(value);
+                break;
+            }
+            case 'K': {
+                // curve|kernel[:ITERS]
+                const size_t colon = value.find(':');
+                const std::string mode = value.substr(0, colon), iters = colon == std::string::npos ? "0" : value.substr(colon + 1);
+                const bool itersOk = !iters.empty() && iters.size() <= 6 && iters.find_first_not_of("0123456789") == std::string::npos;
+                cpuAssert((mode == "curve" || mode == "kernel") && itersOk, "--skeleton: '" + value + "' is not curve[:ITERS] or kernel[:ITERS]\n");
+                o.skeleton = mode == "curve" ? VOX::SKELETON_CURVE : VOX::SKELETON_KERNEL;
+                o.skeletonIters = static_cast<unsigned>(std::stoi(iters));
                 break;
             }
             case 'T': {
@@ -430,6 +458,25 @@ void Thickness(unsigned rmax, unsigned width, const HostVoxelsGrid<gridType>& gr
     if (width) std::printf("thin voxels (thinner than %u voxels, T2 < %u): %llu\n", width, thin2, static_cast<unsigned long long>(count));
 }
 
+// --skeleton: the thinned `grid` into `skel`; prints what the flag promises, and the thickness along the skeleton when `t2` holds one
+template <Types T>
+void Skeleton(int mode, unsigned iters, const HostVoxelsGrid<gridType>& grid, HostVoxelsGrid<gridType>& skel, const HostGrid<uint32_t>* t2)
+{
+    const VOX::SkeletonStats st = VOX::Skeletonize<T>(grid, skel, static_cast<VOX::SkeletonMode>(mode), iters);
+    std::printf("skeleton: %llu voxels, %llu iterations, %llu deleted\n", static_cast<unsigned long long>(st.voxels),
+                static_cast<unsigned long long>(st.iterations), static_cast<unsigned long long>(st.deleted));
+    if (!t2 || st.voxels == 0) return;
+    const uint32_t* bits = reinterpret_cast<const uint32_t*>(skel.View().Data());
+    const uint32_t* v = t2->View().Data();
+    double lo = INFINITY, hi = 0.0, sum = 0.0;
+    for (size_t i = 0; i < t2->View().Size(); ++i)
+        if ((bits[i >> 5] >> (i & 31)) & 1u) {
+            const double t = 2.0 * std::sqrt(static_cast<double>(v[i]));
+            lo = std::min(lo, t); hi = std::max(hi, t); sum += t;
+        }
+    std::printf("skeleton thickness (voxels): min %.3f, mean %.3f, max %.3f\n", lo, sum / static_cast<double>(st.voxels), hi);
+}
+
 // --octree: the tree of `grid` to `path`; prints what the flag promises
 template <Types T>
 void OctreeOut(const HostVoxelsGrid<gridType>& grid, const std::string& path)
@@ -499,6 +546,8 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.fill && opt.gpus > 1), "--fill runs on one device: -g must be 1\n");
     cpuAssert(!(opt.thickness && opt.gpus > 1), "--thickness runs on one device: -g must be 1\n");
     cpuAssert(!(opt.octree && opt.gpus > 1), "--octree runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.skeleton >= 0 && opt.gpus > 1), "--skeleton runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.skeletonOnly && opt.skeleton < 0), "--skeleton-only needs --skeleton curve|kernel\n");
     cpuAssert(!(opt.octree && (opt.numVoxels % 32 != 0 || opt.numVoxels > 1024)), "--octree needs -n to be a multiple of 32 up to 1024\n");
     cpuAssert(!(opt.thinOnly && !(opt.thickness && opt.thinWidth)), "--thin-only needs --thickness RMAX:W: the thin grid is that of a width\n");
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
@@ -549,7 +598,7 @@ int main(int argc, char** argv)
     HostVoxelsGrid<gridType> emptyGrid(N, voxelSize);       // benchmark-mode CSG operand (main.cpp:89,127)
     HostGrid<float> sdf;
     HostGrid<uint32_t> thick;
-    HostVoxelsGrid<gridType> thinGrid;
+    HostVoxelsGrid<gridType> thinGrid, skelGrid;
     const std::string typeName = GetTypesString(TYPE);
     if (EXPORT || opt.octree) std::filesystem::create_directories("out");
 
@@ -627,6 +676,24 @@ int main(int argc, char** argv)
                     Mesh outMesh;
                     GridMesh(GPU, opt.surfaceOnly, opt.surfaceNets, grids[0].View(), outMesh);
                     cpuAssert(ExportMesh("out/thin_" + typeName + "_" + opt.output, outMesh), "Error in " + opt.output + " export (thin)");
+                }
+            }
+        }
+
+        if (opt.skeleton >= 0) {
+            const HostGrid<uint32_t>* t2 = opt.thickness ? &thick : nullptr;
+            switch (TYPE) {
+                case Types::SEQUENTIAL: Skeleton<Types::SEQUENTIAL>(opt.skeleton, opt.skeletonIters, grids[0], skelGrid, t2); break;
+                case Types::OPENMP:     Skeleton<Types::OPENMP>(opt.skeleton, opt.skeletonIters, grids[0], skelGrid, t2); break;
+                case Types::NAIVE:      Skeleton<Types::NAIVE>(opt.skeleton, opt.skeletonIters, grids[0], skelGrid, t2); break;
+                case Types::TILED:      Skeleton<Types::TILED>(opt.skeleton, opt.skeletonIters, grids[0], skelGrid, t2); break;
+            }
+            if (opt.skeletonOnly) {
+                std::memcpy(grids[0].View().Data(), skelGrid.View().Data(), grids[0].View().StorageSize() * sizeof(gridType));
+                if (EXPORT) {
+                    Mesh outMesh;
+                    GridMesh(GPU, opt.surfaceOnly, opt.surfaceNets, grids[0].View(), outMesh);
+                    cpuAssert(ExportMesh("out/skel_" + typeName + "_" + opt.output, outMesh), "Error in " + opt.output + " export (skeleton)");
                 }
             }
         }
@@ -723,6 +790,7 @@ int main(int argc, char** argv)
         WriteRaw(opt.dump + ".grid.u32", grids[0].View().Data(), grids[0].View().StorageSize() * sizeof(gridType));
         if (opt.sdf) WriteRaw(opt.dump + ".sdf.f32", sdf.View().Data(), sdf.View().Size() * sizeof(float));
         if (opt.thickness) WriteRaw(opt.dump + ".thick.u32", thick.View().Data(), thick.View().Size() * sizeof(uint32_t));
+        if (opt.skeleton >= 0) WriteRaw(opt.dump + ".skel.u32", skelGrid.View().Data(), skelGrid.View().StorageSize() * sizeof(gridType));
         if (opt.thickness && opt.thinWidth) WriteRaw(opt.dump + ".thin.u32", thinGrid.View().Data(), thinGrid.View().StorageSize() * sizeof(gridType));
     }
     return 0;

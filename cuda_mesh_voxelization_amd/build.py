@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvphip.so")
 CLI = os.path.join(PKG, "vpcli")
 
-HIP_SOURCES = ["capi.hip", "vox.hip", "csg.hip", "jfa_seed.hip", "jfa_first_two.hip", "jfa_dense.hip", "extract.hip", "multi.hip", "cvox.hip", "fill.hip", "morph.hip", "components.hip", "surfnets.hip", "edt.hip", "meshdist.hip", "isonets.hip", "winding.hip", "thickness.hip", "octree.hip"]
+HIP_SOURCES = ["capi.hip", "vox.hip", "csg.hip", "jfa_seed.hip", "jfa_first_two.hip", "jfa_dense.hip", "extract.hip", "multi.hip", "cvox.hip", "fill.hip", "morph.hip", "components.hip", "surfnets.hip", "edt.hip", "meshdist.hip", "isonets.hip", "winding.hip", "thickness.hip", "octree.hip", "skeleton.hip"]
 DENSE_PARTS = 10                 # jfa_dense.hip is compiled once per id format and pass kind, side by side (-DVP_DENSE_PART=1..10, see the end of the file)
 HOOK_SOURCES = ["vox.hip", "multi.hip", "cvox.hip", "meshdist.hip"]     # the sources that read test hooks from the environment under -DVP_TEST_HOOKS (libvphip_hooks.so)
 HOOKS_LIB = os.path.join(PKG, "libvphip_hooks.so")
@@ -54,7 +54,7 @@ def build_lib(force: bool = False, verbose: bool = False, hooks: bool = False) -
     """libvphip.so; hooks=True: also libvphip_hooks.so -- the same objects except vox.hip / multi.hip / cvox.hip / meshdist.hip compiled with -DVP_TEST_HOOKS, the
     build the tests that force rare paths load (the default library reads no environment variable on any call path)."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "vp_internal.h"), os.path.join(CSRC, "jfa_common.h"), os.path.join(CSRC, "wg_scan.h"), os.path.join(ROOT, "include", "vphip.h")]
+    deps = srcs + [os.path.join(CSRC, "vp_internal.h"), os.path.join(CSRC, "jfa_common.h"), os.path.join(CSRC, "wg_scan.h"), os.path.join(CSRC, "skeleton_simple.h"), os.path.join(ROOT, "include", "vphip.h")]
     objdir = os.path.join(PKG, "build")
     flags = [f for f in HIP_FLAGS if f != "-shared"]
 

@@ -19,6 +19,7 @@ EDT_NONE = 0xFFFFFFFF                                               # vp_edt: "t
 MESH_NONE = 0xFFFFFFFF                                              # vp_mesh_distance: "no triangle within the band"
 ISO_LINEAR, ISO_SIGNED_SQUARE = 0, 1                                # vp_isonets: the field as it is / sign(v) sqrt|v| (every sdf of the library)
 CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
+SKEL_KERNEL, SKEL_CURVE = 0, 1                                      # vp_skeleton: the homotopy kernel / the centre line (line ends stay)
 COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
 MULTI_HALO, MULTI_GHOST, MULTI_HYBRID, MULTI_TRANSPOSE = 0, 1, 2, 3
@@ -70,6 +71,7 @@ SYMBOLS = [
     "vp_winding", "vp_winding_result", "vp_winding_host",
     "vp_thickness", "vp_thickness_result", "vp_thickness_host",
     "vp_octree", "vp_octree_result", "vp_octree_expand", "vp_octree_expand_result", "vp_octree_host", "vp_octree_expand_host", "vp_octree_validate_host",
+    "vp_skeleton", "vp_skeleton_result", "vp_skeleton_host", "vp_skeleton_table_host",
 ]
 
 
@@ -212,6 +214,10 @@ def lib():
         "vp_octree_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_int, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _vp, _vp]),
         "vp_octree_expand_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint64, ctypes.c_int, _vp]),
         "vp_octree_validate_host": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint32]),
+        "vp_skeleton": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, _vp]),
+        "vp_skeleton_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_skeleton_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, _vp, _vp]),
+        "vp_skeleton_table_host": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -274,6 +280,15 @@ def lib():
 def check(rc: int):
     if rc != 0:
         raise VPError(rc, (lib().vp_last_error() or b"").decode("utf-8", "replace"))
+
+
+def skeleton_table(algo: int = ALGO_TILED, _ctx=None):
+    """uint32[2^21]: bit c = simple(m) for the neighbourhood m = (c & 0x1FFF) | (c >> 13) << 14 (include/vphip.h, vp_skeleton), computed on the
+    CPU -- ALGO_NAIVE by the plain form of the test, ALGO_TILED by the shift form.  No GPU needed."""
+    np = __import__("numpy")
+    t = np.empty(1 << 21, np.uint32)
+    check(lib().vp_skeleton_table_host(_ctx, algo, t.ctypes.data_as(_vp)))
+    return t
 
 
 class Context:
@@ -598,7 +613,34 @@ class Context:
         check(lib().vp_octree_expand_result(self._h, ctypes.byref(d), ctypes.byref(n)))
         return d.value or 0, int(n.value)
 
+    def skeleton(self, frame: Frame, d_words: int, mode: int = SKEL_CURVE, max_iters: int = 0, d_anchor: int = 0, algo: int = ALGO_TILED):
+        """Topological thinning of a whole grid (n <= 1024) into a grid the context owns; skeleton_result() hands it out.  Blocks (the
+        deleted count of every iteration is read back) and returns (voxels left, iterations, voxels deleted)."""
+        s = (ctypes.c_uint64 * 3)()
+        check(lib().vp_skeleton(self._h, ctypes.byref(frame), _vp(d_words or None), _vp(d_anchor or None), mode, max_iters, algo, s))
+        return tuple(int(v) for v in s)
+
+    def skeleton_result(self):
+        """(d_skel, stats, n) of the last skeleton(): the device pointer as an int (0 where there is none), (voxels left, iterations, voxels
+        deleted) and the side they are for.  Valid until the next skeleton(), release() or close()."""
+        d, s, n = _vp(), (ctypes.c_uint64 * 3)(), ctypes.c_uint32()
+        check(lib().vp_skeleton_result(self._h, ctypes.byref(d), s, ctypes.byref(n)))
+        return d.value or 0, tuple(int(v) for v in s), int(n.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
+    def skeleton_host(self, frame: Frame, h_words, mode: int = SKEL_CURVE, max_iters: int = 0, h_anchor=None, algo: int = ALGO_TILED):
+        """numpy in, numpy out: (skeleton words uint32[n^3 / 32], (voxels left, iterations, voxels deleted))."""
+        np = __import__("numpy")
+        g, s = np.empty(frame.voxels // 32, np.uint32), (ctypes.c_uint64 * 3)()
+        check(lib().vp_skeleton_host(self._h, ctypes.byref(frame), h_words.ctypes.data_as(_vp), None if h_anchor is None else h_anchor.ctypes.data_as(_vp),
+                                     mode, max_iters, algo, g.ctypes.data_as(_vp), s))
+        return g, tuple(int(v) for v in s)
+
+    def skeleton_table_host(self, algo: int = ALGO_TILED):
+        """The table of the simple neighbourhoods computed on the device: uint32[2^21], bit c = simple(c) (skeleton_table() without a
+        context computes it on the CPU)."""
+        return skeleton_table(algo, self._h)
+
     def octree_host(self, frame: Frame, h_words, algo: int = ALGO_TILED, capacity=None):
         """numpy in, numpy out: (nodes uint32[M, 2], level_offset uint32[11], full_leaves uint32[11]).  The first call asks for the count
         (capacity 0 is refused with the count stored); `capacity` overrides the second call's room."""

@@ -215,7 +215,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
                        &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads,
                        &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree,
                        &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum,
-                       &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt, &ctx->oc_grid };
+                       &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt, &ctx->oc_grid,
+                       &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -230,6 +231,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->wn_host) (void)hipHostFree(ctx->wn_host);
     if (ctx->th_host) (void)hipHostFree(ctx->th_host);
     if (ctx->oc_host) (void)hipHostFree(ctx->oc_host);
+    if (ctx->sk_host) (void)hipHostFree(ctx->sk_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -318,6 +320,8 @@ int vp_ctx_release(vp_ctx* ctx)
     release(ctx->oc_grid);                                         // vp_octree_expand: result
     ctx->oc_n = ctx->oc_grid_n = 0;
     ctx->oc_count = 0;
+    for (Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) release(*b);                                  // vp_skeleton: scratch and result
+    ctx->sk_n = 0;
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -1303,6 +1307,50 @@ int vp_octree_expand_result(vp_ctx* ctx, uint32_t** d_words, uint32_t* h_n)
 
 int vp_octree_validate_host(const uint32_t* h_nodes, uint64_t nodes, uint32_t n) { return octree_validate(h_nodes, nodes, n); }
 
+// ---- topological thinning --------------------------------------------------------------------------
+// what vp_skeleton and its host form share: whole grids up to n = 1024, the mode and the algo
+static int check_skeleton(const vp_frame* f, const char* who, int mode, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_whole(f, who));
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
+    VP_TRY(check_algo(who, algo));
+    if (mode != VP_SKEL_KERNEL && mode != VP_SKEL_CURVE) return set_error(VP_ERR_INVALID, "%s: unknown mode %d", who, mode);
+    return 0;
+}
+
+int vp_skeleton(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, const uint32_t* d_anchor, int mode, uint32_t max_iters, int algo,
+                uint64_t* h_stats)
+{
+    const char* who = "vp_skeleton";
+    if (!ctx || !f || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_skeleton(f, who, mode, algo));
+    VP_TRY(check_aligned(who, {d_words, d_anchor}));
+    // the grid and the anchor are read while every buffer of the call is written: they may lie in none of them (the last skeleton has to
+    // be copied before it is thinned further or used as an anchor)
+    for (const Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) {
+        VP_TRY(check_disjoint(who, "a buffer of the context", d_words, vp_grid_words(f) * 4, b->ptr, b->bytes));
+        if (d_anchor) VP_TRY(check_disjoint(who, "a buffer of the context", d_anchor, vp_grid_words(f) * 4, b->ptr, b->bytes));
+    }
+    // the context's own buffers are outputs like any other: what was recorded about their bytes is gone, before and after they grow
+    for (Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) grid_written(ctx, b->ptr, b->bytes);
+    const int rc = launch_skeleton(ctx, make_frame(f), d_words, d_anchor, mode, max_iters, algo, h_stats);
+    for (Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) grid_written(ctx, b->ptr, b->bytes);
+    return rc;
+}
+
+int vp_skeleton_result(vp_ctx* ctx, uint32_t** d_skel, uint64_t* h_stats, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_skeleton_result: null ctx");
+    const bool any = ctx->sk_n != 0;
+    if (d_skel) *d_skel = any ? (uint32_t*)ctx->sk_grid.ptr : nullptr;
+    if (h_stats)
+        for (int i = 0; i < 3; ++i) h_stats[i] = any ? ctx->sk_stats[i] : 0;
+    if (h_n) *h_n = ctx->sk_n;
+    return 0;
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1465,6 +1513,40 @@ int vp_octree_expand_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_node
     VP_TRY(vp_upload(ctx, dn, h_nodes, nodes * 8));
     VP_TRY(vp_octree_expand(ctx, f, (const uint32_t*)dn, nodes, algo));
     return vp_download(ctx, h_words, ctx->oc_grid.ptr, vp_grid_words(f) * 4);
+}
+
+int vp_skeleton_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, const uint32_t* h_anchor, int mode, uint32_t max_iters, int algo,
+                     uint32_t* h_skel, uint64_t* h_stats)
+{
+    const char* who = "vp_skeleton_host";
+    if (!ctx || !f || !h_words || (!h_skel && !h_stats)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_skeleton(f, who, mode, algo));
+    void *dw = nullptr, *da = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
+    VP_TRY(vp_upload(ctx, dw, h_words, wb));
+    if (h_anchor) {
+        VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &da));
+        VP_TRY(vp_upload(ctx, da, h_anchor, wb));
+    }
+    VP_TRY(vp_skeleton(ctx, f, (const uint32_t*)dw, (const uint32_t*)da, mode, max_iters, algo, h_stats));
+    return h_skel ? vp_download(ctx, h_skel, ctx->sk_grid.ptr, wb) : 0;
+}
+
+int vp_skeleton_table_host(vp_ctx* ctx, int algo, uint32_t* h_table)
+{
+    const char* who = "vp_skeleton_table_host";
+    if (!h_table) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_algo(who, algo));
+    if (!ctx) {
+        skeleton_table_cpu(algo, h_table);
+        return 0;
+    }
+    VP_TRY(bind_device(ctx));
+    void* dt = nullptr;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, (size_t)1 << 23, &dt));
+    VP_TRY(launch_skeleton_table(ctx, algo, (uint32_t*)dt));
+    return vp_download(ctx, h_table, dt, (size_t)1 << 23);
 }
 
 int vp_components_label_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t* h_labels, int connectivity, int algo,

@@ -152,6 +152,14 @@ struct vp_ctx {
     uint32_t oc_n = 0;
     uint64_t oc_count = 0;
     uint32_t oc_level_offset[11] = {}, oc_full_leaves[11] = {};
+    // topological thinning (skeleton.hip): the grid of the last vp_skeleton (n^3 / 8 bytes), which the context owns and vp_skeleton_result
+    // hands out, and its three statistics; NAIVE's second grid, the border words of the current iteration (n^3 / 8 bytes each) and the
+    // counters with TILED's block flags and list of active blocks (8 bytes per block of 32 x 16 x 16 voxels); the pinned host words the
+    // counters come back through; sk_n = the side of the grid the result is for, 0: none.  The four buffers are freed by vp_ctx_release
+    vp::Buffer sk_grid, sk_tmp, sk_border, sk_aux;
+    uint64_t* sk_host = nullptr;
+    uint64_t sk_stats[3] = {};
+    uint32_t sk_n = 0;
 };
 
 namespace vp {
@@ -228,6 +236,12 @@ int launch_thickness(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint3
 int launch_octree(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int algo, uint64_t* h_nodes);
 int launch_octree_expand(vp_ctx* ctx, const Frame& f, const uint32_t* d_nodes, uint64_t nodes, uint32_t* d_words, int algo);
 int octree_validate(const uint32_t* h_nodes, uint64_t nodes, uint32_t n);
+// skeleton.hip: topological thinning of a whole grid into the context's own grid (blocks: the deleted count of every iteration is read back),
+// the table of the simple neighbourhoods on the device (2^21 words, enqueues only) and on the CPU
+int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const uint32_t* d_anchor, int mode, uint32_t max_iters, int algo,
+                    uint64_t* h_stats);
+int launch_skeleton_table(vp_ctx* ctx, int algo, uint32_t* d_table);
+void skeleton_table_cpu(int algo, uint32_t* h_table);
 // meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,

@@ -202,6 +202,18 @@ class Engine:
         return (torch.as_tensor(_DeviceView(dt, frame.voxels, "<i4", self), device=self.device),
                 torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device))
 
+    def skeleton(self, frame: Frame, words, mode: int = capi.SKEL_CURVE, max_iters: int = 0, anchor=None, algo: int = ALGO_TILED):
+        """Topological thinning of a grid (n <= 1024): returns (skel, stats) -- the grid of the voxels that are left, in the library's bit
+        layout, ready for components(), octree(), surface_nets() ..., and (voxels left, iterations, voxels deleted).  capi.SKEL_CURVE keeps
+        line ends and gives the one-voxel-wide centre line, capi.SKEL_KERNEL the homotopy kernel (a ball shrinks to one voxel, a torus to a
+        closed loop); both keep the 26-components of the solid and the 6-components of its complement.  `anchor` is an optional grid whose
+        voxels are never deleted; max_iters > 0 stops after that many iterations (a partial homotopic erosion).  The grid is a VIEW of a
+        buffer the context owns: it is overwritten by the next skeleton() and dies with release() / close() -- clone() what has to live
+        longer (also before it goes back in as `words` or `anchor`).  Blocking."""
+        stats = self.ctx.skeleton(frame, words.data_ptr(), mode, max_iters, 0 if anchor is None else anchor.data_ptr(), algo)
+        dg, _, _ = self.ctx.skeleton_result()
+        return torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device), stats
+
     def octree(self, frame: Frame, words, algo: int = ALGO_TILED):
         """Sparse voxel octree of a grid (n <= 1024): returns (nodes, level_offset, full_leaves) -- an int32 tensor of M x 2 words, the
         records (valid | full << 8, index of the first mixed child) breadth-first and in Morton order within a level, and two lists of 11:

@@ -602,6 +602,62 @@ int vp_octree_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int 
 int vp_octree_expand_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_nodes, uint64_t nodes, int algo, uint32_t* h_words);
 int vp_octree_validate_host(const uint32_t* h_nodes, uint64_t nodes, uint32_t n);
 
+/* ---- topological thinning: curve skeletons and homotopy kernels (no reference counterpart) ------------------------
+ * Reduces a solid to a one-voxel-wide remainder with the same topology (the "Skeletonize3D" next to the "Local Thickness" of Fiji / BoneJ,
+ * ITK's binary thinning), as an 8-subfield parallel thinning for (26, 6) connectivity.  S = the set voxels of a whole-grid frame,
+ * n % 32 == 0, n <= 1024.  OUTSIDE THE GRID COUNTS AS EMPTY, as in vp_thickness.
+ *   neighbourhood   a 27-bit mask m(p), bit i = (dx+1) + 3 (dy+1) + 9 (dz+1) set iff p + (dx, dy, dz) is in S; bit 13 is the centre and is
+ *                   ignored.  N26 = all other bits, N18 = those with |dx| + |dy| + |dz| <= 2, N6 = the six faces.
+ *   simple point    simple(m) holds iff (a) the object bits m & N26 are non-empty and form exactly one 26-connected component, and (b) the
+ *                   background bits ~m & N18 contain at least one face bit and all face bits among them lie in one 6-connected component
+ *                   of ~m & N18 (Bertrand & Malandain 1994 for (26, 6)).  It depends on 26 bits only; exactly 25,985,144 of the 2^26
+ *                   neighbourhoods are simple.
+ *   one iteration   B = { p in S, p not in the anchor, some face neighbour of p unset or outside the grid }, taken ONCE, at the start of
+ *                   the iteration.  Eight sub-iterations follow, s = 0 .. 7 in ascending order, s = (x & 1) | (y & 1) << 1 | (z & 1) << 2
+ *                   in absolute voxel coordinates.  In sub-iteration s every p in B of subfield s that is still set is examined against
+ *                   the CURRENT S and deleted iff simple(m(p)) and, in mode VP_SKEL_CURVE, popcount(m & N26) != 1 (line ends stay).
+ *                   Two voxels of one subfield are never 26-neighbours, so simultaneous deletion equals sequential deletion in any
+ *                   order: topology is preserved by construction and the result does not depend on the order of execution.
+ *   termination     iterations repeat until one deletes nothing or max_iters have run (max_iters = 0: no limit); `iterations` counts the
+ *                   iterations run, the empty last one included.  Every other iteration deletes at least one voxel.
+ *   modes           VP_SKEL_KERNEL: no end-point rule -- a ball shrinks to one voxel, a torus to a closed loop, a shell with a cavity to a
+ *                   closed one-voxel surface.  VP_SKEL_CURVE: the centre line.
+ *   anchor          optional grid whose voxels are never deleted (with VP_SKEL_KERNEL: anchored homotopic thinning, e.g. around the
+ *                   maxima of vp_edt).
+ * Integer logic with a fixed sub-iteration order: numpy, the C++ host form, VP_ALGO_NAIVE and VP_ALGO_TILED give the same bytes and the
+ * same three statistics h_stats = { voxels left, iterations, voxels deleted }.
+ *   vp_skeleton         builds the skeleton into a grow-only grid that the CONTEXT owns; vp_ctx_release frees it.  BLOCKS: the deleted
+ *                       count of every iteration is read back.
+ *   vp_skeleton_result  pointer to the last result, its statistics and the side it is for; any argument may be NULL.  Before a build and
+ *                       after a release: NULL, zeros and side 0.
+ *   vp_skeleton_host    host in, host out (grid and anchor staged through workspace slots); h_skel or h_stats may be NULL, not both.
+ *   vp_skeleton_table_host   bit c of the 2^21 words = simple(m) for m = (c & 0x1FFF) | (c >> 13) << 14, the 26 non-centre bits packed.
+ *                       ctx = NULL: computed on the CPU; otherwise by one launch.  VP_ALGO_NAIVE: the plain form of simple(), a flood fill
+ *                       over adjacency masks; VP_ALGO_TILED: the shift form -- in the x + 3 y + 9 z packing a 26-dilation is three masked
+ *                       shift pairs, a 6-dilation the OR of six masked shifts, run for a fixed 9 steps for (a) and 11 for (b): an
+ *                       exhaustive run needs at most 8 and 10 dilations to reach the component, one more shows the fixed point.
+ * A slab frame and n > 1024: VP_ERR_UNSUPPORTED.  Null ctx / f / words, a buffer that is not 16-byte aligned, d_words or d_anchor
+ * overlapping a buffer the context writes in this call (its result grid among them: copy the last skeleton before thinning it further),
+ * an unknown mode or algo: VP_ERR_INVALID.  A refusal is decided before anything is touched and leaves the previous result as it was.
+ * The result grid is an output like any other: a pending vp_jfa_start / vp_extract_count / vp_surfnets_count of a grid it overlaps is
+ * dropped.
+ *   algo: both run one border-mark launch and eight sub-iteration launches per iteration.  VP_ALGO_NAIVE -- one lane per word of 32
+ *   voxels from global memory with the plain form, ping-pong between two grids.  VP_ALGO_TILED -- one workgroup per block of 32 x 16 x 16
+ *   voxels staged in LDS with a one-voxel halo, candidates compacted over the workgroup before the shift form runs, updated in place (in
+ *   sub-iteration s only subfield-s bits change and nobody reads a subfield-s bit but its owner), driven by the list of the blocks that,
+ *   or a 26-neighbour of which, lost a voxel in the previous iteration (count, scan, write; no atomics on the grid).  Scratch of the
+ *   context (grow-only, freed by vp_ctx_release): n^3 / 8 bytes of border words, NAIVE's second grid, 8 bytes per block.
+ *   Timing books under existing keys: the copy of the input and the border marks under VP_K_SURFACE, the sub-iterations under
+ *   VP_K_MORPH (TILED) / VP_K_MORPH_NAIVE, the block list under VP_K_MD_SCAN, the final count under VP_K_MD_SPLIT, the device table
+ *   under VP_K_MD_NAIVE (plain form) / VP_K_MD_BRICK (shift form). */
+enum { VP_SKEL_KERNEL = 0, VP_SKEL_CURVE = 1 };
+int vp_skeleton(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, const uint32_t* d_anchor /* may be NULL */, int mode,
+                uint32_t max_iters, int algo, uint64_t* h_stats /* 3, may be NULL: voxels left, iterations, voxels deleted */);
+int vp_skeleton_result(vp_ctx* ctx, uint32_t** d_skel, uint64_t* h_stats /* 3 */, uint32_t* h_n);
+int vp_skeleton_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, const uint32_t* h_anchor /* may be NULL */, int mode,
+                     uint32_t max_iters, int algo, uint32_t* h_skel, uint64_t* h_stats /* either may be NULL, not both */);
+int vp_skeleton_table_host(vp_ctx* ctx /* NULL: computed on the CPU */, int algo, uint32_t* h_table /* 2^21 words: bit c = simple(c) */);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
