@@ -52,7 +52,7 @@ SYMBOLS = [
     "vp_device_count", "vp_ctx_create", "vp_ctx_destroy", "vp_ctx_set_stream", "vp_ctx_sync", "vp_last_error", "vp_abi_version",
     "vp_malloc", "vp_free", "vp_memset", "vp_memcpy_d2d", "vp_stream_copy", "vp_ctx_workspace", "vp_ctx_release", "vp_upload", "vp_download",
     "vp_grid_words", "vp_grid_voxels",
-    "vp_voxelize", "vp_csg", "vp_jfa_workspace_bytes", "vp_jfa_id_bytes", "vp_jfa_state_bytes", "vp_jfa", "vp_jfa_start", "vp_jfa_run", "vp_jfa_init", "vp_jfa_pass",
+    "vp_voxelize", "vp_csg", "vp_jfa_workspace_bytes", "vp_jfa_id_bytes", "vp_jfa_state_bytes", "vp_jfa_last_shapes", "vp_jfa", "vp_jfa_start", "vp_jfa_run", "vp_jfa_init", "vp_jfa_pass",
     "vp_jfa_finalize", "vp_jfa_last_pass", "vp_jfa_can_start_from_mask", "vp_jfa_can_fuse_first_two",
     "vp_jfa_window_bytes", "vp_jfa_window_span", "vp_jfa_window_clear", "vp_jfa_window_init", "vp_jfa_window_first_pass", "vp_jfa_window_first_two",
     "vp_jfa_window_pass", "vp_jfa_window_last_pass",
@@ -122,6 +122,12 @@ class Window(ctypes.Structure):
         w = cls()
         w.d_ids, w.bytes, w.planes, w.at = int(d_ids), int(nbytes), int(planes), int(at)
         return w
+
+
+class JfaShape(ctypes.Structure):
+    """vp_jfa_shape: one tile-kernel launch of the most recent pass call (vp_jfa_last_shapes; measurement and tests only)."""
+    _fields_ = [(name, ctypes.c_uint32) for name in ("id_format", "rows", "planes", "threads", "final_pass", "pair_mode", "closed", "full",
+                                                      "cyclic", "tiles", "split")]
 
 
 _lib = None
@@ -222,6 +228,7 @@ def lib():
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
         "vp_jfa_state_bytes": (_sz, [fp, ctypes.c_int]),
+        "vp_jfa_last_shapes": (ctypes.c_int, [_vp, ctypes.POINTER(JfaShape), ctypes.c_int]),
         "vp_jfa": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_float, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_start": (ctypes.c_int, [_vp, fp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_run": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_float, _vp, _vp, _sz, ctypes.c_int]),
@@ -417,6 +424,13 @@ class Context:
     def jfa_state_bytes(self, frame: Frame, algo: int = ALGO_TILED) -> int:
         """Bytes of id state per voxel vp_jfa streams per pass (whole grid): 4, 5 (windows above n = 1024) or 8 (VP_ALGO_NAIVE there)."""
         return int(lib().vp_jfa_state_bytes(ctypes.byref(frame), algo))
+
+    def jfa_last_shapes(self):
+        """The tile kernels the most recent pass call of this context launched, in launch order: one dict per launch with the fields of
+        vp_jfa_shape (empty after a call that was refused or served by another kernel).  Measurement and tests only."""
+        buf = (JfaShape * 4)()
+        count = int(lib().vp_jfa_last_shapes(self._h, buf, 4))
+        return [{name: int(getattr(buf[i], name)) for name, _ in JfaShape._fields_} for i in range(min(count, 4))]
 
     def jfa(self, frame: Frame, d_words: int, fill: float, d_sdf: int, d_work=None, work_bytes: int = 0,
             algo: int = ALGO_TILED):

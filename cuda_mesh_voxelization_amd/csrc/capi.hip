@@ -681,6 +681,7 @@ int vp_surface(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, const ui
 int vp_jfa_pass(vp_ctx* ctx, const vp_frame* f, uint32_t k, const void* d_in, const void* d_minus,
                 const void* d_plus, void* d_out, int algo)
 {
+    if (ctx) ctx->dense_shape_count = 0;
     if (!ctx || !d_in || !d_out || d_in == d_out) return set_error(VP_ERR_INVALID, "vp_jfa_pass: bad buffers");
     VP_TRY(bind_device(ctx));
     VP_TRY(check_frame(f, "vp_jfa_pass", false));
@@ -806,6 +807,13 @@ size_t vp_jfa_state_bytes(const vp_frame* f, int algo)
     return (algo == VP_ALGO_TILED && win_compact(f->n)) ? 5 : vp_jfa_id_bytes(f);
 }
 
+int vp_jfa_last_shapes(const vp_ctx* ctx, vp_jfa_shape* out, int cap)
+{
+    if (!ctx) return 0;
+    for (int i = 0; out && i < ctx->dense_shape_count && i < cap; ++i) out[i] = ctx->dense_shapes[i];
+    return ctx->dense_shape_count;
+}
+
 int vp_jfa_can_start_from_mask(const vp_frame* f, int algo)
 {
     return (f && check_frame(f, "vp_jfa_can_start_from_mask", false) == 0 && jfa_can_start_from_mask(make_frame(f), algo)) ? 1 : 0;
@@ -819,6 +827,7 @@ int vp_jfa_can_fuse_first_two(const vp_frame* f, int algo)
 int vp_jfa_last_pass(vp_ctx* ctx, const vp_frame* f, const void* d_in, const void* d_minus, const void* d_plus,
                      void* d_scratch, const uint32_t* d_words, float fill_unset, float* d_sdf, int algo)
 {
+    if (ctx) ctx->dense_shape_count = 0;
     if (!ctx || !d_in || !d_scratch || !d_words || !d_sdf || d_in == d_scratch)
         return set_error(VP_ERR_INVALID, "vp_jfa_last_pass: bad buffers");
     VP_TRY(bind_device(ctx));
@@ -959,6 +968,7 @@ int vp_jfa_window_first_two_cyclic(vp_ctx* ctx, const vp_frame* f, const uint32_
 int vp_jfa_window_pass_cyclic(vp_ctx* ctx, const vp_frame* f, uint32_t k, const vp_window* in, const vp_window* out, uint32_t ranks, uint32_t rank)
 {
     const char* who = "vp_jfa_window_pass_cyclic";
+    if (ctx) ctx->dense_shape_count = 0;
     IdWin wi, wo;
     VP_TRY(cyclic_check(ctx, f, in, ranks, rank, who, wi));
     VP_TRY(cyclic_check(ctx, f, out, ranks, rank, who, wo));
@@ -1008,6 +1018,7 @@ static void pass_reach(const vp_frame* f, uint32_t k, uint32_t stride, uint32_t&
 static int window_pass(vp_ctx* ctx, const vp_frame* f, uint32_t k, const vp_window* in, const vp_window* out, uint32_t stride,
                        const uint32_t* d_words, float fill, float* d_sdf, const char* who)
 {
+    if (ctx) ctx->dense_shape_count = 0;                            // vp_jfa_last_shapes: the launches of this call, none if it is refused
     if (!in || !out || !in->d_ids || !out->d_ids || in->d_ids == out->d_ids) return set_error(VP_ERR_INVALID, "%s: bad windows", who);
     if (in->planes != out->planes || in->at != out->at) return set_error(VP_ERR_INVALID, "%s: the two windows must have the same planes / at", who);
     // two windows carved from one allocation that partly overlap would have the pass read planes it is overwriting

@@ -579,6 +579,9 @@ void launch_tile(const DenseArgs& a)
                              : ID::kTab == 512 ? (RY == 8 ? 4u : (F && !final_mask_global<ID>()) ? 5u : 6u)
                              : NT == 512 ? (RY == 8 ? 2u : 3u) : 4u;
     const uint32_t sp = a.f.n > (uint32_t)NT ? tail_split(a.ctx, t, perCu) : 0u;     // a row of <= NT voxels has no halves
+    if (a.ctx->dense_shape_count < 4)                              // what this pass call launched (vp_jfa_last_shapes)
+        a.ctx->dense_shapes[a.ctx->dense_shape_count++] = vp_jfa_shape{std::is_same<ID, IdC>::value ? 11u : ID::kTab == 512 ? 9u : 10u,
+            (uint32_t)RY, (uint32_t)CH, (uint32_t)NT, F ? 1u : 0u, (uint32_t)PM, (uint32_t)CL, FULL ? 1u : 0u, CYC ? 1u : 0u, t, sp};
     hipLaunchKernelGGL((jfa_pass_dense<ID, RY, CH, NT, F, PM, CL, FULL, CYC>), dim3(t + sp), dim3(NT), 0, a.ctx->stream, a.f, a.k, a.ka,
                        a.in, a.inB, a.out, a.outB, a.none_row, a.words, a.fill, a.sdf, ty, t, sp, a.cyc);
 }
@@ -588,7 +591,8 @@ void launch_tile(const DenseArgs& a)
 // those keep 4 rows, profiles/r03/ab_ry8_*.txt, r04/ab_gnt_ry8_1024.txt).  FULL (compile-time row / plane counts where every tile is whole):
 // dense -3.2 % at n = 512, -5 % at n = 2048, fused last pass -1 / -4 / -3 %; the id passes with the 4-KB tables lose 4 % (80 VGPRs + 8
 // spilled instead of 71 under the six-wave bound) and keep the run-time counts (profiles/r04/ab_full_*.txt).  Pair mode: 8-plane tiles of
-// power-of-two grids whose rows are whole NT-thread iterations; the lane permutation follows k; k = 2 with the 2-KB tables keeps the plain
+// power-of-two grids whose rows are whole NT-thread iterations and a step that is a power of two itself (every step of the halving sequence
+// there; any other step the ABI accepts runs the plain form); the lane permutation follows k; k = 2 with the 2-KB tables keeps the plain
 // form (7 % faster there: 0.370 vs 0.396 ms; with the 4-KB tables pairs win by 3 %).
 template <int V> using int_c = std::integral_constant<int, V>;
 
@@ -616,7 +620,7 @@ void launch_shape(const DenseArgs& a, bool pairsOk, bool wholeChains)
             else {
                 if constexpr (ID::kTab != 512) { if (a.k == 2) { go(int_c<2>{}); return; } }
                 if (a.k == 4) { go(int_c<4>{}); return; }
-                if (a.k >= 8) { go(int_c<8>{}); return; }
+                if (a.k >= 8 && (a.k & (a.k - 1u)) == 0u) { go(int_c<8>{}); return; }   // (the lane -> x map masks with k - 1: powers of two only)
             }
         }
     }

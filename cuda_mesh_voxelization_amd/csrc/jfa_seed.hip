@@ -545,6 +545,7 @@ int launch_win_pass(vp_ctx* ctx, const Frame& f, uint32_t k, const IdWin& in, co
                     const uint32_t* d_words, float fill, float* d_sdf)
 {
     ProfScope p(ctx, d_sdf ? VP_K_JFA_LAST : k * 4 >= f.n ? VP_K_JFA_SPARSE : VP_K_JFA_DENSE);
+    ctx->dense_shape_count = 0;                                    // the shapes of THIS pass call (vp_jfa_last_shapes)
     if (d_sdf) {
         if (win_compact(f.n)) return launch_dense_idc_last(ctx, f, k, in, out, stride, d_words, fill, d_sdf);
         if (f.n <= 512)       return launch_dense_id9_last(ctx, f, k, in, out, stride, d_words, fill, d_sdf);
@@ -569,6 +570,7 @@ uint32_t jfa_cyclic_passes(uint32_t n, uint32_t ranks)
 int launch_win_pass_cyclic(vp_ctx* ctx, const Frame& f, uint32_t k, const IdWin& in, const IdWin& out, uint32_t ranks, uint32_t rank)
 {
     ProfScope p(ctx, VP_K_JFA_DENSE);
+    ctx->dense_shape_count = 0;
     if (win_compact(f.n)) return launch_cyclic_idc_pass(ctx, f, k, in, out, ranks, rank);
     if (f.n <= 512)       return launch_cyclic_id9_pass(ctx, f, k, in, out, ranks, rank);
     return launch_cyclic_id10_pass(ctx, f, k, in, out, ranks, rank);

@@ -60,6 +60,10 @@ struct vp_ctx {
         size_t work_bytes = 0;
         const uint32_t* words = nullptr;
     } jfa_started;
+    // the tile-kernel launches of the most recent pass call (jfa_dense.hip, launch_tile; vp_jfa_last_shapes): a pass whose chains are
+    // split makes two, so four is room enough; a host-side note, no device work
+    vp_jfa_shape dense_shapes[4];
+    int dense_shape_count = 0;
     vp::Buffer slots[VP_WORKSPACE_SLOTS];      // vp_ctx_workspace
     // vp_extract_*: block counts / offsets of the last count call and what it was for
     vp::Buffer ext_cnt, ext_off;

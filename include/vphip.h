@@ -687,6 +687,26 @@ size_t vp_jfa_id_bytes(const vp_frame* f);
 /* Bytes of id state per voxel that vp_jfa really streams per pass -- the S of SURVEY.md 8(d) "as implemented": 4 for n <= 1024; above
  * that 5 with VP_ALGO_TILED (windows: a 32-bit word plane + a byte plane), 8 with VP_ALGO_NAIVE.  Measurement only. */
 size_t vp_jfa_state_bytes(const vp_frame* f, int algo);
+/* Which tile kernels the most recent pass call of this context launched (vp_jfa_window_pass, vp_jfa_window_last_pass,
+ * vp_jfa_window_pass_cyclic, and vp_jfa_pass / vp_jfa_last_pass: every one of them clears the record when it starts, so a call that is
+ * refused or served by another kernel leaves it empty): one entry per launch in launch order, the template arguments of the
+ * instantiation and the size of its grid.  Returns the number of launches (at most 4: a pass whose plane chains are split makes two)
+ * and stores the first min(that, cap) of them in `out`; 0 for a null context.  A host-side note, no device work.  Measurement and
+ * tests only: the shapes are an implementation detail and change with the kernels. */
+typedef struct vp_jfa_shape {
+    uint32_t id_format;   /* 9, 10: the 32-bit ids of n <= 512 / n <= 1024; 11: the compact ids above */
+    uint32_t rows;        /* y rows per tile */
+    uint32_t planes;      /* z planes per tile */
+    uint32_t threads;     /* per workgroup */
+    uint32_t final_pass;  /* 1: fused with the id -> sdf conversion */
+    uint32_t pair_mode;   /* 0 (none), 1, 2, 4, 8 */
+    uint32_t closed;      /* != 0: the closed 8 x 8 tile of the pass k = n/8 */
+    uint32_t full;        /* 1: compile-time chain lengths */
+    uint32_t cyclic;      /* 1: cyclic plane distribution */
+    uint32_t tiles;       /* tiles of the launch */
+    uint32_t split;       /* how many of them run as two half-row workgroups (grid = tiles + split) */
+} vp_jfa_shape;
+int vp_jfa_last_shapes(const vp_ctx* ctx, vp_jfa_shape* out, int cap);
 int vp_jfa(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fill_unset,
            float* d_sdf, void* d_work, size_t work_bytes, int algo);
 /* vp_jfa in the two parts the reference times separately ("::Initialization" = seeding, jfa/tiled.cu:265-290;

@@ -4,6 +4,7 @@ the SDF is compared bit-exactly too (tolerance of the north star: 1e-4 relative 
 well, so a future non-bit-exact kernel still has a written bound)."""
 import math
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +13,9 @@ import torch
 from cuda_mesh_voxelization_amd import capi, mesh as M
 from cuda_mesh_voxelization_amd.capi import ALGO_NAIVE, ALGO_TILED, Frame
 from oracle import oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from jfa_pass_ref import coords_plain64 as _coords_plain64, coords_window as _coords_window  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -841,21 +845,6 @@ def test_window_calls_check_their_arguments(engine):
     with pytest.raises(capi.VPError, match="whole-grid"):
         ctx.jfa_window_first_two(slab, engine.new_grid(fr).data_ptr(), ok(a))
     engine.sync()
-
-
-def _coords_plain64(t):
-    """(x, scr(y), scr(z), none) of plain 8-byte ids (jfa_common.h: Id64 -- .x = scr(z) << 2 | x << 13, .y = scr(y) << 2, "none" = all ones)"""
-    lo, hi = (t & 0xFFFFFFFF), ((t >> 32) & 0xFFFFFFFF)
-    none = lo == 0xFFFFFFFF
-    return (lo >> 13) & 2047, (hi >> 2) & 2047, (lo >> 2) & 2047, none
-
-
-def _coords_window(w, planes, n):
-    """the same of a window above n = 1024 (IdC: word plane x | scr(y) << 11 | (scr(z) & 1023) << 22, byte plane = top z bit << 1 | none << 2)"""
-    vox = planes * n * n
-    word = w[:vox * 4].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    byte = w[vox * 4:vox * 5].to(torch.int64)
-    return word & 2047, (word >> 11) & 2047, ((word >> 22) & 1023) | ((byte & 2) << 9), (byte & 4) != 0
 
 
 @pytest.mark.parametrize("n,kind", [(512, "noise"), (512, "sparse"), (512, "mesh"), (1024, "sparse"), (288, "noise"), (1152, "noise"), (256, "noise"), (1024, "noise"),
