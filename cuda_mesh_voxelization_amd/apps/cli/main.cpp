@@ -43,6 +43,14 @@
 //                            writes PREFIX.skel.u32 (a grid).  One device only (-g > 1 is refused)
 //         --skeleton-only    (extension, with --skeleton) the grid is replaced by the skeleton before the exports that follow, --octree and
 //                            -s: -e writes out/skel_<type>_<output>, and -d PREFIX.grid.u32 holds it
+//         --geodesic S[:M]   (extension) geodesic distance inside the FINAL grid -- where --octree sits, after --thin-only and --skeleton-only, so
+//                            that "--skeleton curve --skeleton-only --geodesic zmin" measures the centre line: the length of the shortest path
+//                            that stays inside the grid from the seed voxels to every set voxel (include/vphip.h, vp_geodesic;
+//                            vox/geodesic.h).  S = zmin | zmax (the set voxels of the lowest / highest occupied z plane) | X,Y,Z (one voxel,
+//                            which must be set), M = 6 (face steps) | 26 (all 26 steps at cost 1) | chamfer (costs 3, 4, 5; the default).
+//                            Prints "geodesic: n N, seeds S, reached R of V set, max D at (x, y, z)".  -d PREFIX additionally writes
+//                            PREFIX.geo.u32 (n^3 values, 0xFFFFFFFF where no path arrives) and PREFIX.reach.u32 (a grid).  One device only
+//                            (-g > 1 is refused)
 //         --octree           (extension) sparse voxel octree of the FINAL grid -- where --thickness sits: after the voxelization, --morph, --fill,
 //                            CSG, --thin-only and --skeleton-only (include/vphip.h, vp_octree; vox/octree.h): writes out/<output stem>_<type>_out.svo, the
 //                            same bytes for every -t, and prints the nodes per level, the bytes and the ratio to the n^3 / 8 bytes of the
@@ -103,6 +111,7 @@
 #include "mesh/mesh.h"
 #include "mesh/mesh_io.h"
 #include "proc_utils.h"
+#include "vox/geodesic.h"
 #include "vox/octree.h"
 #include "vox/skeleton.h"
 #include "vox/vox.h"
@@ -138,6 +147,9 @@ struct Options {
     int skeleton = -1;                                      // --skeleton curve|kernel[:ITERS]: VOX::SkeletonMode, -1 = not asked for
     unsigned skeletonIters = 0;
     bool skeletonOnly = false;
+    bool geodesic = false;                                  // --geodesic SEED[:METRIC]
+    int geoSeed = 0, geoMetric = 2;                         // 0: zmin, 1: zmax, 2: the voxel geoVoxel; VOX::GeodesicMetric
+    unsigned geoVoxel[3] = {0, 0, 0};
     bool octree = false;                                    // --octree: out/<output stem>_<type>_out.svo of the final grid
     bool exactSdf = false;
     int meshSdf = 0;                                        // --mesh-sdf BAND: band in voxels, 0 = not asked for
@@ -243,6 +255,11 @@ const char* kUsage =
     "                        the skeleton.  -d PREFIX adds PREFIX.skel.u32.  One device only: not with -g > 1 (extension)\n"
     "      --skeleton-only   With --skeleton: replace the grid by the skeleton, so that -e (out/skel_<type>_<output>), --octree, -s\n"
     "                        and -d see it (extension)\n"
+    "      --geodesic arg    Geodesic distance inside the final grid (where --octree sits, after --thin-only and --skeleton-only): arg =\n"
+    "                        SEED[:METRIC], SEED = zmin or zmax (the set voxels of the lowest / highest occupied z plane) or X,Y,Z (one set\n"
+    "                        voxel), METRIC = 6 (face steps), 26 (all steps at cost 1) or chamfer (costs 3, 4, 5: divide by 3; default).\n"
+    "                        Prints the seeds, the voxels reached and the farthest voxel.  -d PREFIX adds PREFIX.geo.u32 and\n"
+    "                        PREFIX.reach.u32.  One device only: not with -g > 1 (extension)\n"
     "      --octree          Sparse voxel octree of the final grid (after --morph, --fill, CSG, --thin-only and --skeleton-only): writes\n"
     "                        out/<output stem>_<type>_out.svo, the same bytes for every -t, and prints its size against the grid's.\n"
     "                        n a multiple of 32 up to 1024.  One device only: not with -g > 1 (extension)\n"
@@ -284,7 +301,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"skeleton", 'K'}, {"skeleton-only", 'Q'},{"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"skeleton", 'K'}, {"skeleton-only", 'Q'}, {"geodesic", 'G'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -350,6 +367,30 @@ Options Parse(int argc, char** argv)
                 const bool digits = !value.empty() && value.size() <= 2 && value.find_first_not_of("0123456789") == std::string::npos;
                 cpuAssert(digits && std::stoi(value) >= 1 && std::stoi(value) <= 32, "--mesh-sdf: '" + value + "' is not a band of 1..32 voxels\n");
                 o.meshSdf = std::stoi(value);
+                break;
+            }
+            case 'G': {
+                // SEED[:METRIC], SEED = zmin | zmax | X,Y,Z
+                const size_t colon = value.find(':');
+                const std::string seed = value.substr(0, colon), metric = colon == std::string::npos ? "chamfer" : value.substr(colon + 1);
+                const std::string bad = "--geodesic: '" + value + "' is not SEED[:METRIC] with SEED = zmin, zmax or X,Y,Z and METRIC = 6, 26 or chamfer\n";
+                cpuAssert(metric == "6" || metric == "26" || metric == "chamfer", bad);
+                o.geoMetric = metric == "6" ? VOX::GEODESIC_6 : metric == "26" ? VOX::GEODESIC_26 : VOX::GEODESIC_CHAMFER;
+                if (seed == "zmin" || seed == "zmax") {
+                    o.geoSeed = seed == "zmin" ? 0 : 1;
+                } else {
+                    size_t at = 0;
+                    for (int k = 0; k < 3; ++k) {
+                        const size_t end = k < 2 ? seed.find(',', at) : seed.size();
+                        cpuAssert(end != std::string::npos && end > at, bad);
+                        const std::string part = seed.substr(at, end - at);
+                        cpuAssert(part.size() <= 6 && part.find_first_not_of("0123456789") == std::string::npos, bad);
+                        o.geoVoxel[k] = static_cast<unsigned>(std::stoul(part));
+                        at = end + 1;
+                    }
+                    o.geoSeed = 2;
+                }
+                o.geodesic = true;
                 break;
             }
             case 'K': {
@@ -489,6 +530,43 @@ void OctreeOut(const HostVoxelsGrid<gridType>& grid, const std::string& path)
     std::printf("], %zu bytes, grid %.0f bytes, ratio %.2f, %s\n", tree.Bytes(), gridBytes, gridBytes / static_cast<double>(tree.Bytes()), path.c_str());
 }
 
+// --geodesic: the distance inside `grid` from the seeds `seed` names (0: the lowest occupied z plane, 1: the highest, 2: the voxel xyz) into
+// `dist` and `reach`; prints what the flag promises
+template <Types T>
+void Geodesic(int seed, const unsigned xyz[3], int metric, const HostVoxelsGrid<gridType>& grid, HostGrid<uint32_t>& dist,
+              HostVoxelsGrid<gridType>& reach)
+{
+    const size_t n = grid.View().VoxelsPerSide(), plane = n * n;
+    HostVoxelsGrid<gridType> seeds(n, grid.View().VoxelSize());
+    const uint32_t* bits = reinterpret_cast<const uint32_t*>(grid.View().Data());
+    uint32_t* sbits = reinterpret_cast<uint32_t*>(seeds.View().Data());
+    const size_t words = (n * n * n + 31) / 32;
+    std::fill(sbits, sbits + words, 0u);
+    auto set = [&](const uint32_t* w, size_t i) { return (w[i >> 5] >> (i & 31)) & 1u; };
+    uint64_t total = 0;
+    size_t zlo = n, zhi = n;
+    for (size_t i = 0; i < n * n * n; ++i)
+        if (set(bits, i)) {
+            ++total;
+            if (zlo == n) zlo = i / plane;
+            zhi = i / plane;
+        }
+    if (seed == 2) {
+        const size_t i = xyz[0] + n * (xyz[1] + n * xyz[2]);
+        cpuAssert(xyz[0] < n && xyz[1] < n && xyz[2] < n && set(bits, i), "--geodesic: the seed voxel is not a set voxel of the grid\n");
+        sbits[i >> 5] |= 1u << (i & 31);
+    } else if (total) {
+        const size_t z = seed == 0 ? zlo : zhi;
+        for (size_t i = z * plane; i < (z + 1) * plane; ++i)
+            if (set(bits, i)) sbits[i >> 5] |= 1u << (i & 31);
+    }
+    const VOX::GeodesicStats st = VOX::GeodesicDistance<T>(grid, seeds, static_cast<VOX::GeodesicMetric>(metric), dist, &reach);
+    std::printf("geodesic: n %zu, seeds %llu, reached %llu of %llu set, max %llu at (%llu, %llu, %llu)\n", n,
+                static_cast<unsigned long long>(st.seeds), static_cast<unsigned long long>(st.reached), static_cast<unsigned long long>(total),
+                static_cast<unsigned long long>(st.maxDist), static_cast<unsigned long long>(st.maxIndex % n),
+                static_cast<unsigned long long>(st.maxIndex / n % n), static_cast<unsigned long long>(st.maxIndex / plane));
+}
+
 template <Types T>
 void Csg(CSG::Op op, HostVoxelsGrid<gridType>& a, HostVoxelsGrid<gridType>& b)
 {
@@ -548,6 +626,9 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.octree && opt.gpus > 1), "--octree runs on one device: -g must be 1\n");
     cpuAssert(!(opt.skeleton >= 0 && opt.gpus > 1), "--skeleton runs on one device: -g must be 1\n");
     cpuAssert(!(opt.skeletonOnly && opt.skeleton < 0), "--skeleton-only needs --skeleton curve|kernel\n");
+    cpuAssert(!(opt.geodesic && opt.gpus > 1), "--geodesic runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.geodesic && opt.geoSeed == 2 && (opt.geoVoxel[0] >= opt.numVoxels || opt.geoVoxel[1] >= opt.numVoxels || opt.geoVoxel[2] >= opt.numVoxels)),
+              "--geodesic: the seed voxel lies outside the grid\n");
     cpuAssert(!(opt.octree && (opt.numVoxels % 32 != 0 || opt.numVoxels > 1024)), "--octree needs -n to be a multiple of 32 up to 1024\n");
     cpuAssert(!(opt.thinOnly && !(opt.thickness && opt.thinWidth)), "--thin-only needs --thickness RMAX:W: the thin grid is that of a width\n");
     cpuAssert(!(!opt.morph.empty() && opt.gpus > 1), "--morph runs on one device: -g must be 1\n");
@@ -598,7 +679,8 @@ int main(int argc, char** argv)
     HostVoxelsGrid<gridType> emptyGrid(N, voxelSize);       // benchmark-mode CSG operand (main.cpp:89,127)
     HostGrid<float> sdf;
     HostGrid<uint32_t> thick;
-    HostVoxelsGrid<gridType> thinGrid, skelGrid;
+    HostVoxelsGrid<gridType> thinGrid, skelGrid, geoReach;
+    HostGrid<uint32_t> geoDist;
     const std::string typeName = GetTypesString(TYPE);
     if (EXPORT || opt.octree) std::filesystem::create_directories("out");
 
@@ -708,6 +790,15 @@ int main(int argc, char** argv)
             }
         }
 
+        if (opt.geodesic) {
+            switch (TYPE) {
+                case Types::SEQUENTIAL: Geodesic<Types::SEQUENTIAL>(opt.geoSeed, opt.geoVoxel, opt.geoMetric, grids[0], geoDist, geoReach); break;
+                case Types::OPENMP:     Geodesic<Types::OPENMP>(opt.geoSeed, opt.geoVoxel, opt.geoMetric, grids[0], geoDist, geoReach); break;
+                case Types::NAIVE:      Geodesic<Types::NAIVE>(opt.geoSeed, opt.geoVoxel, opt.geoMetric, grids[0], geoDist, geoReach); break;
+                case Types::TILED:      Geodesic<Types::TILED>(opt.geoSeed, opt.geoVoxel, opt.geoMetric, grids[0], geoDist, geoReach); break;
+            }
+        }
+
         if (EXPORT && OPERATION != CSG::Op::VOID) {                                                     // main.cpp:192-197
             Mesh outMesh;
             GridMesh(GPU, opt.surfaceOnly, opt.surfaceNets, grids[0].View(), outMesh);
@@ -790,6 +881,10 @@ int main(int argc, char** argv)
         WriteRaw(opt.dump + ".grid.u32", grids[0].View().Data(), grids[0].View().StorageSize() * sizeof(gridType));
         if (opt.sdf) WriteRaw(opt.dump + ".sdf.f32", sdf.View().Data(), sdf.View().Size() * sizeof(float));
         if (opt.thickness) WriteRaw(opt.dump + ".thick.u32", thick.View().Data(), thick.View().Size() * sizeof(uint32_t));
+        if (opt.geodesic) {
+            WriteRaw(opt.dump + ".geo.u32", geoDist.View().Data(), geoDist.View().Size() * sizeof(uint32_t));
+            WriteRaw(opt.dump + ".reach.u32", geoReach.View().Data(), geoReach.View().StorageSize() * sizeof(gridType));
+        }
         if (opt.skeleton >= 0) WriteRaw(opt.dump + ".skel.u32", skelGrid.View().Data(), skelGrid.View().StorageSize() * sizeof(gridType));
         if (opt.thickness && opt.thinWidth) WriteRaw(opt.dump + ".thin.u32", thinGrid.View().Data(), thinGrid.View().StorageSize() * sizeof(gridType));
     }

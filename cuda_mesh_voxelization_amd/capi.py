@@ -20,6 +20,8 @@ MESH_NONE = 0xFFFFFFFF                                              # vp_mesh_di
 ISO_LINEAR, ISO_SIGNED_SQUARE = 0, 1                                # vp_isonets: the field as it is / sign(v) sqrt|v| (every sdf of the library)
 CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
 SKEL_KERNEL, SKEL_CURVE = 0, 1                                      # vp_skeleton: the homotopy kernel / the centre line (line ends stay)
+GEO_6, GEO_26, GEO_CHAMFER = 0, 1, 2                                # vp_geodesic: face steps / all 26 steps at cost 1 / at cost 3, 4, 5
+GEO_NONE = 0xFFFFFFFF                                               # vp_geodesic: "no path from a seed arrives here"
 COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
 MULTI_HALO, MULTI_GHOST, MULTI_HYBRID, MULTI_TRANSPOSE = 0, 1, 2, 3
@@ -72,6 +74,7 @@ SYMBOLS = [
     "vp_thickness", "vp_thickness_result", "vp_thickness_host",
     "vp_octree", "vp_octree_result", "vp_octree_expand", "vp_octree_expand_result", "vp_octree_host", "vp_octree_expand_host", "vp_octree_validate_host",
     "vp_skeleton", "vp_skeleton_result", "vp_skeleton_host", "vp_skeleton_table_host",
+    "vp_geodesic", "vp_geodesic_result", "vp_geodesic_host",
 ]
 
 
@@ -224,6 +227,9 @@ def lib():
         "vp_skeleton_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
         "vp_skeleton_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, _vp, _vp]),
         "vp_skeleton_table_host": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+        "vp_geodesic": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+        "vp_geodesic_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_geodesic_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -641,7 +647,33 @@ class Context:
         check(lib().vp_skeleton_result(self._h, ctypes.byref(d), s, ctypes.byref(n)))
         return d.value or 0, tuple(int(v) for v in s), int(n.value)
 
+    def geodesic(self, frame: Frame, d_mask: int, d_seeds: int, metric: int = GEO_CHAMFER, algo: int = ALGO_TILED):
+        """Geodesic distance inside the mask from the seed voxels of a whole grid (n <= 1024) into buffers the context owns;
+        geodesic_result() hands them out.  Blocks (convergence is read back) and returns (seeds used, voxels reached, largest finite
+        distance, lowest linear index that attains it)."""
+        s = (ctypes.c_uint64 * 4)()
+        check(lib().vp_geodesic(self._h, ctypes.byref(frame), _vp(d_mask or None), _vp(d_seeds or None), metric, algo, s))
+        return tuple(int(v) for v in s)
+
+    def geodesic_result(self):
+        """(d_dist, d_reach, stats, n) of the last geodesic(): the device pointers as ints (0 where there is none), the four statistics
+        and the side they are for.  Valid until the next geodesic(), release() or close()."""
+        d, r, s, n = _vp(), _vp(), (ctypes.c_uint64 * 4)(), ctypes.c_uint32()
+        check(lib().vp_geodesic_result(self._h, ctypes.byref(d), ctypes.byref(r), s, ctypes.byref(n)))
+        return d.value or 0, r.value or 0, tuple(int(v) for v in s), int(n.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
+    def geodesic_host(self, frame: Frame, h_mask, h_seeds, metric: int = GEO_CHAMFER, algo: int = ALGO_TILED, want=(True, True, True)):
+        """numpy in, numpy out: (dist uint32[n^3], reach words uint32[n^3 / 32], statistics); want = which of the three are asked for (the
+        others go in as NULL and come back as None)."""
+        np = __import__("numpy")
+        d = np.empty(frame.voxels, np.uint32) if want[0] else None
+        r = np.empty(frame.voxels // 32, np.uint32) if want[1] else None
+        s = (ctypes.c_uint64 * 4)() if want[2] else None
+        check(lib().vp_geodesic_host(self._h, ctypes.byref(frame), h_mask.ctypes.data_as(_vp), h_seeds.ctypes.data_as(_vp), metric, algo,
+                                     None if d is None else d.ctypes.data_as(_vp), None if r is None else r.ctypes.data_as(_vp), s))
+        return d, r, None if s is None else tuple(int(v) for v in s)
+
     def skeleton_host(self, frame: Frame, h_words, mode: int = SKEL_CURVE, max_iters: int = 0, h_anchor=None, algo: int = ALGO_TILED):
         """numpy in, numpy out: (skeleton words uint32[n^3 / 32], (voxels left, iterations, voxels deleted))."""
         np = __import__("numpy")

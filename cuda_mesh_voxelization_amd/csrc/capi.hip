@@ -216,7 +216,8 @@ int vp_ctx_destroy(vp_ctx* ctx)
                        &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree,
                        &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum,
                        &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt, &ctx->oc_grid,
-                       &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux };
+                       &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux,
+                       &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux };
     for (Buffer* b : bufs) release(*b);
     for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -232,6 +233,7 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (ctx->th_host) (void)hipHostFree(ctx->th_host);
     if (ctx->oc_host) (void)hipHostFree(ctx->oc_host);
     if (ctx->sk_host) (void)hipHostFree(ctx->sk_host);
+    if (ctx->gd_host) (void)hipHostFree(ctx->gd_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -322,6 +324,8 @@ int vp_ctx_release(vp_ctx* ctx)
     ctx->oc_count = 0;
     for (Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) release(*b);                                  // vp_skeleton: scratch and result
     ctx->sk_n = 0;
+    for (Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) release(*b);                                                 // vp_geodesic: result and scratch
+    ctx->gd_n = 0;
     ctx->jfa_started.valid = false;
     ctx->ext_words = nullptr;
     ctx->sn_words = nullptr;
@@ -1362,6 +1366,50 @@ int vp_skeleton_result(vp_ctx* ctx, uint32_t** d_skel, uint64_t* h_stats, uint32
     return 0;
 }
 
+// ---- geodesic distance ------------------------------------------------------------------------------
+// what vp_geodesic and its host form share: whole grids up to n = 1024, the metric and the algo
+static int check_geodesic(const vp_frame* f, const char* who, int metric, int algo)
+{
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_whole(f, who));
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
+    VP_TRY(check_algo(who, algo));
+    if (metric != VP_GEO_6 && metric != VP_GEO_26 && metric != VP_GEO_CHAMFER) return set_error(VP_ERR_INVALID, "%s: unknown metric %d", who, metric);
+    return 0;
+}
+
+int vp_geodesic(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_mask, const uint32_t* d_seeds, int metric, int algo, uint64_t* h_stats)
+{
+    const char* who = "vp_geodesic";
+    if (!ctx || !f || !d_mask || !d_seeds) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_geodesic(f, who, metric, algo));
+    VP_TRY(check_aligned(who, {d_mask, d_seeds}));
+    // the mask and the seeds are read while every buffer of the call is written: they may lie in none of them (the last reach grid has to
+    // be copied before it goes back in as a mask or as seeds)
+    for (const Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) {
+        VP_TRY(check_disjoint(who, "a buffer of the context", d_mask, vp_grid_words(f) * 4, b->ptr, b->bytes));
+        VP_TRY(check_disjoint(who, "a buffer of the context", d_seeds, vp_grid_words(f) * 4, b->ptr, b->bytes));
+    }
+    // the context's own buffers are outputs like any other: what was recorded about their bytes is gone, before and after they grow
+    for (Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) grid_written(ctx, b->ptr, b->bytes);
+    const int rc = launch_geodesic(ctx, make_frame(f), d_mask, d_seeds, metric, algo, h_stats);
+    for (Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) grid_written(ctx, b->ptr, b->bytes);
+    return rc;
+}
+
+int vp_geodesic_result(vp_ctx* ctx, uint32_t** d_dist, uint32_t** d_reach, uint64_t* h_stats, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_geodesic_result: null ctx");
+    const bool any = ctx->gd_n != 0;
+    if (d_dist) *d_dist = any ? (uint32_t*)ctx->gd_dist.ptr : nullptr;
+    if (d_reach) *d_reach = any ? (uint32_t*)ctx->gd_reach.ptr : nullptr;
+    if (h_stats)
+        for (int i = 0; i < 4; ++i) h_stats[i] = any ? ctx->gd_stats[i] : 0;
+    if (h_n) *h_n = ctx->gd_n;
+    return 0;
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1542,6 +1590,23 @@ int vp_skeleton_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, co
     }
     VP_TRY(vp_skeleton(ctx, f, (const uint32_t*)dw, (const uint32_t*)da, mode, max_iters, algo, h_stats));
     return h_skel ? vp_download(ctx, h_skel, ctx->sk_grid.ptr, wb) : 0;
+}
+
+int vp_geodesic_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, const uint32_t* h_seeds, int metric, int algo, uint32_t* h_dist,
+                     uint32_t* h_reach, uint64_t* h_stats)
+{
+    const char* who = "vp_geodesic_host";
+    if (!ctx || !f || !h_mask || !h_seeds || (!h_dist && !h_reach && !h_stats)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_geodesic(f, who, metric, algo));
+    void *dm = nullptr, *ds = nullptr;
+    const size_t wb = vp_grid_words(f) * 4;
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dm));
+    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &ds));
+    VP_TRY(vp_upload(ctx, dm, h_mask, wb));
+    VP_TRY(vp_upload(ctx, ds, h_seeds, wb));
+    VP_TRY(vp_geodesic(ctx, f, (const uint32_t*)dm, (const uint32_t*)ds, metric, algo, h_stats));
+    if (h_dist) VP_TRY(vp_download(ctx, h_dist, ctx->gd_dist.ptr, vp_grid_voxels(f) * 4));
+    return h_reach ? vp_download(ctx, h_reach, ctx->gd_reach.ptr, wb) : 0;
 }
 
 int vp_skeleton_table_host(vp_ctx* ctx, int algo, uint32_t* h_table)

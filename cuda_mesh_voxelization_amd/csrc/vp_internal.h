@@ -164,6 +164,14 @@ struct vp_ctx {
     uint64_t* sk_host = nullptr;
     uint64_t sk_stats[3] = {};
     uint32_t sk_n = 0;
+    // geodesic distance (geodesic.hip): D (4 n^3 bytes) and the reach grid (n^3 / 8 bytes) of the last vp_geodesic, which the context owns
+    // and vp_geodesic_result hands out, and its four statistics; the counters with TILED's block flags and list of active blocks (8 bytes
+    // per block of 32 x 16 x 16 voxels) or NAIVE's ring of round flags; the pinned host words they come back through; gd_n = the side the
+    // result is for, 0: none.  The three buffers are freed by vp_ctx_release
+    vp::Buffer gd_dist, gd_reach, gd_aux;
+    uint64_t* gd_host = nullptr;
+    uint64_t gd_stats[4] = {};
+    uint32_t gd_n = 0;
 };
 
 namespace vp {
@@ -246,6 +254,9 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
                     uint64_t* h_stats);
 int launch_skeleton_table(vp_ctx* ctx, int algo, uint32_t* d_table);
 void skeleton_table_cpu(int algo, uint32_t* h_table);
+// geodesic.hip: geodesic distances inside a mask from seed voxels and the reach grid, into the context's own buffers (blocks: the round
+// flags or the length of the block list are read back)
+int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const uint32_t* d_seeds, int metric, int algo, uint64_t* h_stats);
 // meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,

@@ -214,6 +214,20 @@ class Engine:
         dg, _, _ = self.ctx.skeleton_result()
         return torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device), stats
 
+    def geodesic(self, frame: Frame, mask, seeds, metric: int = capi.GEO_CHAMFER, algo: int = ALGO_TILED):
+        """Geodesic distance of a grid (n <= 1024): returns (dist, reach, stats) -- a tensor of n^3 values, x fastest, the length of the
+        shortest path from a seed voxel that stays inside `mask` (0 at the seeds inside the mask; capi.GEO_NONE, which reads -1 in the
+        int32 view, where no path arrives and outside the mask), the grid of the reached voxels in the library's bit layout -- the
+        components of the mask that touch a seed, ready for components(), octree() ... -- and (seeds used, voxels reached, largest
+        finite distance, lowest linear index that attains it).  A step to a face / edge / corner neighbour costs 1 / - / - (capi.GEO_6),
+        1 / 1 / 1 (capi.GEO_26) or 3 / 4 / 5 (capi.GEO_CHAMFER: divide by 3 for voxels).  Both tensors are VIEWS of buffers the context
+        owns: they are overwritten by the next geodesic() and die with release() / close() -- clone() what has to live longer (the reach
+        grid too, before it goes back in as `mask` or `seeds`).  Blocking."""
+        stats = self.ctx.geodesic(frame, mask.data_ptr(), seeds.data_ptr(), metric, algo)
+        dd, dr, _, _ = self.ctx.geodesic_result()
+        return (torch.as_tensor(_DeviceView(dd, frame.voxels, "<i4", self), device=self.device),
+                torch.as_tensor(_DeviceView(dr, frame.voxels // 32, "<i4", self), device=self.device), stats)
+
     def octree(self, frame: Frame, words, algo: int = ALGO_TILED):
         """Sparse voxel octree of a grid (n <= 1024): returns (nodes, level_offset, full_leaves) -- an int32 tensor of M x 2 words, the
         records (valid | full << 8, index of the first mixed child) breadth-first and in Morton order within a level, and two lists of 11:

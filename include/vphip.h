@@ -658,6 +658,58 @@ int vp_skeleton_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, co
                      uint32_t max_iters, int algo, uint32_t* h_skel, uint64_t* h_stats /* either may be NULL, not both */);
 int vp_skeleton_table_host(vp_ctx* ctx /* NULL: computed on the CPU */, int algo, uint32_t* h_table /* 2^21 words: bit c = simple(c) */);
 
+/* ---- geodesic distance: path length inside the solid from seed voxels (no reference counterpart) ----------------
+ * Every other distance of the library (JFA, vp_edt, vp_mesh_distance) is a straight line and goes through walls.  This is the geodesic
+ * distance map that Fiji / MorphoLibJ put beside "Local Thickness" and "Skeletonize3D": the length of the shortest path that stays
+ * inside a mask, from a set of seed voxels to every voxel of the mask.
+ *   inputs      a whole-grid frame, n % 32 == 0, n <= 1024; a mask grid M and a seed grid S, both bit grids in the library's layout.
+ *               OUTSIDE THE GRID COUNTS AS NOT IN M.  The seeds used are S & M: seed bits outside M are ignored.
+ *   step        from a voxel of M to one of its 26 neighbours that is also in M.  No other voxel has to be set for a diagonal step: two
+ *               cubes of M that touch at one corner are connected for the metrics with corner steps (MorphoLibJ's rule).  A step that
+ *               changes 1, 2 or 3 coordinates costs w1, w2 or w3:
+ *                 VP_GEO_6        (1, -, -)   face steps only
+ *                 VP_GEO_26       (1, 1, 1)   all 26 steps
+ *                 VP_GEO_CHAMFER  (3, 4, 5)   all 26 steps (Borgefors; divide by 3 for voxels)
+ *   output D    one uint32 per voxel, x fastest like vp_edt: the minimum cost over all such paths from any used seed.  Seeds read 0;
+ *               voxels of M that no path reaches, and voxels outside M, read VP_GEO_NONE.  Sums saturate at VP_GEO_MAX: the add is
+ *               min(d + w, VP_GEO_MAX) in every form (monotone, so the fixed point stays unique; not reachable in practice at n <= 1024).
+ *   reach R     a bit grid, one bit set per voxel with D != VP_GEO_NONE: the components of M that touch a used seed (morphological
+ *               reconstruction; face-connected for VP_GEO_6, 26-connected for the others).
+ *   h_stats     { seeds used |S & M|, voxels reached, the largest finite D, the lowest linear index x + n (y + n z) of a voxel that
+ *               attains it }.  With no seed used D is VP_GEO_NONE everywhere, R is empty and the statistics are zeros.  Nothing that
+ *               depends on the number of rounds is reported.
+ * The distances are integers and the minimum over paths is unique: numpy, the C++ host form, VP_ALGO_NAIVE and VP_ALGO_TILED give the same
+ * bytes and statistics whatever the order of execution (the argument is in csrc/geodesic.hip and DESIGN.md section 21).
+ *   vp_geodesic         builds D and R into grow-only buffers that the CONTEXT owns (4 n^3 and n^3 / 8 bytes); vp_ctx_release frees them.
+ *                       BLOCKS: convergence is read back -- a batch of round flags at a time (NAIVE), the length of the list of active
+ *                       blocks once per round (TILED).
+ *   vp_geodesic_result  pointers to the last D and R, the statistics and the side they are for; any argument may be NULL.  Before a build
+ *                       and after a release: NULL, zeros and side 0.
+ *   vp_geodesic_host    host in, host out (mask and seeds staged through workspace slots); any two of h_dist / h_reach / h_stats may be
+ *                       NULL, not all three.
+ * A slab frame and n > 1024: VP_ERR_UNSUPPORTED.  Null ctx / f / mask / seeds, a buffer that is not 16-byte aligned, d_mask or d_seeds
+ * overlapping a buffer the context writes in this call (the last D and R among them: copy them first), an unknown metric or algo:
+ * VP_ERR_INVALID.  A refusal is decided before anything is touched and leaves the previous result as it was.
+ *   algo: VP_ALGO_NAIVE -- one lane per voxel of M pulls min(D[q] + w) over its allowed neighbours from global memory, in place;
+ *   whole-grid launches repeat until one changes nothing.  VP_ALGO_TILED -- one workgroup per active block of 32 x 16 x 16 voxels, D and a
+ *   one-voxel halo staged in LDS (45 KB), relaxed inside the block until a sweep changes nothing or a fixed number of sweeps have run,
+ *   changed values written back; a block whose face, edge or corner voxel changed raises the flags of the neighbour blocks that see the
+ *   voxel, the next list comes from the flags by count, scan, write; the first list is the blocks that hold a used seed or see one in their halo (a seed reads 0
+ *   from the start and is never "changed", so the launch that writes the initial D raises them by the same rule), the loop ends with the
+ *   first empty list; a block that is never listed sees VP_GEO_NONE only.  No atomics on D; kernel boundaries are the only synchronisation between workgroups.  Scratch of the context
+ *   (grow-only, freed by vp_ctx_release): 8 bytes per block.
+ *   Timing books under existing keys: the launch that writes the initial D under VP_K_MD_FILL, the final reach / statistics launch under
+ *   VP_K_MD_SPLIT, the block list under VP_K_MD_SCAN, the TILED relaxation rounds under VP_K_MD_BRICK, the NAIVE rounds under
+ *   VP_K_MD_NAIVE. */
+enum { VP_GEO_6 = 0, VP_GEO_26 = 1, VP_GEO_CHAMFER = 2 };
+#define VP_GEO_NONE 0xFFFFFFFFu
+#define VP_GEO_MAX 0xFFFFFFFEu
+int vp_geodesic(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_mask, const uint32_t* d_seeds, int metric, int algo,
+                uint64_t* h_stats /* 4, may be NULL: seeds used, voxels reached, largest finite D, lowest index that attains it */);
+int vp_geodesic_result(vp_ctx* ctx, uint32_t** d_dist, uint32_t** d_reach, uint64_t* h_stats /* 4 */, uint32_t* h_n);
+int vp_geodesic_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, const uint32_t* h_seeds, int metric, int algo,
+                     uint32_t* h_dist, uint32_t* h_reach, uint64_t* h_stats /* any two may be NULL, not all three */);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
