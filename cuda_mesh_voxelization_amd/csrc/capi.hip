@@ -1,6 +1,8 @@
 // capi.hip -- the extern "C" surface of libvphip.so (declared in include/vphip.h):
 // context / stream / workspace management, argument validation, per-kernel hipEvent timing and
 // the host-in/host-out conveniences that reproduce the reference's Compute() calling convention.
+// The context's state is one struct per feature (vp_internal.h): vp_ctx_destroy and vp_ctx_release walk the features, and the calls
+// that build a result the context owns share build_owned -- neither names a buffer.
 #include "vp_internal.h"
 
 #include <algorithm>
@@ -126,11 +128,11 @@ static bool overlaps(const void* a, size_t an, const void* b, size_t bn)
 static void grid_written(vp_ctx* ctx, const void* d_ptr, size_t bytes)
 {
     if (!d_ptr) return;
-    if (overlaps(d_ptr, bytes, ctx->ext_words, (size_t)ctx->ext_n * ctx->ext_n * ctx->ext_n / 8)) ctx->ext_words = nullptr;
-    const vp_ctx::JfaStarted& st = ctx->jfa_started;
+    if (overlaps(d_ptr, bytes, ctx->ext.words, (size_t)ctx->ext.n * ctx->ext.n * ctx->ext.n / 8)) ctx->ext.words = nullptr;
+    const vp_ctx::Jfa::Started& st = ctx->jfa.started;
     if (st.valid && (overlaps(d_ptr, bytes, st.words, (size_t)st.n * st.n * st.n / 8) || overlaps(d_ptr, bytes, st.work, st.work_bytes)))
-        ctx->jfa_started.valid = false;
-    if (overlaps(d_ptr, bytes, ctx->sn_words, (size_t)ctx->sn_n * ctx->sn_n * ctx->sn_n / 8)) ctx->sn_words = nullptr;
+        ctx->jfa.started.valid = false;
+    if (overlaps(d_ptr, bytes, ctx->sn.words, (size_t)ctx->sn.n * ctx->sn.n * ctx->sn.n / 8)) ctx->sn.words = nullptr;
 }
 
 static const char* kNames[VP_K_ALL] = {
@@ -156,16 +158,46 @@ using namespace vp;
 // for a slot already drops the records of the grids that lay in it.
 enum { SLOT_GRID_A = 0, SLOT_GRID_B = 1, SLOT_XYZ = 2, SLOT_TRI = 3, SLOT_SDF = 4, SLOT_NEAREST = 5 };
 
+// a host array up into a slot
+static int stage(vp_ctx* ctx, int slot, const void* h_src, size_t bytes, void** d_out)
+{
+    VP_TRY(vp_ctx_workspace(ctx, slot, bytes, d_out));
+    return vp_upload(ctx, *d_out, h_src, bytes);
+}
+
 template <typename Call>
 static int host_round_trip(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, void* h_out, int out_slot, Call call)
 {
     void *din = nullptr, *dout = nullptr;
     const size_t wb = vp_grid_words(f) * 4, ob = out_slot == SLOT_SDF ? vp_grid_voxels(f) * 4 : wb;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &din));
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_words, wb, &din));
     VP_TRY(vp_ctx_workspace(ctx, out_slot, ob, &dout));
-    VP_TRY(vp_upload(ctx, din, h_words, wb));
     VP_TRY(call((const uint32_t*)din, dout));
     return vp_download(ctx, h_out, dout, ob);
+}
+
+// One path for the calls that build a result the context owns (vp_isonets, vp_winding, vp_thickness, vp_octree, vp_octree_expand,
+// vp_skeleton, vp_geodesic): `ft` is the feature that is built, `also` what the call writes besides that feature's buffers, launch() the
+// work.  The inputs are read while every one of those buffers is written: an input that lies in one is refused (the last result has to be
+// copied before it goes back in); `inputs` is empty for the calls that have never refused it.  The context's own buffers are outputs
+// like any other: whatever was recorded about their bytes is gone -- about the bytes they hold now (a buffer that has to grow is freed
+// first: a record left standing on it would be served on freed memory) and, after the launch, about the bytes they hold then.
+template <typename Ft, typename Launch>
+static int build_owned(vp_ctx* ctx, const char* who, Ft& ft, std::initializer_list<Buffer*> also,
+                       std::initializer_list<std::pair<const void*, size_t>> inputs, Launch launch)
+{
+    auto all = [&](auto f) { ft.released(f); ft.kept(f); for (Buffer* b : also) f(*b); };
+    int rc = 0;
+    all([&](Buffer& b) {
+        for (const auto& in : inputs)
+            if (!rc && overlaps(in.first, in.second, b.ptr, b.bytes)) rc = set_error(VP_ERR_INVALID, "%s: a buffer of the context overlaps d_words", who);
+    });
+    VP_TRY(rc);
+    auto written = [&](Buffer& b) { grid_written(ctx, b.ptr, b.bytes); };
+    all(written);
+    rc = launch();
+    all(written);
+    return rc;
 }
 
 extern "C" {
@@ -207,33 +239,11 @@ int vp_ctx_destroy(vp_ctx* ctx)
     if (!ctx) return 0;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    Buffer* bufs[] = { &ctx->rec, &ctx->tile_cnt, &ctx->tile_off, &ctx->tile_cur, &ctx->pairs, &ctx->scratch, &ctx->none_row, &ctx->jfa_work,
-                       &ctx->ext_cnt, &ctx->ext_off, &ctx->cvox_cnt, &ctx->cvox_rec, &ctx->cvox_base, &ctx->fill_flags, &ctx->morph_tab, &ctx->morph_tmp,
-                       &ctx->comp_cnt, &ctx->comp_off, &ctx->comp_labels, &ctx->comp_sizes, &ctx->comp_keep, &ctx->comp_small,
-                       &ctx->sn_cnt, &ctx->sn_off, &ctx->sn_rank, &ctx->sn_xyz, &ctx->edt_mask, &ctx->edt_vol, &ctx->edt_vol2, &ctx->edt_tmp,
-                       &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list,
-                       &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads,
-                       &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree,
-                       &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum,
-                       &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt, &ctx->oc_grid,
-                       &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux,
-                       &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux };
-    for (Buffer* b : bufs) release(*b);
-    for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
+    ctx->each_feature([](auto& ft) { ft.released(release); ft.kept(release); });
     for (auto& s : ctx->prof_pending) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : ctx->prof_pool) (void)hipEventDestroy(e);
-    if (ctx->vox_total_event) (void)hipEventDestroy(ctx->vox_total_event);
-    if (ctx->vox_total_host) (void)hipHostFree(ctx->vox_total_host);
-    if (ctx->cvox_event) (void)hipEventDestroy(ctx->cvox_event);
-    if (ctx->cvox_host) (void)hipHostFree(ctx->cvox_host);
-    if (ctx->fill_host) (void)hipHostFree(ctx->fill_host);
-    if (ctx->comp_host) (void)hipHostFree(ctx->comp_host);
-    if (ctx->md_host) (void)hipHostFree(ctx->md_host);
-    if (ctx->wn_host) (void)hipHostFree(ctx->wn_host);
-    if (ctx->th_host) (void)hipHostFree(ctx->th_host);
-    if (ctx->oc_host) (void)hipHostFree(ctx->oc_host);
-    if (ctx->sk_host) (void)hipHostFree(ctx->sk_host);
-    if (ctx->gd_host) (void)hipHostFree(ctx->gd_host);
+    if (ctx->vox.total_event) (void)hipEventDestroy(ctx->vox.total_event);
+    if (ctx->cvox.event) (void)hipEventDestroy(ctx->cvox.event);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return 0;
@@ -290,9 +300,9 @@ int vp_ctx_workspace(vp_ctx* ctx, int slot, size_t bytes, void** d_out)
 {
     if (!ctx || !d_out || slot < 0 || slot >= VP_WORKSPACE_SLOTS) return set_error(VP_ERR_INVALID, "vp_ctx_workspace: bad argument");
     VP_TRY(bind_device(ctx));
-    VP_TRY(reserve(ctx, ctx->slots[slot], bytes ? bytes : 1));
-    *d_out = ctx->slots[slot].ptr;
-    grid_written(ctx, *d_out, ctx->slots[slot].bytes);             // whoever asks for the slot is about to fill it
+    VP_TRY(reserve(ctx, ctx->ws.slots[slot], bytes ? bytes : 1));
+    *d_out = ctx->ws.slots[slot].ptr;
+    grid_written(ctx, *d_out, ctx->ws.slots[slot].bytes);             // whoever asks for the slot is about to fill it
     return 0;
 }
 
@@ -301,34 +311,8 @@ int vp_ctx_release(vp_ctx* ctx)
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_ctx_release: null ctx");
     VP_TRY(bind_device(ctx));
     VP_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < VP_WORKSPACE_SLOTS; ++i) release(ctx->slots[i]);
-    release(ctx->jfa_work);
-    release(ctx->comp_labels);                                     // vp_components_filter's label volume, 4 n^3 bytes
-    release(ctx->sn_rank);                                         // vp_surfnets' rank lookup and second position buffer
-    release(ctx->sn_xyz);
-    release(ctx->edt_mask);                                        // vp_edt*'s border mask, distance volumes and intermediate grid
-    release(ctx->edt_vol);
-    release(ctx->edt_vol2);
-    release(ctx->edt_tmp);
-    for (Buffer* b : { &ctx->md_keys, &ctx->md_rec, &ctx->md_base, &ctx->md_cnt, &ctx->md_off, &ctx->md_list }) release(*b);   // vp_mesh_distance
-    for (Buffer* b : { &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads }) release(*b);      // vp_isonets: scratch and result
-    ctx->iso_vertices = ctx->iso_quad_count = 0;
-    ctx->iso_has_normals = false;
-    for (Buffer* b : { &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree }) release(*b);                                // vp_winding: scratch and result
-    ctx->wn_n = 0;
-    for (Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum }) release(*b);                   // vp_thickness: scratch and result
-    ctx->th_n = 0;
-    for (Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt }) release(*b);                   // vp_octree: scratch and result
-    release(ctx->oc_grid);                                         // vp_octree_expand: result
-    ctx->oc_n = ctx->oc_grid_n = 0;
-    ctx->oc_count = 0;
-    for (Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) release(*b);                                  // vp_skeleton: scratch and result
-    ctx->sk_n = 0;
-    for (Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) release(*b);                                                 // vp_geodesic: result and scratch
-    ctx->gd_n = 0;
-    ctx->jfa_started.valid = false;
-    ctx->ext_words = nullptr;
-    ctx->sn_words = nullptr;
+    // every feature gives up the buffers it marks as released (vp_internal.h) and the result or record that lay in them
+    ctx->each_feature([](auto& ft) { ft.released(release); ft.forget(); });
     return 0;
 }
 
@@ -387,6 +371,21 @@ static int check_algo(const char* who, int algo)
 {
     if (algo != VP_ALGO_NAIVE && algo != VP_ALGO_TILED) return set_error(VP_ERR_INVALID, "%s: unknown algo %d", who, algo);
     return 0;
+}
+
+// What every call that serves whole grids up to n = 1024 checks first, in this order: the frame, the whole grid, the side -- `why` is what
+// the refusal says in parentheses -- and, where the algo comes next, the algo.
+static int check_grid_1024(const vp_frame* f, const char* who, const char* why = "32 <= n <= 1024")
+{
+    VP_TRY(check_frame(f, who, false));
+    VP_TRY(check_whole(f, who));
+    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (%s)", who, f->n, why);
+    return 0;
+}
+static int check_grid_1024(const vp_frame* f, const char* who, int algo, const char* why = "32 <= n <= 1024")
+{
+    VP_TRY(check_grid_1024(f, who, why));
+    return check_algo(who, algo);
 }
 
 static int check_morph_op(const char* who, int op)
@@ -466,11 +465,7 @@ static int check_fill(float fill, const char* who);
 // what vp_edt, vp_edt_sdf and vp_edt_morph share: whole grids up to n = 1024, the algo
 static int check_edt(const vp_frame* f, const char* who, int algo)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: the distance volume would be 32 GiB)", who, f->n);
-    VP_TRY(check_algo(who, algo));
-    return 0;
+    return check_grid_1024(f, who, algo, "32 <= n <= 1024: the distance volume would be 32 GiB");
 }
 
 static int check_edt_seeds(const char* who, int seeds)
@@ -532,10 +527,7 @@ int vp_edt_morph(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32
 // what vp_mesh_distance and its host form share: whole grids up to n = 1024, the algo, the band
 static int check_mesh_distance(const vp_frame* f, const char* who, uint32_t band, int algo)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
-    VP_TRY(check_algo(who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     if (band < 1 || band > 32) return set_error(VP_ERR_INVALID, "%s: band %u (1 .. 32 voxels)", who, band);
     return 0;
 }
@@ -564,16 +556,14 @@ int vp_mesh_distance(vp_ctx* ctx, const vp_frame* f, const float* d_xyz, size_t 
 int vp_mesh_distance_stats(vp_ctx* ctx, uint64_t* list_entries)
 {
     if (!ctx || !list_entries) return set_error(VP_ERR_INVALID, "vp_mesh_distance_stats: null argument");
-    *list_entries = ctx->md_last_total;
+    *list_entries = ctx->md.last_total;
     return 0;
 }
 
 // what the three vp_components_* entry points share: whole grids up to n = 1024, connectivity and algo
 static int check_components(const vp_frame* f, const char* who, int connectivity, int algo)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: voxel indices are 32-bit)", who, f->n);
+    VP_TRY(check_grid_1024(f, who, "32 <= n <= 1024: voxel indices are 32-bit"));
     if (connectivity != VP_CONN_6 && connectivity != VP_CONN_26) return set_error(VP_ERR_INVALID, "%s: unknown connectivity %d (6 or 26)", who, connectivity);
     VP_TRY(check_algo(who, algo));
     return 0;
@@ -720,11 +710,11 @@ static int jfa_check(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, vo
     VP_TRY(check_aligned(who, {d_words, d_work}));
     VP_TRY(check_algo(who, algo));
     if (!d_work) {                                                 // context-owned workspace (grow-only, reused by later calls)
-        const void* before = ctx->jfa_work.ptr;
-        VP_TRY(reserve(ctx, ctx->jfa_work, vp_jfa_workspace_bytes(f)));
-        if (ctx->jfa_work.ptr != before) ctx->jfa_started.valid = false;   // regrown: what a vp_jfa_start left there is gone
-        d_work = ctx->jfa_work.ptr;
-        work_bytes = ctx->jfa_work.bytes;
+        const void* before = ctx->jfa.work.ptr;
+        VP_TRY(reserve(ctx, ctx->jfa.work, vp_jfa_workspace_bytes(f)));
+        if (ctx->jfa.work.ptr != before) ctx->jfa.started.valid = false;   // regrown: what a vp_jfa_start left there is gone
+        d_work = ctx->jfa.work.ptr;
+        work_bytes = ctx->jfa.work.bytes;
     } else if (work_bytes < vp_jfa_workspace_bytes(f)) {
         return set_error(VP_ERR_INVALID, "%s: workspace too small", who);
     }
@@ -743,11 +733,11 @@ int vp_jfa_start(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, void* 
     const size_t volBytes = vp_grid_voxels(f) * vp_jfa_id_bytes(f);
     char* a = (char*)d_work;
     const bool mask = jfa_tile_sequence(fr, algo);
-    ctx->jfa_started.valid = false;
+    ctx->jfa.started.valid = false;
     if (explicitWork) grid_written(ctx, d_work, vp_jfa_workspace_bytes(f));     // the workspace may be a grid somebody counted
     if (mask) VP_TRY(launch_jfa_init(ctx, fr, d_words, nullptr, nullptr, nullptr, (uint32_t*)(a + 2 * volBytes)));   // border mask only
     else      VP_TRY(launch_jfa_init(ctx, fr, d_words, nullptr, nullptr, a, nullptr));
-    ctx->jfa_started = {true, mask, f->n, algo, d_work, work_bytes, d_words};
+    ctx->jfa.started = {true, mask, f->n, algo, d_work, work_bytes, d_words};
     return 0;
 }
 
@@ -767,8 +757,8 @@ int vp_jfa_run(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, float fi
     // The workspace must hold what THIS sequence starts from: the record of the matching vp_jfa_start (same grid, frame size,
     // algo and workspace).  One start serves one run: the passes overwrite the volumes.
     const bool wantMask = jfa_tile_sequence(fr, algo);
-    const vp_ctx::JfaStarted st = ctx->jfa_started;
-    ctx->jfa_started.valid = false;
+    const vp_ctx::Jfa::Started st = ctx->jfa.started;
+    ctx->jfa.started.valid = false;
     if (!st.valid || st.n != f->n || st.algo != algo || st.work != d_work || st.words != d_words || st.mask != wantMask)
         return set_error(VP_ERR_INVALID, "vp_jfa_run: call vp_jfa_start with the same grid, frame, algo and workspace first");
     if (explicitWork) grid_written(ctx, d_work, vp_jfa_workspace_bytes(f));     // the passes overwrite the volumes (the caller's: the context's own is nobody's grid)
@@ -1076,7 +1066,7 @@ int vp_extract(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int mode
     // the records and values are outputs like any other: at most min(capacity, the standing count) of them are written.  Reported whether or
     // not that count is of this grid -- launch_extract_write alone decides that, and refuses below where it is not; an output that lies on
     // the grid itself drops the count here and is refused too
-    const size_t cnt = (size_t)std::min<uint64_t>(capacity, ctx->ext_total);
+    const size_t cnt = (size_t)std::min<uint64_t>(capacity, ctx->ext.total);
     if (cnt) {
         grid_written(ctx, d_records, cnt * 8);
         grid_written(ctx, d_values, cnt * 4);
@@ -1088,10 +1078,7 @@ int vp_extract(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int mode
 // what the three vp_surfnets* entry points share: whole grids up to n = 1024
 static int check_surfnets(const vp_frame* f, const char* who)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024: cell indices are 32-bit)", who, f->n);
-    return 0;
+    return check_grid_1024(f, who, "32 <= n <= 1024: cell indices are 32-bit");
 }
 
 int vp_surfnets_count(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint64_t* h_vertices, uint64_t* h_quads)
@@ -1114,13 +1101,13 @@ int vp_surfnets(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int alg
     VP_TRY(check_surfnets(f, who));
     VP_TRY(check_algo(who, algo));
     if (iterations > 64) return set_error(VP_ERR_INVALID, "%s: %u iterations (0 .. 64)", who, iterations);
-    if (ctx->sn_words != d_words || ctx->sn_algo != algo || ctx->sn_n != f->n)
+    if (ctx->sn.words != d_words || ctx->sn.algo != algo || ctx->sn.n != f->n)
         return set_error(VP_ERR_INVALID, "%s: call vp_surfnets_count with the same grid and algo first", who);
-    if (vertex_capacity < ctx->sn_vertices || quad_capacity < ctx->sn_quads)
+    if (vertex_capacity < ctx->sn.vertices || quad_capacity < ctx->sn.quads)
         return set_error(VP_ERR_INVALID, "%s: capacity %zu vertices / %zu quads, the grid has %llu / %llu", who, vertex_capacity, quad_capacity,
-                         (unsigned long long)ctx->sn_vertices, (unsigned long long)ctx->sn_quads);
-    if ((ctx->sn_vertices && (!d_cells || !d_xyz)) || (ctx->sn_quads && !d_quads)) return set_error(VP_ERR_INVALID, "%s: null output", who);
-    const size_t gb = vp_grid_words(f) * 4, cb = (size_t)ctx->sn_vertices * 8, xb = (size_t)ctx->sn_vertices * 12, qb = (size_t)ctx->sn_quads * 16;
+                         (unsigned long long)ctx->sn.vertices, (unsigned long long)ctx->sn.quads);
+    if ((ctx->sn.vertices && (!d_cells || !d_xyz)) || (ctx->sn.quads && !d_quads)) return set_error(VP_ERR_INVALID, "%s: null output", who);
+    const size_t gb = vp_grid_words(f) * 4, cb = (size_t)ctx->sn.vertices * 8, xb = (size_t)ctx->sn.vertices * 12, qb = (size_t)ctx->sn.quads * 16;
     if (overlaps(d_words, gb, d_cells, cb) || overlaps(d_words, gb, d_xyz, xb) || overlaps(d_words, gb, d_quads, qb))
         return set_error(VP_ERR_INVALID, "%s: an output overlaps d_words", who);
     grid_written(ctx, d_cells, cb); grid_written(ctx, d_xyz, xb); grid_written(ctx, d_quads, qb);     // writes like any other (not to this grid)
@@ -1146,26 +1133,21 @@ int vp_isonets(vp_ctx* ctx, const vp_frame* f, const float* d_field, int transfo
     VP_TRY(bind_device(ctx));
     VP_TRY(check_isonets(f, who, transform, iso, iterations, algo));
     VP_TRY(check_aligned(who, {d_field}));
-    const int rc = launch_isonets(ctx, f->n, d_field, transform, iso, iterations, want_normals != 0, algo);
-    // the context's own buffers are outputs like any other: whatever was recorded about their bytes is gone
-    for (Buffer* b : { &ctx->iso_words, &ctx->iso_cells, &ctx->iso_xyz, &ctx->iso_normals, &ctx->iso_quads }) grid_written(ctx, b->ptr, b->bytes);
-    VP_TRY(rc);
-    if (h_vertices) *h_vertices = ctx->iso_vertices;
-    if (h_quads) *h_quads = ctx->iso_quad_count;
-    return 0;
+    VP_TRY(build_owned(ctx, who, ctx->iso, {}, {}, [&] { return launch_isonets(ctx, f->n, d_field, transform, iso, iterations, want_normals != 0, algo); }));
+    return vp_isonets_result(ctx, nullptr, nullptr, nullptr, nullptr, h_vertices, h_quads);
 }
 
 int vp_isonets_result(vp_ctx* ctx, uint64_t** d_cells, float** d_xyz, float** d_normals, uint32_t** d_quads, uint64_t* h_vertices,
                       uint64_t* h_quads)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_isonets_result: null ctx");
-    const bool any = ctx->iso_vertices != 0;                       // no vertex, hence no quad
-    if (d_cells) *d_cells = any ? (uint64_t*)ctx->iso_cells.ptr : nullptr;
-    if (d_xyz) *d_xyz = any ? (float*)ctx->iso_xyz.ptr : nullptr;
-    if (d_normals) *d_normals = any && ctx->iso_has_normals ? (float*)ctx->iso_normals.ptr : nullptr;
-    if (d_quads) *d_quads = any ? (uint32_t*)ctx->iso_quads.ptr : nullptr;
-    if (h_vertices) *h_vertices = ctx->iso_vertices;
-    if (h_quads) *h_quads = ctx->iso_quad_count;
+    const bool any = ctx->iso.vertices != 0;                       // no vertex, hence no quad
+    if (d_cells) *d_cells = any ? (uint64_t*)ctx->iso.cells.ptr : nullptr;
+    if (d_xyz) *d_xyz = any ? (float*)ctx->iso.xyz.ptr : nullptr;
+    if (d_normals) *d_normals = any && ctx->iso.has_normals ? (float*)ctx->iso.normals.ptr : nullptr;
+    if (d_quads) *d_quads = any ? (uint32_t*)ctx->iso.quads.ptr : nullptr;
+    if (h_vertices) *h_vertices = ctx->iso.vertices;
+    if (h_quads) *h_quads = ctx->iso.quad_count;
     return 0;
 }
 
@@ -1173,10 +1155,7 @@ int vp_isonets_result(vp_ctx* ctx, uint64_t** d_cells, float** d_xyz, float** d_
 // what vp_winding and its host form share: whole grids up to n = 1024, the algo, beta in {0} U [1, 64], a finite level
 static int check_winding(const vp_frame* f, const char* who, float beta, float level, int algo)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
-    VP_TRY(check_algo(who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     if (!(beta == 0.0f || (beta >= 1.0f && beta <= 64.0f))) return set_error(VP_ERR_INVALID, "%s: beta %g (0, or 1 .. 64)", who, (double)beta);
     if (!std::isfinite(level)) return set_error(VP_ERR_INVALID, "%s: level must be finite", who);
     return 0;
@@ -1192,19 +1171,17 @@ int vp_winding(vp_ctx* ctx, const vp_frame* f, const float* d_xyz, size_t nverts
     if (ntris && (!d_xyz || !d_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
     if (ntris > 0xFFFFFFFFull / 3) return set_error(VP_ERR_UNSUPPORTED, "%s: too many triangles", who);
     VP_TRY(check_aligned(who, {d_xyz, d_tri}));
-    const int rc = launch_winding(ctx, make_frame(f), d_xyz, nverts, d_tri, ntris, beta, level, algo, h_inside_count);
-    // the context's own buffers are outputs like any other: whatever was recorded about their bytes is gone
-    for (Buffer* b : { &ctx->wn_w, &ctx->wn_inside, &ctx->wn_rec, &ctx->wn_tree }) grid_written(ctx, b->ptr, b->bytes);
-    return rc;
+    return build_owned(ctx, who, ctx->wn, {}, {},
+                       [&] { return launch_winding(ctx, make_frame(f), d_xyz, nverts, d_tri, ntris, beta, level, algo, h_inside_count); });
 }
 
 int vp_winding_result(vp_ctx* ctx, float** d_w, uint32_t** d_inside, uint32_t* h_n)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_winding_result: null ctx");
-    const bool any = ctx->wn_n != 0;
-    if (d_w) *d_w = any ? (float*)ctx->wn_w.ptr : nullptr;
-    if (d_inside) *d_inside = any ? (uint32_t*)ctx->wn_inside.ptr : nullptr;
-    if (h_n) *h_n = ctx->wn_n;
+    const bool any = ctx->wn.n != 0;
+    if (d_w) *d_w = any ? (float*)ctx->wn.w.ptr : nullptr;
+    if (d_inside) *d_inside = any ? (uint32_t*)ctx->wn.inside.ptr : nullptr;
+    if (h_n) *h_n = ctx->wn.n;
     return 0;
 }
 
@@ -1212,10 +1189,7 @@ int vp_winding_result(vp_ctx* ctx, float** d_w, uint32_t** d_inside, uint32_t* h
 // what vp_thickness and its host form share: whole grids up to n = 1024, the algo, rmax in 1 .. 32, thin2 in 0 .. rmax^2
 static int check_thickness(const vp_frame* f, const char* who, uint32_t rmax, uint32_t thin2, int algo)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
-    VP_TRY(check_algo(who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     if (rmax < 1 || rmax > 32) return set_error(VP_ERR_INVALID, "%s: rmax %u (1 .. 32)", who, rmax);
     if (thin2 > rmax * rmax) return set_error(VP_ERR_INVALID, "%s: thin2 %u (0 .. rmax^2 = %u)", who, thin2, rmax * rmax);
     return 0;
@@ -1228,67 +1202,43 @@ int vp_thickness(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, uint32
     VP_TRY(bind_device(ctx));
     VP_TRY(check_thickness(f, who, rmax, thin2, algo));
     VP_TRY(check_aligned(who, {d_words}));
-    // the grid is read while every buffer of the call is written: it may lie in none of them (the last thin grid has to be copied first)
-    for (const Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum, &ctx->edt_vol, &ctx->edt_vol2 })
-        VP_TRY(check_disjoint(who, "a buffer of the context", d_words, vp_grid_words(f) * 4, b->ptr, b->bytes));
-    // the context's own buffers are outputs like any other: whatever was recorded about their bytes is gone -- about the bytes they
-    // hold now (a buffer that has to grow is freed first) and, after the launch, about the bytes they hold then
-    for (Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum, &ctx->edt_vol, &ctx->edt_vol2 })
-        grid_written(ctx, b->ptr, b->bytes);
-    const int rc = launch_thickness(ctx, make_frame(f), d_words, rmax, thin2, algo, h_thin_count);
-    for (Buffer* b : { &ctx->th_t2, &ctx->th_thin, &ctx->th_d16, &ctx->th_sat, &ctx->th_sum, &ctx->edt_vol, &ctx->edt_vol2 })
-        grid_written(ctx, b->ptr, b->bytes);
-    return rc;
+    // the distance volumes of the transform are written too
+    return build_owned(ctx, who, ctx->th, {&ctx->edt.vol, &ctx->edt.vol2}, {{d_words, vp_grid_words(f) * 4}},
+                       [&] { return launch_thickness(ctx, make_frame(f), d_words, rmax, thin2, algo, h_thin_count); });
 }
 
 int vp_thickness_result(vp_ctx* ctx, uint32_t** d_t2, uint32_t** d_thin, uint32_t* h_n)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_thickness_result: null ctx");
-    const bool any = ctx->th_n != 0;
-    if (d_t2) *d_t2 = any ? (uint32_t*)ctx->th_t2.ptr : nullptr;
-    if (d_thin) *d_thin = any ? (uint32_t*)ctx->th_thin.ptr : nullptr;
-    if (h_n) *h_n = ctx->th_n;
+    const bool any = ctx->th.n != 0;
+    if (d_t2) *d_t2 = any ? (uint32_t*)ctx->th.t2.ptr : nullptr;
+    if (d_thin) *d_thin = any ? (uint32_t*)ctx->th.thin.ptr : nullptr;
+    if (h_n) *h_n = ctx->th.n;
     return 0;
 }
 
 // ---- sparse voxel octree ---------------------------------------------------------------------------
-// what the octree calls share: whole grids up to n = 1024 and the algo
-static int check_octree(const vp_frame* f, const char* who, int algo)
-{
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
-    return check_algo(who, algo);
-}
-
 int vp_octree(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, int algo, uint64_t* h_nodes)
 {
     const char* who = "vp_octree";
     if (!ctx || !f || !d_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(bind_device(ctx));
-    VP_TRY(check_octree(f, who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     VP_TRY(check_aligned(who, {d_words}));
-    // the grid is read while every buffer of the call is written: it may lie in none of them (the context's own nodes among them)
-    for (const Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt })
-        VP_TRY(check_disjoint(who, "a buffer of the context", d_words, vp_grid_words(f) * 4, b->ptr, b->bytes));
-    // the context's own buffers are outputs like any other: what was recorded about their bytes is gone, before and after they grow
-    for (Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt }) grid_written(ctx, b->ptr, b->bytes);
-    const int rc = launch_octree(ctx, make_frame(f), d_words, algo, h_nodes);
-    for (Buffer* b : { &ctx->oc_nodes, &ctx->oc_sum, &ctx->oc_state, &ctx->oc_rank, &ctx->oc_cnt }) grid_written(ctx, b->ptr, b->bytes);
-    return rc;
+    return build_owned(ctx, who, ctx->oc, {}, {{d_words, vp_grid_words(f) * 4}}, [&] { return launch_octree(ctx, make_frame(f), d_words, algo, h_nodes); });
 }
 
 int vp_octree_result(vp_ctx* ctx, uint32_t** d_nodes, uint64_t* h_nodes, uint32_t* h_level_offset, uint32_t* h_full_leaves, uint32_t* h_n)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_octree_result: null ctx");
-    const bool any = ctx->oc_n != 0;
-    if (d_nodes) *d_nodes = any ? (uint32_t*)ctx->oc_nodes.ptr : nullptr;
-    if (h_nodes) *h_nodes = any ? ctx->oc_count : 0;
+    const bool any = ctx->oc.n != 0;
+    if (d_nodes) *d_nodes = any ? (uint32_t*)ctx->oc.nodes.ptr : nullptr;
+    if (h_nodes) *h_nodes = any ? ctx->oc.count : 0;
     for (int l = 0; l < 11; ++l) {
-        if (h_level_offset) h_level_offset[l] = any ? ctx->oc_level_offset[l] : 0u;
-        if (h_full_leaves) h_full_leaves[l] = any ? ctx->oc_full_leaves[l] : 0u;
+        if (h_level_offset) h_level_offset[l] = any ? ctx->oc.level_offset[l] : 0u;
+        if (h_full_leaves) h_full_leaves[l] = any ? ctx->oc.full_leaves[l] : 0u;
     }
-    if (h_n) *h_n = ctx->oc_n;
+    if (h_n) *h_n = ctx->oc.n;
     return 0;
 }
 
@@ -1297,26 +1247,26 @@ int vp_octree_expand(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_nodes, ui
     const char* who = "vp_octree_expand";
     if (!ctx || !f || !d_nodes) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(bind_device(ctx));
-    VP_TRY(check_octree(f, who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     if (nodes < 1 || nodes >= (1ull << 28)) return set_error(VP_ERR_INVALID, "%s: %llu nodes (1 .. 2^28 - 1)", who, (unsigned long long)nodes);
     VP_TRY(check_aligned(who, {d_nodes}));
-    // the nodes are read while the context's grid is written: they may not lie in it
-    if (overlaps(d_nodes, nodes * 8, ctx->oc_grid.ptr, ctx->oc_grid.bytes)) return set_error(VP_ERR_INVALID, "%s: d_nodes overlaps the context's grid", who);
-    // the context's own grid is an output like any other: what was recorded about its bytes is gone, before and after it grows
-    grid_written(ctx, ctx->oc_grid.ptr, ctx->oc_grid.bytes);
-    ctx->oc_grid_n = 0;
-    VP_TRY(reserve(ctx, ctx->oc_grid, vp_grid_words(f) * 4, false));
-    grid_written(ctx, ctx->oc_grid.ptr, ctx->oc_grid.bytes);
-    VP_TRY(launch_octree_expand(ctx, make_frame(f), d_nodes, nodes, (uint32_t*)ctx->oc_grid.ptr, algo));
-    ctx->oc_grid_n = f->n;
-    return 0;
+    vp_ctx::OcExpand& ox = ctx->ocx;
+    // the nodes are read while the context's grid is written: they may not lie in it (refused in this call's own words)
+    if (overlaps(d_nodes, nodes * 8, ox.grid.ptr, ox.grid.bytes)) return set_error(VP_ERR_INVALID, "%s: d_nodes overlaps the context's grid", who);
+    return build_owned(ctx, who, ox, {}, {}, [&]() -> int {
+        ox.n = 0;                                                  // from here on the previous result is gone
+        VP_TRY(reserve(ctx, ox.grid, vp_grid_words(f) * 4, false));
+        VP_TRY(launch_octree_expand(ctx, make_frame(f), d_nodes, nodes, (uint32_t*)ox.grid.ptr, algo));
+        ox.n = f->n;
+        return 0;
+    });
 }
 
 int vp_octree_expand_result(vp_ctx* ctx, uint32_t** d_words, uint32_t* h_n)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_octree_expand_result: null ctx");
-    if (d_words) *d_words = ctx->oc_grid_n ? (uint32_t*)ctx->oc_grid.ptr : nullptr;
-    if (h_n) *h_n = ctx->oc_grid_n;
+    if (d_words) *d_words = ctx->ocx.n ? (uint32_t*)ctx->ocx.grid.ptr : nullptr;
+    if (h_n) *h_n = ctx->ocx.n;
     return 0;
 }
 
@@ -1326,10 +1276,7 @@ int vp_octree_validate_host(const uint32_t* h_nodes, uint64_t nodes, uint32_t n)
 // what vp_skeleton and its host form share: whole grids up to n = 1024, the mode and the algo
 static int check_skeleton(const vp_frame* f, const char* who, int mode, int algo)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
-    VP_TRY(check_algo(who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     if (mode != VP_SKEL_KERNEL && mode != VP_SKEL_CURVE) return set_error(VP_ERR_INVALID, "%s: unknown mode %d", who, mode);
     return 0;
 }
@@ -1342,27 +1289,19 @@ int vp_skeleton(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_words, const u
     VP_TRY(bind_device(ctx));
     VP_TRY(check_skeleton(f, who, mode, algo));
     VP_TRY(check_aligned(who, {d_words, d_anchor}));
-    // the grid and the anchor are read while every buffer of the call is written: they may lie in none of them (the last skeleton has to
-    // be copied before it is thinned further or used as an anchor)
-    for (const Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) {
-        VP_TRY(check_disjoint(who, "a buffer of the context", d_words, vp_grid_words(f) * 4, b->ptr, b->bytes));
-        if (d_anchor) VP_TRY(check_disjoint(who, "a buffer of the context", d_anchor, vp_grid_words(f) * 4, b->ptr, b->bytes));
-    }
-    // the context's own buffers are outputs like any other: what was recorded about their bytes is gone, before and after they grow
-    for (Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) grid_written(ctx, b->ptr, b->bytes);
-    const int rc = launch_skeleton(ctx, make_frame(f), d_words, d_anchor, mode, max_iters, algo, h_stats);
-    for (Buffer* b : { &ctx->sk_grid, &ctx->sk_tmp, &ctx->sk_border, &ctx->sk_aux }) grid_written(ctx, b->ptr, b->bytes);
-    return rc;
+    const size_t wb = vp_grid_words(f) * 4;                        // (a null anchor overlaps nothing)
+    return build_owned(ctx, who, ctx->sk, {}, {{d_words, wb}, {d_anchor, wb}},
+                       [&] { return launch_skeleton(ctx, make_frame(f), d_words, d_anchor, mode, max_iters, algo, h_stats); });
 }
 
 int vp_skeleton_result(vp_ctx* ctx, uint32_t** d_skel, uint64_t* h_stats, uint32_t* h_n)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_skeleton_result: null ctx");
-    const bool any = ctx->sk_n != 0;
-    if (d_skel) *d_skel = any ? (uint32_t*)ctx->sk_grid.ptr : nullptr;
+    const bool any = ctx->sk.n != 0;
+    if (d_skel) *d_skel = any ? (uint32_t*)ctx->sk.grid.ptr : nullptr;
     if (h_stats)
-        for (int i = 0; i < 3; ++i) h_stats[i] = any ? ctx->sk_stats[i] : 0;
-    if (h_n) *h_n = ctx->sk_n;
+        for (int i = 0; i < 3; ++i) h_stats[i] = any ? ctx->sk.stats[i] : 0;
+    if (h_n) *h_n = ctx->sk.n;
     return 0;
 }
 
@@ -1370,10 +1309,7 @@ int vp_skeleton_result(vp_ctx* ctx, uint32_t** d_skel, uint64_t* h_stats, uint32
 // what vp_geodesic and its host form share: whole grids up to n = 1024, the metric and the algo
 static int check_geodesic(const vp_frame* f, const char* who, int metric, int algo)
 {
-    VP_TRY(check_frame(f, who, false));
-    VP_TRY(check_whole(f, who));
-    if (f->n > 1024) return set_error(VP_ERR_UNSUPPORTED, "%s: n=%u is not served (32 <= n <= 1024)", who, f->n);
-    VP_TRY(check_algo(who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     if (metric != VP_GEO_6 && metric != VP_GEO_26 && metric != VP_GEO_CHAMFER) return set_error(VP_ERR_INVALID, "%s: unknown metric %d", who, metric);
     return 0;
 }
@@ -1385,28 +1321,20 @@ int vp_geodesic(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_mask, const ui
     VP_TRY(bind_device(ctx));
     VP_TRY(check_geodesic(f, who, metric, algo));
     VP_TRY(check_aligned(who, {d_mask, d_seeds}));
-    // the mask and the seeds are read while every buffer of the call is written: they may lie in none of them (the last reach grid has to
-    // be copied before it goes back in as a mask or as seeds)
-    for (const Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) {
-        VP_TRY(check_disjoint(who, "a buffer of the context", d_mask, vp_grid_words(f) * 4, b->ptr, b->bytes));
-        VP_TRY(check_disjoint(who, "a buffer of the context", d_seeds, vp_grid_words(f) * 4, b->ptr, b->bytes));
-    }
-    // the context's own buffers are outputs like any other: what was recorded about their bytes is gone, before and after they grow
-    for (Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) grid_written(ctx, b->ptr, b->bytes);
-    const int rc = launch_geodesic(ctx, make_frame(f), d_mask, d_seeds, metric, algo, h_stats);
-    for (Buffer* b : { &ctx->gd_dist, &ctx->gd_reach, &ctx->gd_aux }) grid_written(ctx, b->ptr, b->bytes);
-    return rc;
+    const size_t wb = vp_grid_words(f) * 4;
+    return build_owned(ctx, who, ctx->gd, {}, {{d_mask, wb}, {d_seeds, wb}},
+                       [&] { return launch_geodesic(ctx, make_frame(f), d_mask, d_seeds, metric, algo, h_stats); });
 }
 
 int vp_geodesic_result(vp_ctx* ctx, uint32_t** d_dist, uint32_t** d_reach, uint64_t* h_stats, uint32_t* h_n)
 {
     if (!ctx) return set_error(VP_ERR_INVALID, "vp_geodesic_result: null ctx");
-    const bool any = ctx->gd_n != 0;
-    if (d_dist) *d_dist = any ? (uint32_t*)ctx->gd_dist.ptr : nullptr;
-    if (d_reach) *d_reach = any ? (uint32_t*)ctx->gd_reach.ptr : nullptr;
+    const bool any = ctx->gd.n != 0;
+    if (d_dist) *d_dist = any ? (uint32_t*)ctx->gd.dist.ptr : nullptr;
+    if (d_reach) *d_reach = any ? (uint32_t*)ctx->gd.reach.ptr : nullptr;
     if (h_stats)
-        for (int i = 0; i < 4; ++i) h_stats[i] = any ? ctx->gd_stats[i] : 0;
-    if (h_n) *h_n = ctx->gd_n;
+        for (int i = 0; i < 4; ++i) h_stats[i] = any ? ctx->gd.stats[i] : 0;
+    if (h_n) *h_n = ctx->gd.n;
     return 0;
 }
 
@@ -1422,10 +1350,8 @@ static int voxelize_host(const char* who, decltype(&vp_voxelize) call, vp_ctx* c
     void *dw = nullptr, *dx = nullptr, *dt = nullptr;
     const size_t wb = vp_grid_words(f) * 4;
     VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nverts * 12, &dx));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
-    VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
-    VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
+    VP_TRY(stage(ctx, SLOT_XYZ, h_xyz, nverts * 12, &dx));
+    VP_TRY(stage(ctx, SLOT_TRI, h_tri, ntris * 12, &dt));
     VP_TRY(call(ctx, f, (uint32_t*)dw, (const float*)dx, nverts, (const uint32_t*)dt, ntris, algo, 0));
     return vp_download(ctx, h_words, dw, wb);
 }
@@ -1501,14 +1427,11 @@ int vp_mesh_distance_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, si
     if (ntris && (!h_xyz || !h_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
     void *dw = nullptr, *dx = nullptr, *dt = nullptr, *dd = nullptr, *dn = nullptr;
     const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
-    if (h_sign_words) VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nverts * 12, &dx));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
+    if (h_sign_words) VP_TRY(stage(ctx, SLOT_GRID_A, h_sign_words, wb, &dw));
+    VP_TRY(stage(ctx, SLOT_XYZ, h_xyz, nverts * 12, &dx));
+    VP_TRY(stage(ctx, SLOT_TRI, h_tri, ntris * 12, &dt));
     VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, vb, &dd));
     if (h_nearest) VP_TRY(vp_ctx_workspace(ctx, SLOT_NEAREST, vb, &dn));
-    if (h_sign_words) VP_TRY(vp_upload(ctx, dw, h_sign_words, wb));
-    VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
-    VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
     VP_TRY(vp_mesh_distance(ctx, f, (const float*)dx, nverts, (const uint32_t*)dt, ntris, (const uint32_t*)dw, band, (float*)dd, (uint32_t*)dn, algo));
     VP_TRY(vp_download(ctx, h_dist2, dd, vb));
     return h_nearest ? vp_download(ctx, h_nearest, dn, vb) : 0;
@@ -1522,13 +1445,11 @@ int vp_winding_host(vp_ctx* ctx, const vp_frame* f, const float* h_xyz, size_t n
     VP_TRY(check_winding(f, who, beta, level, algo));
     if (ntris && (!h_xyz || !h_tri || !nverts)) return set_error(VP_ERR_INVALID, "%s: null mesh arrays", who);
     void *dx = nullptr, *dt = nullptr;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_XYZ, nverts * 12, &dx));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_TRI, ntris * 12, &dt));
-    VP_TRY(vp_upload(ctx, dx, h_xyz, nverts * 12));
-    VP_TRY(vp_upload(ctx, dt, h_tri, ntris * 12));
+    VP_TRY(stage(ctx, SLOT_XYZ, h_xyz, nverts * 12, &dx));
+    VP_TRY(stage(ctx, SLOT_TRI, h_tri, ntris * 12, &dt));
     VP_TRY(vp_winding(ctx, f, (const float*)dx, nverts, (const uint32_t*)dt, ntris, beta, level, algo, h_inside_count));
-    if (h_w) VP_TRY(vp_download(ctx, h_w, ctx->wn_w.ptr, vp_grid_voxels(f) * 4));
-    return h_inside ? vp_download(ctx, h_inside, ctx->wn_inside.ptr, vp_grid_words(f) * 4) : 0;
+    if (h_w) VP_TRY(vp_download(ctx, h_w, ctx->wn.w.ptr, vp_grid_voxels(f) * 4));
+    return h_inside ? vp_download(ctx, h_inside, ctx->wn.inside.ptr, vp_grid_words(f) * 4) : 0;
 }
 
 int vp_thickness_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, uint32_t rmax, uint32_t thin2, int algo, uint32_t* h_t2,
@@ -1538,11 +1459,10 @@ int vp_thickness_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, u
     if (!ctx || !f || !h_words || (!h_t2 && !h_thin)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
     VP_TRY(check_thickness(f, who, rmax, thin2, algo));
     void* dw = nullptr;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, vp_grid_words(f) * 4, &dw));
-    VP_TRY(vp_upload(ctx, dw, h_words, vp_grid_words(f) * 4));
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_words, vp_grid_words(f) * 4, &dw));
     VP_TRY(vp_thickness(ctx, f, (const uint32_t*)dw, rmax, thin2, algo, h_thin_count));
-    if (h_t2) VP_TRY(vp_download(ctx, h_t2, ctx->th_t2.ptr, vp_grid_voxels(f) * 4));
-    return h_thin ? vp_download(ctx, h_thin, ctx->th_thin.ptr, vp_grid_words(f) * 4) : 0;
+    if (h_t2) VP_TRY(vp_download(ctx, h_t2, ctx->th.t2.ptr, vp_grid_voxels(f) * 4));
+    return h_thin ? vp_download(ctx, h_thin, ctx->th.thin.ptr, vp_grid_words(f) * 4) : 0;
 }
 
 int vp_octree_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int algo, uint32_t* h_nodes, uint64_t capacity, uint64_t* h_count,
@@ -1550,28 +1470,26 @@ int vp_octree_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, int 
 {
     const char* who = "vp_octree_host";
     if (!ctx || !f || !h_words || !h_count || (!h_nodes && capacity)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
-    VP_TRY(check_octree(f, who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     void* dw = nullptr;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, vp_grid_words(f) * 4, &dw));
-    VP_TRY(vp_upload(ctx, dw, h_words, vp_grid_words(f) * 4));
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_words, vp_grid_words(f) * 4, &dw));
     VP_TRY(vp_octree(ctx, f, (const uint32_t*)dw, algo, h_count));
     VP_TRY(vp_octree_result(ctx, nullptr, nullptr, h_level_offset, h_full_leaves, nullptr));
     if (*h_count > capacity) return set_error(VP_ERR_INVALID, "%s: capacity %llu below the %llu nodes of the tree", who,
                                               (unsigned long long)capacity, (unsigned long long)*h_count);
-    return vp_download(ctx, h_nodes, ctx->oc_nodes.ptr, *h_count * 8);
+    return vp_download(ctx, h_nodes, ctx->oc.nodes.ptr, *h_count * 8);
 }
 
 int vp_octree_expand_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_nodes, uint64_t nodes, int algo, uint32_t* h_words)
 {
     const char* who = "vp_octree_expand_host";
     if (!ctx || !f || !h_nodes || !h_words) return set_error(VP_ERR_INVALID, "%s: null argument", who);
-    VP_TRY(check_octree(f, who, algo));
+    VP_TRY(check_grid_1024(f, who, algo));
     VP_TRY(octree_validate(h_nodes, nodes, f->n));                 // nothing that fails the check reaches the device
     void* dn = nullptr;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, nodes * 8, &dn));
-    VP_TRY(vp_upload(ctx, dn, h_nodes, nodes * 8));
+    VP_TRY(stage(ctx, SLOT_SDF, h_nodes, nodes * 8, &dn));
     VP_TRY(vp_octree_expand(ctx, f, (const uint32_t*)dn, nodes, algo));
-    return vp_download(ctx, h_words, ctx->oc_grid.ptr, vp_grid_words(f) * 4);
+    return vp_download(ctx, h_words, ctx->ocx.grid.ptr, vp_grid_words(f) * 4);
 }
 
 int vp_skeleton_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, const uint32_t* h_anchor, int mode, uint32_t max_iters, int algo,
@@ -1582,14 +1500,10 @@ int vp_skeleton_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, co
     VP_TRY(check_skeleton(f, who, mode, algo));
     void *dw = nullptr, *da = nullptr;
     const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_upload(ctx, dw, h_words, wb));
-    if (h_anchor) {
-        VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &da));
-        VP_TRY(vp_upload(ctx, da, h_anchor, wb));
-    }
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_words, wb, &dw));
+    if (h_anchor) VP_TRY(stage(ctx, SLOT_GRID_B, h_anchor, wb, &da));
     VP_TRY(vp_skeleton(ctx, f, (const uint32_t*)dw, (const uint32_t*)da, mode, max_iters, algo, h_stats));
-    return h_skel ? vp_download(ctx, h_skel, ctx->sk_grid.ptr, wb) : 0;
+    return h_skel ? vp_download(ctx, h_skel, ctx->sk.grid.ptr, wb) : 0;
 }
 
 int vp_geodesic_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, const uint32_t* h_seeds, int metric, int algo, uint32_t* h_dist,
@@ -1600,13 +1514,11 @@ int vp_geodesic_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, con
     VP_TRY(check_geodesic(f, who, metric, algo));
     void *dm = nullptr, *ds = nullptr;
     const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dm));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, wb, &ds));
-    VP_TRY(vp_upload(ctx, dm, h_mask, wb));
-    VP_TRY(vp_upload(ctx, ds, h_seeds, wb));
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_mask, wb, &dm));
+    VP_TRY(stage(ctx, SLOT_GRID_B, h_seeds, wb, &ds));
     VP_TRY(vp_geodesic(ctx, f, (const uint32_t*)dm, (const uint32_t*)ds, metric, algo, h_stats));
-    if (h_dist) VP_TRY(vp_download(ctx, h_dist, ctx->gd_dist.ptr, vp_grid_voxels(f) * 4));
-    return h_reach ? vp_download(ctx, h_reach, ctx->gd_reach.ptr, wb) : 0;
+    if (h_dist) VP_TRY(vp_download(ctx, h_dist, ctx->gd.dist.ptr, vp_grid_voxels(f) * 4));
+    return h_reach ? vp_download(ctx, h_reach, ctx->gd.reach.ptr, wb) : 0;
 }
 
 int vp_skeleton_table_host(vp_ctx* ctx, int algo, uint32_t* h_table)
@@ -1658,8 +1570,7 @@ int vp_surfnets_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_words, ui
     if (!counts_only && (!h_cells || !h_xyz || !h_quads)) return set_error(VP_ERR_INVALID, "%s: the three outputs go together", who);
     void *dw = nullptr, *dc = nullptr, *dx = nullptr, *dq = nullptr;
     const size_t wb = vp_grid_words(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, wb, &dw));
-    VP_TRY(vp_upload(ctx, dw, h_words, wb));
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_words, wb, &dw));
     uint64_t nv = 0, nq = 0;
     VP_TRY(vp_surfnets_count(ctx, f, (const uint32_t*)dw, VP_ALGO_TILED, &nv, &nq));
     if (!counts_only && (vertex_capacity < nv || quad_capacity < nq))
@@ -1689,18 +1600,17 @@ int vp_isonets_host(vp_ctx* ctx, const vp_frame* f, const float* h_field, int tr
     if (!counts_only && (!h_cells || !h_xyz || !h_quads)) return set_error(VP_ERR_INVALID, "%s: records, positions and quads go together", who);
     void* df = nullptr;
     const size_t fb = vp_grid_voxels(f) * 4;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_SDF, fb, &df));
-    VP_TRY(vp_upload(ctx, df, h_field, fb));
+    VP_TRY(stage(ctx, SLOT_SDF, h_field, fb, &df));
     uint64_t nv = 0, nq = 0;
     VP_TRY(vp_isonets(ctx, f, (const float*)df, transform, iso, iterations, h_normals != nullptr, algo, &nv, &nq));
     if (!counts_only && (vertex_capacity < nv || quad_capacity < nq))
         return set_error(VP_ERR_INVALID, "%s: capacity %zu vertices / %zu quads, the field has %llu / %llu", who, vertex_capacity, quad_capacity,
                          (unsigned long long)nv, (unsigned long long)nq);
     if (!counts_only && nv) {
-        VP_TRY(vp_download(ctx, h_cells, ctx->iso_cells.ptr, nv * 8));
-        VP_TRY(vp_download(ctx, h_xyz, ctx->iso_xyz.ptr, nv * 12));
-        if (h_normals) VP_TRY(vp_download(ctx, h_normals, ctx->iso_normals.ptr, nv * 12));
-        VP_TRY(vp_download(ctx, h_quads, ctx->iso_quads.ptr, nq * 16));
+        VP_TRY(vp_download(ctx, h_cells, ctx->iso.cells.ptr, nv * 8));
+        VP_TRY(vp_download(ctx, h_xyz, ctx->iso.xyz.ptr, nv * 12));
+        if (h_normals) VP_TRY(vp_download(ctx, h_normals, ctx->iso.normals.ptr, nv * 12));
+        VP_TRY(vp_download(ctx, h_quads, ctx->iso.quads.ptr, nq * 16));
     }
     *h_vertices = nv; *h_quads_out = nq;
     return 0;
@@ -1710,10 +1620,8 @@ int vp_csg_host(vp_ctx* ctx, uint32_t* h_a, const uint32_t* h_b, size_t nwords, 
 {
     if (!ctx || ((!h_a || !h_b) && nwords)) return set_error(VP_ERR_INVALID, "vp_csg_host: null argument");
     void *da = nullptr, *db = nullptr;
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_A, nwords * 4, &da));
-    VP_TRY(vp_ctx_workspace(ctx, SLOT_GRID_B, nwords * 4, &db));
-    VP_TRY(vp_upload(ctx, da, h_a, nwords * 4));
-    VP_TRY(vp_upload(ctx, db, h_b, nwords * 4));
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_a, nwords * 4, &da));
+    VP_TRY(stage(ctx, SLOT_GRID_B, h_b, nwords * 4, &db));
     VP_TRY(vp_csg(ctx, (uint32_t*)da, (const uint32_t*)db, nwords, op));
     return vp_download(ctx, h_a, da, nwords * 4);
 }

@@ -414,10 +414,10 @@ int enqueue_label(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_
     const uint32_t w = n / 32;
     const size_t nvox = (size_t)n * n * n, nwords = nvox / 32, nvec = nvox / 4;
     const uint32_t chunks = (uint32_t)(nvox / kChunk);
-    VP_TRY(reserve(ctx, ctx->comp_cnt, (size_t)chunks * 4));
-    VP_TRY(reserve(ctx, ctx->comp_off, ((size_t)chunks + 1) * 4));
-    uint32_t* cnt = (uint32_t*)ctx->comp_cnt.ptr;
-    uint32_t* off = (uint32_t*)ctx->comp_off.ptr;
+    VP_TRY(reserve(ctx, ctx->comp.cnt, (size_t)chunks * 4));
+    VP_TRY(reserve(ctx, ctx->comp.off, ((size_t)chunks + 1) * 4));
+    uint32_t* cnt = (uint32_t*)ctx->comp.cnt.ptr;
+    uint32_t* off = (uint32_t*)ctx->comp.off.ptr;
     if (algo == VP_ALGO_NAIVE) {
         const unsigned blocks = (unsigned)(nvox / 256);
         {
@@ -466,22 +466,16 @@ int enqueue_sizes(vp_ctx* ctx, uint32_t n, const uint32_t* d_labels, uint32_t co
     return 0;
 }
 
-int host_words(vp_ctx* ctx)
-{
-    if (!ctx->comp_host) VP_HIP(hipHostMalloc((void**)&ctx->comp_host, 2 * sizeof(uint64_t), hipHostMallocDefault));
-    return 0;
-}
-
 }  // namespace
 
 int launch_components_label(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_labels, int conn, int algo, uint32_t* h_count)
 {
-    VP_TRY(host_words(ctx));
+    VP_TRY(ctx->comp.host.need(2));
     VP_TRY(enqueue_label(ctx, n, d_words, d_labels, conn, algo));
     const size_t chunks = (size_t)n * n * n / kChunk;
-    VP_HIP(hipMemcpyAsync(ctx->comp_host, (const uint32_t*)ctx->comp_off.ptr + chunks, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VP_HIP(hipMemcpyAsync(ctx->comp.host, (const uint32_t*)ctx->comp.off.ptr + chunks, 4, hipMemcpyDeviceToHost, ctx->stream));
     VP_HIP(hipStreamSynchronize(ctx->stream));
-    if (h_count) *h_count = (uint32_t)ctx->comp_host[0];
+    if (h_count) *h_count = (uint32_t)ctx->comp.host[0];
     return 0;
 }
 
@@ -498,24 +492,24 @@ int launch_components_filter(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, u
 {
     hipStream_t st = ctx->stream;
     const size_t nvox = (size_t)n * n * n, nvec = nvox / 4, chunks = nvox / kChunk;
-    VP_TRY(host_words(ctx));
-    VP_TRY(reserve(ctx, ctx->comp_labels, nvox * 4, false));
-    VP_TRY(reserve(ctx, ctx->comp_small, 17 * sizeof(uint64_t), false));
-    uint32_t* labels = (uint32_t*)ctx->comp_labels.ptr;
-    unsigned long long* best = (unsigned long long*)ctx->comp_small.ptr;     // 16 winners of KEEP_LARGEST, then the kept voxels
+    VP_TRY(ctx->comp.host.need(2));
+    VP_TRY(reserve(ctx, ctx->comp.labels, nvox * 4, false));
+    VP_TRY(reserve(ctx, ctx->comp.small, 17 * sizeof(uint64_t), false));
+    uint32_t* labels = (uint32_t*)ctx->comp.labels.ptr;
+    unsigned long long* best = (unsigned long long*)ctx->comp.small.ptr;     // 16 winners of KEEP_LARGEST, then the kept voxels
     VP_TRY(enqueue_label(ctx, n, d_words, labels, conn, algo));
     // K sizes the size and keep arrays, so it is read back here; the kept count follows at the end
-    VP_HIP(hipMemcpyAsync(ctx->comp_host, (const uint32_t*)ctx->comp_off.ptr + chunks, 4, hipMemcpyDeviceToHost, st));
+    VP_HIP(hipMemcpyAsync(ctx->comp.host, (const uint32_t*)ctx->comp.off.ptr + chunks, 4, hipMemcpyDeviceToHost, st));
     VP_HIP(hipStreamSynchronize(st));
-    const uint32_t K = (uint32_t)ctx->comp_host[0];
-    ctx->comp_host[1] = 0;
+    const uint32_t K = (uint32_t)ctx->comp.host[0];
+    ctx->comp.host[1] = 0;
     if (K == 0) {
         VP_HIP(hipMemsetAsync(d_out, 0, nvox / 8, st));
     } else {
-        VP_TRY(reserve(ctx, ctx->comp_sizes, (size_t)K * 4));
-        VP_TRY(reserve(ctx, ctx->comp_keep, (size_t)K));
-        uint32_t* sizes = (uint32_t*)ctx->comp_sizes.ptr;
-        uint8_t* keep = (uint8_t*)ctx->comp_keep.ptr;
+        VP_TRY(reserve(ctx, ctx->comp.sizes, (size_t)K * 4));
+        VP_TRY(reserve(ctx, ctx->comp.keep, (size_t)K));
+        uint32_t* sizes = (uint32_t*)ctx->comp.sizes.ptr;
+        uint8_t* keep = (uint8_t*)ctx->comp.keep.ptr;
         VP_TRY(enqueue_sizes(ctx, n, labels, K, sizes));
         VP_HIP(hipMemsetAsync(best, 0, 17 * sizeof(uint64_t), st));
         {
@@ -535,11 +529,11 @@ int launch_components_filter(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, u
             hipLaunchKernelGGL(comp_write, dim3(stream_blocks(ctx, nvec)), dim3(256), 0, st, (const uint4*)labels, nvec, keep, d_out, best + 16);
         }
         VP_HIP(hipGetLastError());
-        VP_HIP(hipMemcpyAsync(ctx->comp_host + 1, best + 16, 8, hipMemcpyDeviceToHost, st));
+        VP_HIP(hipMemcpyAsync(ctx->comp.host + 1, best + 16, 8, hipMemcpyDeviceToHost, st));
     }
     VP_HIP(hipStreamSynchronize(st));
     if (h_count) *h_count = K;
-    if (h_kept) *h_kept = ctx->comp_host[1];
+    if (h_kept) *h_kept = ctx->comp.host[1];
     return 0;
 }
 

@@ -280,8 +280,8 @@ int launch_voxelize_conservative(vp_ctx* ctx, const Frame& f, uint32_t* d_words,
     const size_t nwords = (size_t)f.n * f.n * (f.z1 - f.z0) / 32;
     const unsigned tblocks = (unsigned)((ntris + 255) / 256);
     const bool tiled = algo == VP_ALGO_TILED && ntris > 0;
-    VP_TRY(reserve(ctx, ctx->cvox_cnt, 16));
-    uint32_t* d_nbig = (uint32_t*)ctx->cvox_cnt.ptr;
+    VP_TRY(reserve(ctx, ctx->cvox.cnt, 16));
+    uint32_t* d_nbig = (uint32_t*)ctx->cvox.cnt.ptr;
     {
         // nwords is a multiple of 8 n (n % 32 == 0): whole uint4s; d_words is 16-byte aligned (checked at the ABI)
         const size_t nvec = accumulate ? 0 : nwords / 4;
@@ -303,32 +303,29 @@ int launch_voxelize_conservative(vp_ctx* ctx, const Frame& f, uint32_t* d_words,
     // ---- TILED ----
     // Large-triangle count of an earlier call, if its copy has landed (never waited for): sizes the record list, grow-only.  This is the
     // conservative path's own state; the solid voxelizer's job cache is neither read nor written.
-    if (ctx->cvox_event && ctx->cvox_pending && hipEventQuery(ctx->cvox_event) == hipSuccess) {
-        ctx->cvox_pending = false;
-        ctx->cvox_nbig_seen = std::max<uint64_t>(ctx->cvox_nbig_seen, ctx->cvox_host[0]);
+    if (ctx->cvox.event && ctx->cvox.pending && hipEventQuery(ctx->cvox.event) == hipSuccess) {
+        ctx->cvox.pending = false;
+        ctx->cvox.nbig_seen = std::max<uint64_t>(ctx->cvox.nbig_seen, ctx->cvox.host[0]);
     }
-    const size_t wantRec = std::min<size_t>(ntris, std::max<size_t>((size_t)1 << 16, (size_t)ctx->cvox_nbig_seen + ctx->cvox_nbig_seen / 4));
-    VP_TRY(reserve(ctx, ctx->cvox_rec, wantRec * sizeof(CRec)));
-    uint32_t rcap = (uint32_t)std::min<size_t>(ctx->cvox_rec.bytes / sizeof(CRec), ntris);
+    const size_t wantRec = std::min<size_t>(ntris, std::max<size_t>((size_t)1 << 16, (size_t)ctx->cvox.nbig_seen + ctx->cvox.nbig_seen / 4));
+    VP_TRY(reserve(ctx, ctx->cvox.rec, wantRec * sizeof(CRec)));
+    uint32_t rcap = (uint32_t)std::min<size_t>(ctx->cvox.rec.bytes / sizeof(CRec), ntris);
 #ifdef VP_TEST_HOOKS   // test builds only (libvphip_hooks.so): force the walk-in-place path of a full record list
     if (const char* e = getenv("VP_CVOX_REC_CAP")) rcap = std::min<uint32_t>(rcap, (uint32_t)strtoul(e, nullptr, 10));
 #endif
-    VP_TRY(reserve(ctx, ctx->cvox_base, ((size_t)rcap + 1) * 8));
-    CRec* rec = (CRec*)ctx->cvox_rec.ptr;
-    unsigned long long* base = (unsigned long long*)ctx->cvox_base.ptr;
+    VP_TRY(reserve(ctx, ctx->cvox.base, ((size_t)rcap + 1) * 8));
+    CRec* rec = (CRec*)ctx->cvox.rec.ptr;
+    unsigned long long* base = (unsigned long long*)ctx->cvox.base.ptr;
     {
         ProfScope p(ctx, VP_K_CVOX_SETUP);
         hipLaunchKernelGGL(cvox_setup, dim3(tblocks), dim3(256), 0, st, f, d_xyz, nverts, d_tri, ntris, rec, rcap, d_nbig, d_words);
     }
-    if (!ctx->cvox_host) {
-        VP_HIP(hipHostMalloc((void**)&ctx->cvox_host, sizeof(uint32_t), hipHostMallocDefault));
-        ctx->cvox_host[0] = 0;
-        VP_HIP(hipEventCreateWithFlags(&ctx->cvox_event, hipEventDisableTiming));
-    }
-    if (!ctx->cvox_pending) {
-        VP_HIP(hipMemcpyAsync(ctx->cvox_host, d_nbig, 4, hipMemcpyDeviceToHost, st));
-        VP_HIP(hipEventRecord(ctx->cvox_event, st));
-        ctx->cvox_pending = true;
+    VP_TRY(ctx->cvox.host.need(1, true));
+    if (!ctx->cvox.event) VP_HIP(hipEventCreateWithFlags(&ctx->cvox.event, hipEventDisableTiming));
+    if (!ctx->cvox.pending) {
+        VP_HIP(hipMemcpyAsync(ctx->cvox.host, d_nbig, 4, hipMemcpyDeviceToHost, st));
+        VP_HIP(hipEventRecord(ctx->cvox.event, st));
+        ctx->cvox.pending = true;
     }
     {
         ProfScope p(ctx, VP_K_CVOX_SCAN);

@@ -171,14 +171,14 @@ int launch_edt(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int seeds, 
     const size_t nvox = (size_t)n * n * n;
     uint32_t* vol2 = nullptr;
     if (algo == VP_ALGO_NAIVE) {
-        VP_TRY(reserve(ctx, ctx->edt_vol2, nvox * 4, false));
-        vol2 = (uint32_t*)ctx->edt_vol2.ptr;
+        VP_TRY(reserve(ctx, ctx->edt.vol2, nvox * 4, false));
+        vol2 = (uint32_t*)ctx->edt.vol2.ptr;
     }
     const uint32_t* sw = d_words;
     if (seeds == VP_EDT_SEEDS_BORDER) {
-        VP_TRY(reserve(ctx, ctx->edt_mask, nvox / 8, false));
-        VP_TRY(launch_jfa_init(ctx, f, d_words, nullptr, nullptr, nullptr, (uint32_t*)ctx->edt_mask.ptr));
-        sw = (const uint32_t*)ctx->edt_mask.ptr;
+        VP_TRY(reserve(ctx, ctx->edt.mask, nvox / 8, false));
+        VP_TRY(launch_jfa_init(ctx, f, d_words, nullptr, nullptr, nullptr, (uint32_t*)ctx->edt.mask.ptr));
+        sw = (const uint32_t*)ctx->edt.mask.ptr;
     }
     {
         const uint32_t rows = n * n, RB = 256u / w;
@@ -228,10 +228,10 @@ int launch_edt_morph(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint3
     const size_t nvox = (size_t)f.n * f.n * f.n, bytes = nvox / 8;
     if (radius == 0) return launch_stream_copy(ctx, d_out, d_words, bytes);
     const bool two = op == VP_MORPH_OPEN || op == VP_MORPH_CLOSE;
-    VP_TRY(reserve(ctx, ctx->edt_vol, nvox * 4, false));
-    if (algo == VP_ALGO_NAIVE) VP_TRY(reserve(ctx, ctx->edt_vol2, nvox * 4, false));
-    if (two) VP_TRY(reserve(ctx, ctx->edt_tmp, bytes, false));
-    uint32_t* vol = (uint32_t*)ctx->edt_vol.ptr;
+    VP_TRY(reserve(ctx, ctx->edt.vol, nvox * 4, false));
+    if (algo == VP_ALGO_NAIVE) VP_TRY(reserve(ctx, ctx->edt.vol2, nvox * 4, false));
+    if (two) VP_TRY(reserve(ctx, ctx->edt.tmp, bytes, false));
+    uint32_t* vol = (uint32_t*)ctx->edt.vol.ptr;
     const uint32_t r2 = radius * radius;                             // radius <= 65535
     auto one = [&](const uint32_t* in, uint32_t* out, bool erode) -> int {
         VP_TRY(launch_edt(ctx, f, in, erode ? VP_EDT_SEEDS_UNSET : VP_EDT_SEEDS_SET, vol, algo));
@@ -241,7 +241,7 @@ int launch_edt_morph(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint3
         return 0;
     };
     if (!two) return one(d_words, d_out, op == VP_MORPH_ERODE);
-    uint32_t* tmp = (uint32_t*)ctx->edt_tmp.ptr;
+    uint32_t* tmp = (uint32_t*)ctx->edt.tmp.ptr;
     VP_TRY(one(d_words, tmp, op == VP_MORPH_OPEN));                  // open = dilate(erode), close = erode(dilate)
     return one(tmp, d_out, op == VP_MORPH_CLOSE);
 }

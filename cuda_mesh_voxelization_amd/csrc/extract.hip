@@ -115,10 +115,10 @@ int launch_extract_count(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, i
 {
     const size_t nwords = (size_t)f.n * f.n * f.n / 32;
     const size_t blocks = (nwords + kBlockWords - 1) / kBlockWords;
-    VP_TRY(reserve(ctx, ctx->ext_cnt, blocks * 4));
-    VP_TRY(reserve(ctx, ctx->ext_off, (blocks + 1) * 8));
-    uint32_t* cnt = (uint32_t*)ctx->ext_cnt.ptr;
-    unsigned long long* off = (unsigned long long*)ctx->ext_off.ptr;
+    VP_TRY(reserve(ctx, ctx->ext.cnt, blocks * 4));
+    VP_TRY(reserve(ctx, ctx->ext.off, (blocks + 1) * 8));
+    uint32_t* cnt = (uint32_t*)ctx->ext.cnt.ptr;
+    unsigned long long* off = (unsigned long long*)ctx->ext.off.ptr;
     {
         ProfScope p(ctx, VP_K_EXTRACT);
         if (mode == VP_EXTRACT_EXPOSED) hipLaunchKernelGGL(extract_count<VP_EXTRACT_EXPOSED>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, d_words, nwords, cnt);
@@ -129,7 +129,7 @@ int launch_extract_count(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, i
     unsigned long long total = 0;
     VP_HIP(hipMemcpyAsync(&total, off + blocks, 8, hipMemcpyDeviceToHost, ctx->stream));
     VP_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->ext_words = d_words; ctx->ext_mode = mode; ctx->ext_n = f.n; ctx->ext_total = total;
+    ctx->ext.words = d_words; ctx->ext.mode = mode; ctx->ext.n = f.n; ctx->ext.total = total;
     if (h_count) *h_count = total;
     return 0;
 }
@@ -137,11 +137,11 @@ int launch_extract_count(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, i
 int launch_extract_write(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int mode, const float* d_sdf,
                          uint64_t* d_records, float* d_values, size_t capacity)
 {
-    if (ctx->ext_words != d_words || ctx->ext_mode != mode || ctx->ext_n != f.n)
+    if (ctx->ext.words != d_words || ctx->ext.mode != mode || ctx->ext.n != f.n)
         return set_error(VP_ERR_INVALID, "vp_extract: call vp_extract_count with the same grid and mode first");
     const size_t nwords = (size_t)f.n * f.n * f.n / 32;
     const size_t blocks = (nwords + kBlockWords - 1) / kBlockWords;
-    const unsigned long long* off = (const unsigned long long*)ctx->ext_off.ptr;
+    const unsigned long long* off = (const unsigned long long*)ctx->ext.off.ptr;
     ProfScope p(ctx, VP_K_EXTRACT);
     if (mode == VP_EXTRACT_SET)
         hipLaunchKernelGGL(extract_write<VP_EXTRACT_SET>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, d_words, nwords, off, d_sdf,

@@ -204,9 +204,9 @@ int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint3
     hipStream_t st = ctx->stream;
     const uint32_t w = n / 32;
     const size_t nwords = (size_t)n * n * w;
-    VP_TRY(reserve(ctx, ctx->fill_flags, 2 * kFillBatch * sizeof(uint32_t), false));
-    if (!ctx->fill_host) VP_HIP(hipHostMalloc((void**)&ctx->fill_host, kFillBatch * sizeof(uint32_t), hipHostMallocDefault));
-    uint32_t* flags = (uint32_t*)ctx->fill_flags.ptr;
+    VP_TRY(reserve(ctx, ctx->fill.flags, 2 * kFillBatch * sizeof(uint32_t), false));
+    VP_TRY(ctx->fill.host.need(kFillBatch));
+    uint32_t* flags = (uint32_t*)ctx->fill.flags.ptr;
 
     uint32_t lshift = 0;
     while ((1u << lshift) < w) ++lshift;
@@ -237,10 +237,10 @@ int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint3
             }
         }
         VP_HIP(hipGetLastError());
-        VP_HIP(hipMemcpyAsync(ctx->fill_host, fl, kFillBatch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VP_HIP(hipMemcpyAsync(ctx->fill.host, fl, kFillBatch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         VP_HIP(hipStreamSynchronize(st));
         uint32_t i = 0;
-        while (i < kFillBatch && ctx->fill_host[i]) ++i;
+        while (i < kFillBatch && ctx->fill.host[i]) ++i;
         if (i < kFillBatch) { rounds = batch * kFillBatch + i + 1; break; }
     }
     {

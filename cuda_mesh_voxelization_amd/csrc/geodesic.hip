@@ -18,7 +18,7 @@
 //                     reads per voxel), then relaxes forward and backward along its own row in registers (exact for the face weight) and
 //                     stores what it lowered.  Sweeps repeat until one lowers nothing in the block or kGeoSweeps have run; then the
 //                     values that changed are written back, by the lanes along x.
-//          gd_list    the list of active blocks by count -> scan -> write from the block flags, which it clears (one workgroup).  A block
+//          block_list (block_list.h)  the list of active blocks by count -> scan -> write from the block flags, which it clears (one workgroup).  A block
 //                     whose face, edge or corner voxel changed raises, with plain stores of 1, the flags of exactly the neighbour blocks
 //                     whose halo holds that voxel (face neighbours only for VP_GEO_6); a block that was still changing at the sweep cap
 //                     raises its own.  The first list is the blocks whose tile holds a used seed, in its interior OR in its halo (gd_init
@@ -38,8 +38,8 @@
 // voxel of M but the seeds, and with (3) D is the shortest distance: the unique fixed point, whatever the order of execution.  Saturation
 // is monotone and changes none of it.
 // Kernel boundaries are the only synchronisation between workgroups; every device loop has a compile-time bound.
+#include "block_list.h"
 #include "vp_internal.h"
-#include "wg_scan.h"
 
 #include <algorithm>
 
@@ -49,15 +49,12 @@ namespace {
 
 constexpr uint32_t kGeoSweeps = 64;  // TILED: sweeps over a block per launch at most (tests/test_geodesic_gpu.py reads this line)
 constexpr uint32_t kGeoBatch = 8;    // NAIVE: rounds enqueued between two read-backs of their flags
-constexpr uint32_t kBlockY = 16, kBlockZ = 16;                    // a block is one word (32 voxels) x 16 x 16: one lane per x row
-constexpr uint32_t kHalo = 18;                                    // staged rows per axis
+constexpr uint32_t kHalo = 18;                                    // staged rows per axis of a block (block_list.h: one lane per x row)
 constexpr uint32_t kRowVals = 34, kRowPitch = 35;                 // staged values per row (x - 1 .. x + 32) and the pitch in words
 constexpr uint32_t kStaged = kHalo * kHalo * kRowVals;            // 11,016 values
-constexpr uint32_t kMaxBlocksPerThread = 128;                     // n = 1024: 32 * 64 * 64 blocks / 1024 threads
 constexpr uint32_t kNone = VP_GEO_NONE, kMax = VP_GEO_MAX;
 // the counters in front of the flags: kAuxHead bytes, of which seeds used (u64) | voxels reached (u64) | key of the farthest voxel (u64) |
 // active blocks (u32) are in use; kCnt* = where each starts, in 32-bit words
-constexpr size_t kAuxHead = 64;
 constexpr uint32_t kCntSeeds = 0, kCntReached = 2, kCntKey = 4, kCntActive = 6;
 constexpr uint32_t kFaceBlocks = (1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22);   // of bit dx+1 + 3 (dy+1) + 9 (dz+1)
 
@@ -157,21 +154,6 @@ gd_naive(const uint32_t* __restrict__ mask, uint32_t* D, uint32_t n, const uint3
 }
 
 // ---- TILED -------------------------------------------------------------------------------------------------------------------------
-
-// one workgroup: list = the indices of the raised flags in ascending order, counters[kCntActive] = their number; the flags are cleared
-__global__ void __launch_bounds__(1024)
-gd_list(uint32_t* __restrict__ flags, uint32_t nblocks, uint32_t* __restrict__ list, uint32_t* __restrict__ counters)
-{
-    __shared__ uint32_t part[1024];
-    const uint32_t total = wg_scan_1024<uint32_t, uint32_t>(
-        part, nblocks, [&](uint32_t i) { return flags[i] ? 1u : 0u; }, [&](uint32_t i, uint32_t v) { if (flags[i]) list[v] = i; });
-    __syncthreads();
-    for (uint32_t k = 0; k < kMaxBlocksPerThread; ++k) {
-        const uint32_t i = k * 1024u + threadIdx.x;
-        if (i < nblocks) flags[i] = 0u;
-    }
-    if (threadIdx.x == 0) counters[kCntActive] = total;
-}
 
 // column c of the window around the row at `row` (word offset of its column 0): own = the row's value, same = the minimum that reaches a
 // voxel of the row at the same x (through the eight rows around it), side = the one that reaches the voxels at x - 1 and x + 1
@@ -291,21 +273,21 @@ void naive_launch(hipStream_t st, unsigned wgs, const uint32_t* mask, uint32_t* 
 int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const uint32_t* d_seeds, int metric, int algo, uint64_t* h_stats)
 {
     hipStream_t st = ctx->stream;
-    const uint32_t n = f.n, w = n / 32, nb = n / kBlockY, nblocks = w * nb * nb;
+    const uint32_t n = f.n, nblocks = block_count(n);
     const size_t voxels = (size_t)n * n * n;
     const unsigned wgs = (unsigned)(voxels / 256);
-    ctx->gd_n = 0;                                                 // from here on the previous result is gone
-    VP_TRY(reserve(ctx, ctx->gd_dist, voxels * 4, false));
-    VP_TRY(reserve(ctx, ctx->gd_reach, voxels / 8, false));
-    VP_TRY(reserve(ctx, ctx->gd_aux, kAuxHead + (size_t)std::max(nblocks * 2u, 2u * kGeoBatch) * 4, false));
-    if (!ctx->gd_host) VP_HIP(hipHostMalloc((void**)&ctx->gd_host, kAuxHead, hipHostMallocDefault));
-    uint32_t* D = (uint32_t*)ctx->gd_dist.ptr;
-    uint32_t* counters = (uint32_t*)ctx->gd_aux.ptr;
-    uint32_t* flags = (uint32_t*)((char*)ctx->gd_aux.ptr + kAuxHead);   // TILED: block flags, then the list; NAIVE: the ring of round flags
+    ctx->gd.n = 0;                                                 // from here on the previous result is gone
+    VP_TRY(reserve(ctx, ctx->gd.dist, voxels * 4, false));
+    VP_TRY(reserve(ctx, ctx->gd.reach, voxels / 8, false));
+    VP_TRY(reserve(ctx, ctx->gd.aux, kAuxHead + (size_t)std::max(nblocks * 2u, 2u * kGeoBatch) * 4, false));
+    VP_TRY(ctx->gd.host.need(kAuxHead / 8));
+    uint32_t* D = (uint32_t*)ctx->gd.dist.ptr;
+    uint32_t* counters = (uint32_t*)ctx->gd.aux.ptr;
+    uint32_t* flags = block_flags(ctx->gd.aux.ptr);                      // TILED: block flags, then the list; NAIVE: the ring of round flags
     uint32_t* list = flags + nblocks;
-    volatile uint32_t* host = (volatile uint32_t*)ctx->gd_host;
+    volatile uint32_t* host = (volatile uint32_t*)ctx->gd.host.p;
 
-    VP_HIP(hipMemsetAsync(ctx->gd_aux.ptr, 0, kAuxHead + (size_t)(algo == VP_ALGO_TILED ? nblocks : 2u * kGeoBatch) * 4, st));
+    VP_HIP(hipMemsetAsync(ctx->gd.aux.ptr, 0, kAuxHead + (size_t)(algo == VP_ALGO_TILED ? nblocks : 2u * kGeoBatch) * 4, st));
     {
         ProfScope p(ctx, VP_K_MD_FILL);
         hipLaunchKernelGGL(gd_init, dim3(wgs / 4), dim3(256), 0, st, d_mask, d_seeds, (uint4*)D, n, algo == VP_ALGO_TILED ? flags : nullptr,
@@ -315,10 +297,10 @@ int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const u
         for (;;) {
             {
                 ProfScope p(ctx, VP_K_MD_SCAN);
-                hipLaunchKernelGGL(gd_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters);
+                hipLaunchKernelGGL(block_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters + kCntActive);
             }
             VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->gd_host, counters + kCntActive, 4, hipMemcpyDeviceToHost, st));
+            VP_HIP(hipMemcpyAsync(ctx->gd.host, counters + kCntActive, 4, hipMemcpyDeviceToHost, st));
             VP_HIP(hipStreamSynchronize(st));
             const uint32_t active = host[0];
             if (active == 0) break;                                // no block's halo or interior changed since it last ran: the fixed point
@@ -340,7 +322,7 @@ int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const u
                 else naive_launch<VP_GEO_CHAMFER>(st, wgs, d_mask, D, n, prev, fl + i);
             }
             VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->gd_host, fl, kGeoBatch * 4, hipMemcpyDeviceToHost, st));
+            VP_HIP(hipMemcpyAsync(ctx->gd.host, fl, kGeoBatch * 4, hipMemcpyDeviceToHost, st));
             VP_HIP(hipStreamSynchronize(st));
             uint32_t i = 0;
             while (i < kGeoBatch && host[i]) ++i;
@@ -349,19 +331,19 @@ int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const u
     }
     {
         ProfScope p(ctx, VP_K_MD_SPLIT);
-        hipLaunchKernelGGL(gd_final, dim3(wgs), dim3(256), 0, st, (const uint32_t*)D, (uint32_t*)ctx->gd_reach.ptr, (unsigned long long*)counters);
+        hipLaunchKernelGGL(gd_final, dim3(wgs), dim3(256), 0, st, (const uint32_t*)D, (uint32_t*)ctx->gd.reach.ptr, (unsigned long long*)counters);
     }
     VP_HIP(hipGetLastError());
-    VP_HIP(hipMemcpyAsync(ctx->gd_host, counters, 24, hipMemcpyDeviceToHost, st));
+    VP_HIP(hipMemcpyAsync(ctx->gd.host, counters, 24, hipMemcpyDeviceToHost, st));
     VP_HIP(hipStreamSynchronize(st));
-    const uint64_t* h64 = (const uint64_t*)ctx->gd_host;
+    const uint64_t* h64 = ctx->gd.host;
     const uint64_t reached = h64[kCntReached / 2], key = h64[kCntKey / 2];
-    ctx->gd_stats[0] = reached ? h64[kCntSeeds / 2] : 0;
-    ctx->gd_stats[1] = reached;
-    ctx->gd_stats[2] = reached ? key >> 32 : 0;
-    ctx->gd_stats[3] = reached ? 0xFFFFFFFFull - (key & 0xFFFFFFFFull) : 0;
-    if (h_stats) std::copy(ctx->gd_stats, ctx->gd_stats + 4, h_stats);
-    ctx->gd_n = n;
+    ctx->gd.stats[0] = reached ? h64[kCntSeeds / 2] : 0;
+    ctx->gd.stats[1] = reached;
+    ctx->gd.stats[2] = reached ? key >> 32 : 0;
+    ctx->gd.stats[3] = reached ? 0xFFFFFFFFull - (key & 0xFFFFFFFFull) : 0;
+    if (h_stats) std::copy(ctx->gd.stats, ctx->gd.stats + 4, h_stats);
+    ctx->gd.n = n;
     return 0;
 }
 

@@ -170,36 +170,36 @@ int launch_iso_place(vp_ctx* ctx, uint32_t n, int algo, const IsoField& iso, con
 int launch_isonets(vp_ctx* ctx, uint32_t n, const float* d_field, int transform, float iso, uint32_t iterations, bool want_normals, int algo)
 {
     const size_t nvox = (size_t)n * n * n;
-    ctx->iso_vertices = ctx->iso_quad_count = 0;
-    ctx->iso_has_normals = false;
-    VP_TRY(reserve(ctx, ctx->iso_words, nvox / 8));
+    ctx->iso.vertices = ctx->iso.quad_count = 0;
+    ctx->iso.has_normals = false;
+    VP_TRY(reserve(ctx, ctx->iso.words, nvox / 8));
     const Field f{d_field, n, transform, iso};
     {
         ProfScope p(ctx, algo == VP_ALGO_NAIVE ? VP_K_SN_CELLS_NAIVE : VP_K_SN_CELLS);
         if (algo == VP_ALGO_NAIVE) {
             const size_t nwords = nvox / 32;
             hipLaunchKernelGGL(iso_classify_naive, dim3((unsigned)((nwords + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, f, nwords,
-                               (uint32_t*)ctx->iso_words.ptr);
+                               (uint32_t*)ctx->iso.words.ptr);
         } else {
             const size_t per_block = (size_t)64 * kLoads * (kBlock / 64);
             hipLaunchKernelGGL(iso_classify, dim3((unsigned)((nvox + per_block - 1) / per_block)), dim3(kBlock), 0, ctx->stream, f, nvox,
-                               (unsigned long long*)ctx->iso_words.ptr);
+                               (unsigned long long*)ctx->iso.words.ptr);
         }
     }
     VP_HIP(hipGetLastError());
-    const uint32_t* words = (const uint32_t*)ctx->iso_words.ptr;
+    const uint32_t* words = (const uint32_t*)ctx->iso.words.ptr;
     uint64_t nv = 0, nq = 0;
     const int rc = launch_surfnets_count(ctx, n, words, algo, &nv, &nq);
-    ctx->sn_words = nullptr;                                      // the scratch now belongs to this build: no vp_surfnets may be served from it
+    ctx->sn.words = nullptr;                                      // the scratch now belongs to this build: no vp_surfnets may be served from it
     VP_TRY(rc);
-    VP_TRY(reserve(ctx, ctx->iso_cells, nv ? nv * 8 : 8));
-    VP_TRY(reserve(ctx, ctx->iso_xyz, nv ? nv * 12 : 8));
-    if (want_normals) VP_TRY(reserve(ctx, ctx->iso_normals, nv ? nv * 12 : 8));
-    VP_TRY(reserve(ctx, ctx->iso_quads, nq ? nq * 16 : 8));
-    IsoField field{d_field, transform, iso, want_normals ? (float*)ctx->iso_normals.ptr : nullptr};
-    VP_TRY(launch_surfnets_write(ctx, n, words, algo, iterations, (uint64_t*)ctx->iso_cells.ptr, (float*)ctx->iso_xyz.ptr,
-                                 (uint32_t*)ctx->iso_quads.ptr, &field));
-    ctx->iso_vertices = nv; ctx->iso_quad_count = nq; ctx->iso_has_normals = want_normals;
+    VP_TRY(reserve(ctx, ctx->iso.cells, nv ? nv * 8 : 8));
+    VP_TRY(reserve(ctx, ctx->iso.xyz, nv ? nv * 12 : 8));
+    if (want_normals) VP_TRY(reserve(ctx, ctx->iso.normals, nv ? nv * 12 : 8));
+    VP_TRY(reserve(ctx, ctx->iso.quads, nq ? nq * 16 : 8));
+    IsoField field{d_field, transform, iso, want_normals ? (float*)ctx->iso.normals.ptr : nullptr};
+    VP_TRY(launch_surfnets_write(ctx, n, words, algo, iterations, (uint64_t*)ctx->iso.cells.ptr, (float*)ctx->iso.xyz.ptr,
+                                 (uint32_t*)ctx->iso.quads.ptr, &field));
+    ctx->iso.vertices = nv; ctx->iso.quad_count = nq; ctx->iso.has_normals = want_normals;
     return 0;
 }
 

@@ -458,18 +458,18 @@ size_t jfa_id_bytes(const Frame& f) { return wide(f) ? 8 : 4; }
 // format's word row (2048 x 4) with its byte row (2048 x 1) right behind it.
 int ensure_none_rows(vp_ctx* ctx)
 {
-    if (ctx->none_row.ptr) return 0;
-    VP_TRY(reserve(ctx, ctx->none_row, 2 * 1024 * 4 + 2048 * 4 + 2048));
-    char* p = (char*)ctx->none_row.ptr;
+    if (ctx->jfa.none_row.ptr) return 0;
+    VP_TRY(reserve(ctx, ctx->jfa.none_row, 2 * 1024 * 4 + 2048 * 4 + 2048));
+    char* p = (char*)ctx->jfa.none_row.ptr;
     VP_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)kNone9, 1024, ctx->stream));
     VP_HIP(hipMemsetD32Async((hipDeviceptr_t)(p + 1024 * 4), (int)kNone10, 1024, ctx->stream));
     VP_HIP(hipMemsetD32Async((hipDeviceptr_t)(p + 2 * 1024 * 4), (int)IdC::kNoneWord, 2048, ctx->stream));
     VP_HIP(hipMemsetAsync(p + 2 * 1024 * 4 + 2048 * 4, (int)IdC::kNoneByte, 2048, ctx->stream));
     return 0;
 }
-const void* none_row_id9(vp_ctx* ctx) { return ctx->none_row.ptr; }
-const void* none_row_id10(vp_ctx* ctx) { return (const char*)ctx->none_row.ptr + 1024 * 4; }
-const void* none_row_idc(vp_ctx* ctx) { return (const char*)ctx->none_row.ptr + 2 * 1024 * 4; }
+const void* none_row_id9(vp_ctx* ctx) { return ctx->jfa.none_row.ptr; }
+const void* none_row_id10(vp_ctx* ctx) { return (const char*)ctx->jfa.none_row.ptr + 1024 * 4; }
+const void* none_row_idc(vp_ctx* ctx) { return (const char*)ctx->jfa.none_row.ptr + 2 * 1024 * 4; }
 static_assert(Id9::kNoneValue == kNone9 && Id10::kNoneValue == kNone10, "vp_internal.h");
 
 // ------------------------------------------------------------------------------------------ seeding

@@ -435,8 +435,8 @@ int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t
     }
 
     if (algo == VP_ALGO_NAIVE) {
-        VP_TRY(reserve(ctx, ctx->md_keys, voxels * 8, false));
-        unsigned long long* keys = (unsigned long long*)ctx->md_keys.ptr;
+        VP_TRY(reserve(ctx, ctx->md.keys, voxels * 8, false));
+        unsigned long long* keys = (unsigned long long*)ctx->md.keys.ptr;
         uint32_t b2bits;
         memcpy(&b2bits, &bn.b2, 4);
         {
@@ -457,18 +457,18 @@ int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t
 
     // ---- TILED ----
     const uint32_t nb = f.n / 8, per_plane = nb * nb, bricks = per_plane * nb;
-    VP_TRY(reserve(ctx, ctx->md_rec, ntris * sizeof(MRec)));
-    VP_TRY(reserve(ctx, ctx->md_base, (ntris + 1) * 8 + ntris * 4));            // the row scan, then the row counts
-    VP_TRY(reserve(ctx, ctx->md_cnt, (size_t)bricks * 8 + (size_t)nb * 8));         // counts, write cursors, plane sums
-    VP_TRY(reserve(ctx, ctx->md_off, (size_t)bricks * 8));
-    if (!ctx->md_host) VP_HIP(hipHostMalloc((void**)&ctx->md_host, 128 * sizeof(uint64_t), hipHostMallocDefault));
-    MRec* rec = (MRec*)ctx->md_rec.ptr;
-    unsigned long long* base = (unsigned long long*)ctx->md_base.ptr;
+    VP_TRY(reserve(ctx, ctx->md.rec, ntris * sizeof(MRec)));
+    VP_TRY(reserve(ctx, ctx->md.base, (ntris + 1) * 8 + ntris * 4));            // the row scan, then the row counts
+    VP_TRY(reserve(ctx, ctx->md.cnt, (size_t)bricks * 8 + (size_t)nb * 8));         // counts, write cursors, plane sums
+    VP_TRY(reserve(ctx, ctx->md.off, (size_t)bricks * 8));
+    VP_TRY(ctx->md.host.need(128));
+    MRec* rec = (MRec*)ctx->md.rec.ptr;
+    unsigned long long* base = (unsigned long long*)ctx->md.base.ptr;
     uint32_t* rows = (uint32_t*)(base + ntris + 1);
-    unsigned long long* sums = (unsigned long long*)ctx->md_cnt.ptr;                 // 8-byte aligned at the front
+    unsigned long long* sums = (unsigned long long*)ctx->md.cnt.ptr;                 // 8-byte aligned at the front
     uint32_t* cnt = (uint32_t*)(sums + nb);
     uint32_t* cur = cnt + bricks;
-    unsigned long long* off = (unsigned long long*)ctx->md_off.ptr;
+    unsigned long long* off = (unsigned long long*)ctx->md.off.ptr;
     const unsigned bblocks = (unsigned)ctx->cus * 8u;
 
     VP_HIP(hipMemsetAsync(cnt, 0, (size_t)bricks * 8, st));
@@ -487,7 +487,7 @@ int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t
         hipLaunchKernelGGL(md_plane_sums, dim3(nb), dim3(256), 0, st, (const uint32_t*)cnt, per_plane, sums);
     }
     VP_HIP(hipGetLastError());
-    VP_HIP(hipMemcpyAsync(ctx->md_host, sums, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    VP_HIP(hipMemcpyAsync(ctx->md.host, sums, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
     VP_HIP(hipStreamSynchronize(st));                              // the one read-back: the plane totals size the lists
 
     uint64_t cap = kListCap;
@@ -497,20 +497,20 @@ int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t
     // z ranges of brick planes whose lists fit the cap (a single plane above the cap is a range of its own)
     uint64_t longest = 0, total = 0;
     for (uint32_t z = 0; z < nb;) {
-        uint64_t s = ctx->md_host[z];
+        uint64_t s = ctx->md.host[z];
         uint32_t e = z + 1;
-        while (e < nb && s + ctx->md_host[e] <= cap) s += ctx->md_host[e++];
+        while (e < nb && s + ctx->md.host[e] <= cap) s += ctx->md.host[e++];
         longest = std::max(longest, s);
         total += s;
         z = e;
     }
-    ctx->md_last_total = total;
-    VP_TRY(reserve(ctx, ctx->md_list, std::max<uint64_t>(longest, 4) * 4));
-    uint32_t* list = (uint32_t*)ctx->md_list.ptr;
+    ctx->md.last_total = total;
+    VP_TRY(reserve(ctx, ctx->md.list, std::max<uint64_t>(longest, 4) * 4));
+    uint32_t* list = (uint32_t*)ctx->md.list.ptr;
     for (uint32_t z = 0; z < nb;) {
-        uint64_t s = ctx->md_host[z];
+        uint64_t s = ctx->md.host[z];
         uint32_t e = z + 1;
-        while (e < nb && s + ctx->md_host[e] <= cap) s += ctx->md_host[e++];
+        while (e < nb && s + ctx->md.host[e] <= cap) s += ctx->md.host[e++];
         if (s) {
             const uint32_t first = z * per_plane, m = (e - z) * per_plane;
             {

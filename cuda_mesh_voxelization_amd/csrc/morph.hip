@@ -237,7 +237,7 @@ int one_pass(vp_ctx* ctx, uint32_t n, const uint32_t* d_in, uint32_t* d_out, boo
         hipLaunchKernelGGL(morph_naive, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, d_in, d_out, n, w, (int)r, inv, nwords);
     } else {
         const Tables& t = tables();
-        const uint32_t* tab = (const uint32_t*)ctx->morph_tab.ptr + t.start[r];
+        const uint32_t* tab = (const uint32_t*)ctx->morph.tab.ptr + t.start[r];
         const uint32_t ntab = t.start[r + 1] - t.start[r];
         const uint32_t G = (w % 4 == 0) ? 4u : 1u;
         const TileShape s = tile_shape(w, G, r);
@@ -262,15 +262,15 @@ int launch_morph(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint32_t* d_o
 {
     const size_t bytes = (size_t)n * n * n / 8;
     if (radius == 0) return launch_stream_copy(ctx, d_out, d_words, bytes);
-    if (algo == VP_ALGO_TILED && !ctx->morph_tab.ptr) {
+    if (algo == VP_ALGO_TILED && !ctx->morph.tab.ptr) {
         // first tiled call on this context: the row tables of every radius (the only synchronising step besides growing morph_tmp)
         const Tables& t = tables();
-        VP_TRY(reserve(ctx, ctx->morph_tab, t.entries.size() * sizeof(uint32_t), false));
-        VP_HIP(hipMemcpy(ctx->morph_tab.ptr, t.entries.data(), t.entries.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        VP_TRY(reserve(ctx, ctx->morph.tab, t.entries.size() * sizeof(uint32_t), false));
+        VP_HIP(hipMemcpy(ctx->morph.tab.ptr, t.entries.data(), t.entries.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (op == VP_MORPH_DILATE || op == VP_MORPH_ERODE) return one_pass(ctx, n, d_words, d_out, op == VP_MORPH_ERODE, radius, algo);
-    VP_TRY(reserve(ctx, ctx->morph_tmp, bytes, false));
-    uint32_t* tmp = (uint32_t*)ctx->morph_tmp.ptr;
+    VP_TRY(reserve(ctx, ctx->morph.tmp, bytes, false));
+    uint32_t* tmp = (uint32_t*)ctx->morph.tmp.ptr;
     VP_TRY(one_pass(ctx, n, d_words, tmp, op == VP_MORPH_OPEN, radius, algo));      // open = dilate(erode), close = erode(dilate)
     return one_pass(ctx, n, tmp, d_out, op == VP_MORPH_CLOSE, radius, algo);
 }

@@ -412,15 +412,15 @@ int launch_octree(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int algo
 {
     hipStream_t st = ctx->stream;
     const uint32_t n = f.n, L = levels_of(n), U = L - 5u, nb = 1u << (3 * U);
-    ctx->oc_n = 0;                                                 // from here on the previous result is gone
-    if (!ctx->oc_host) VP_HIP(hipHostMalloc((void**)&ctx->oc_host, kSumWords * sizeof(uint32_t), hipHostMallocDefault));
-    VP_TRY(reserve(ctx, ctx->oc_sum, kSumWords * 4, false));
-    uint32_t* sum = (uint32_t*)ctx->oc_sum.ptr;
+    ctx->oc.n = 0;                                                 // from here on the previous result is gone
+    VP_TRY(ctx->oc.host.need(kSumWords));
+    VP_TRY(reserve(ctx, ctx->oc.sum, kSumWords * 4, false));
+    uint32_t* sum = (uint32_t*)ctx->oc.sum.ptr;
     const uint32_t top = algo == VP_ALGO_NAIVE ? L - 1u : U;       // the levels 0 .. top have state bytes
-    VP_TRY(reserve(ctx, ctx->oc_state, level_start(top + 1), false));
-    VP_TRY(reserve(ctx, ctx->oc_rank, std::max<size_t>(level_start(algo == VP_ALGO_NAIVE ? L : U), 1) * 4, false));
-    uint8_t* state = (uint8_t*)ctx->oc_state.ptr;
-    uint32_t* rank = (uint32_t*)ctx->oc_rank.ptr;
+    VP_TRY(reserve(ctx, ctx->oc.state, level_start(top + 1), false));
+    VP_TRY(reserve(ctx, ctx->oc.rank, std::max<size_t>(level_start(algo == VP_ALGO_NAIVE ? L : U), 1) * 4, false));
+    uint8_t* state = (uint8_t*)ctx->oc.state.ptr;
+    uint32_t* rank = (uint32_t*)ctx->oc.rank.ptr;
     uint32_t *cnt = nullptr, *flb = nullptr, *off = nullptr;
     VP_HIP(hipMemsetAsync(sum, 0, kSumWords * 4, st));
     auto cells_of = [](uint32_t l) { return (size_t)1 << (3 * l); };
@@ -441,8 +441,8 @@ int launch_octree(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int algo
                                rank + level_start(l), sum + 2 * kSlots + l);
         hipLaunchKernelGGL(oc_offsets, dim3(1), dim3(64), 0, st, sum, L);
     } else {
-        VP_TRY(reserve(ctx, ctx->oc_cnt, (size_t)nb * 15 * 4, false));
-        cnt = (uint32_t*)ctx->oc_cnt.ptr; flb = cnt + 5 * (size_t)nb; off = flb + 5 * (size_t)nb;
+        VP_TRY(reserve(ctx, ctx->oc.cnt, (size_t)nb * 15 * 4, false));
+        cnt = (uint32_t*)ctx->oc.cnt.ptr; flb = cnt + 5 * (size_t)nb; off = flb + 5 * (size_t)nb;
         {
             ProfScope p(ctx, VP_K_MD_COUNT);
             hipLaunchKernelGGL(oc_block<false>, dim3(nb), dim3(256), 0, st, d_words, n, L, nb, cnt, flb, state + level_start(U),
@@ -453,11 +453,11 @@ int launch_octree(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int algo
         hipLaunchKernelGGL(oc_upper, dim3(1), dim3(1024), 0, st, L, nb, (const uint32_t*)cnt, (const uint32_t*)flb, off, state, rank, sum);
     }
     VP_HIP(hipGetLastError());
-    VP_HIP(hipMemcpyAsync(ctx->oc_host, sum, kSumWords * 4, hipMemcpyDeviceToHost, st));
+    VP_HIP(hipMemcpyAsync(ctx->oc.host, sum, kSumWords * 4, hipMemcpyDeviceToHost, st));
     VP_HIP(hipStreamSynchronize(st));
-    const uint64_t M = ctx->oc_host[kSlots - 1];
-    VP_TRY(reserve(ctx, ctx->oc_nodes, M * 8, false));
-    uint2* nodes = (uint2*)ctx->oc_nodes.ptr;
+    const uint64_t M = ctx->oc.host[kSlots - 1];
+    VP_TRY(reserve(ctx, ctx->oc.nodes, M * 8, false));
+    uint2* nodes = (uint2*)ctx->oc.nodes.ptr;
 
     {
         ProfScope p(ctx, algo == VP_ALGO_NAIVE ? VP_K_MD_NAIVE : VP_K_MD_WRITE);
@@ -474,9 +474,9 @@ int launch_octree(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, int algo
         }
     }
     VP_HIP(hipGetLastError());
-    for (int l = 0; l < kSlots; ++l) { ctx->oc_level_offset[l] = ctx->oc_host[l]; ctx->oc_full_leaves[l] = ctx->oc_host[kSlots + l]; }
-    ctx->oc_count = M;
-    ctx->oc_n = n;
+    for (int l = 0; l < kSlots; ++l) { ctx->oc.level_offset[l] = ctx->oc.host[l]; ctx->oc.full_leaves[l] = ctx->oc.host[kSlots + l]; }
+    ctx->oc.count = M;
+    ctx->oc.n = n;
     if (h_nodes) *h_nodes = M;
     return 0;
 }

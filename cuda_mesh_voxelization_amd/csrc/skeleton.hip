@@ -7,7 +7,7 @@
 //          sk_sub_naive     one lane per word of 32 voxels, global memory only: the words of the wrong y / z parity are copied, the others
 //                           examine their candidate bits one by one with the plain simple() and write the word into the OTHER grid (eight
 //                           launches: the result is back in the first).  The deleted count is read back after every iteration.
-//   TILED  sk_mark_nonempty / sk_list   the list of active blocks by count -> scan -> write: a block of 32 x 16 x 16 voxels is active when it or a
+//   TILED  sk_mark_nonempty / block_list (block_list.h)   the list of active blocks by count -> scan -> write: a block of 32 x 16 x 16 voxels is active when it or a
 //                           26-neighbour block lost a voxel in the previous iteration (every non-empty block in the first).  A block
 //                           that lost a voxel raises the flags of its 27 blocks with plain stores of 1; one workgroup scans the flags
 //                           into the list and clears them.  The list length comes back with the deleted count, so every launch has
@@ -28,18 +28,16 @@
 #include <thread>
 #include <vector>
 
+#include "block_list.h"
 #include "skeleton_simple.h"
 #include "vp_internal.h"
-#include "wg_scan.h"
 
 namespace vp {
 
 namespace {
 
-constexpr uint32_t kBlockY = 16, kBlockZ = 16;                    // a block is one word (32 voxels) x 16 x 16: one lane per word
-constexpr uint32_t kHalo = 18;                                    // staged rows per axis
-constexpr uint32_t kMaxBlocksPerThread = 128;                     // n = 1024: 32 * 64 * 64 blocks / 1024 threads
-constexpr size_t kAuxHead = 64;                                   // counters in front of the flags: deleted | active blocks | - | - | voxels left (u64)
+constexpr uint32_t kHalo = 18;                                    // staged rows per axis of a block (block_list.h: one lane per word)
+// the counters in front of the block flags (kAuxHead bytes): deleted | active blocks | - | - | voxels left (u64)
 
 // the row of word xw at (y, z) with its two x neighbours: bit 0 = voxel 32 xw - 1, bits 1 .. 32 the word, bit 33 = voxel 32 xw + 32;
 // rows and voxels outside the grid are unset
@@ -122,21 +120,6 @@ sk_mark_nonempty(const uint32_t* __restrict__ g, uint32_t n, uint32_t* __restric
     if (g[i] == 0u) return;
     const uint32_t w = n / 32, nb = n / kBlockY, xw = (uint32_t)(i % w), y = (uint32_t)((i / w) % n), z = (uint32_t)(i / ((size_t)w * n));
     flags[xw + w * (y / kBlockY + nb * (z / kBlockZ))] = 1u;
-}
-
-// one workgroup: list = the indices of the raised flags in ascending order, counters[1] = their number; the flags are cleared
-__global__ void __launch_bounds__(1024)
-sk_list(uint32_t* __restrict__ flags, uint32_t nblocks, uint32_t* __restrict__ list, uint32_t* __restrict__ counters)
-{
-    __shared__ uint32_t part[1024];
-    const uint32_t total = wg_scan_1024<uint32_t, uint32_t>(
-        part, nblocks, [&](uint32_t i) { return flags[i] ? 1u : 0u; }, [&](uint32_t i, uint32_t v) { if (flags[i]) list[v] = i; });
-    __syncthreads();
-    for (uint32_t k = 0; k < kMaxBlocksPerThread; ++k) {
-        const uint32_t i = k * 1024u + threadIdx.x;
-        if (i < nblocks) flags[i] = 0u;
-    }
-    if (threadIdx.x == 0) counters[1] = total;
 }
 
 __global__ void __launch_bounds__(256)
@@ -231,24 +214,24 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
                     uint64_t* h_stats)
 {
     hipStream_t st = ctx->stream;
-    const uint32_t n = f.n, w = n / 32, nb = n / kBlockY, nblocks = w * nb * nb;
+    const uint32_t n = f.n, nblocks = block_count(n);
     const size_t nwords = (size_t)n * n * n / 32;
     const unsigned wgs = (unsigned)(nwords / 256);
-    ctx->sk_n = 0;                                                 // from here on the previous result is gone
-    VP_TRY(reserve(ctx, ctx->sk_grid, nwords * 4, false));
-    VP_TRY(reserve(ctx, ctx->sk_border, nwords * 4, false));
-    VP_TRY(reserve(ctx, ctx->sk_aux, kAuxHead + (size_t)nblocks * 8, false));
-    if (algo == VP_ALGO_NAIVE) VP_TRY(reserve(ctx, ctx->sk_tmp, nwords * 4, false));
-    if (!ctx->sk_host) VP_HIP(hipHostMalloc((void**)&ctx->sk_host, kAuxHead, hipHostMallocDefault));
-    uint32_t* grid = (uint32_t*)ctx->sk_grid.ptr;
-    uint32_t* other = (uint32_t*)ctx->sk_tmp.ptr;
-    uint32_t* border = (uint32_t*)ctx->sk_border.ptr;
-    uint32_t* counters = (uint32_t*)ctx->sk_aux.ptr;
-    uint32_t* flags = (uint32_t*)((char*)ctx->sk_aux.ptr + kAuxHead);
+    ctx->sk.n = 0;                                                 // from here on the previous result is gone
+    VP_TRY(reserve(ctx, ctx->sk.grid, nwords * 4, false));
+    VP_TRY(reserve(ctx, ctx->sk.border, nwords * 4, false));
+    VP_TRY(reserve(ctx, ctx->sk.aux, block_aux_bytes(nblocks), false));
+    if (algo == VP_ALGO_NAIVE) VP_TRY(reserve(ctx, ctx->sk.tmp, nwords * 4, false));
+    VP_TRY(ctx->sk.host.need(kAuxHead / 8));
+    uint32_t* grid = (uint32_t*)ctx->sk.grid.ptr;
+    uint32_t* other = (uint32_t*)ctx->sk.tmp.ptr;
+    uint32_t* border = (uint32_t*)ctx->sk.border.ptr;
+    uint32_t* counters = (uint32_t*)ctx->sk.aux.ptr;
+    uint32_t* flags = block_flags(ctx->sk.aux.ptr);
     uint32_t* list = flags + nblocks;
-    volatile uint32_t* host = (volatile uint32_t*)ctx->sk_host;
+    volatile uint32_t* host = (volatile uint32_t*)ctx->sk.host.p;
 
-    VP_HIP(hipMemsetAsync(ctx->sk_aux.ptr, 0, kAuxHead + (size_t)nblocks * 4, st));
+    VP_HIP(hipMemsetAsync(ctx->sk.aux.ptr, 0, kAuxHead + (size_t)nblocks * 4, st));
     {
         ProfScope p(ctx, VP_K_SURFACE);
         VP_TRY(launch_stream_copy(ctx, grid, d_words, nwords * 4));
@@ -258,10 +241,10 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
         {
             ProfScope p(ctx, VP_K_MD_SCAN);
             hipLaunchKernelGGL(sk_mark_nonempty, dim3(wgs), dim3(256), 0, st, (const uint32_t*)grid, n, flags);
-            hipLaunchKernelGGL(sk_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters);
+            hipLaunchKernelGGL(block_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters + 1);
         }
         VP_HIP(hipGetLastError());
-        VP_HIP(hipMemcpyAsync(ctx->sk_host, counters, 8, hipMemcpyDeviceToHost, st));
+        VP_HIP(hipMemcpyAsync(ctx->sk.host, counters, 8, hipMemcpyDeviceToHost, st));
         VP_HIP(hipStreamSynchronize(st));
         active = host[1];
     }
@@ -280,7 +263,7 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
                                    (const uint32_t*)border, n, s, mode, counters);
             }
             VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->sk_host, counters, 8, hipMemcpyDeviceToHost, st));
+            VP_HIP(hipMemcpyAsync(ctx->sk.host, counters, 8, hipMemcpyDeviceToHost, st));
             VP_HIP(hipStreamSynchronize(st));
             lost = host[0];
         } else if (active) {
@@ -296,10 +279,10 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
             }
             {
                 ProfScope p(ctx, VP_K_MD_SCAN);
-                hipLaunchKernelGGL(sk_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters);
+                hipLaunchKernelGGL(block_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters + 1);
             }
             VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->sk_host, counters, 8, hipMemcpyDeviceToHost, st));
+            VP_HIP(hipMemcpyAsync(ctx->sk.host, counters, 8, hipMemcpyDeviceToHost, st));
             VP_HIP(hipStreamSynchronize(st));
             lost = host[0];
             active = host[1];
@@ -314,13 +297,13 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
         hipLaunchKernelGGL(sk_count, dim3(wgs), dim3(256), 0, st, (const uint32_t*)grid, (unsigned long long*)(counters + 4));
     }
     VP_HIP(hipGetLastError());
-    VP_HIP(hipMemcpyAsync(ctx->sk_host + 2, counters + 4, 8, hipMemcpyDeviceToHost, st));
+    VP_HIP(hipMemcpyAsync(ctx->sk.host + 2, counters + 4, 8, hipMemcpyDeviceToHost, st));
     VP_HIP(hipStreamSynchronize(st));
-    ctx->sk_stats[0] = ctx->sk_host[2];
-    ctx->sk_stats[1] = iterations;
-    ctx->sk_stats[2] = deleted;
-    if (h_stats) std::copy(ctx->sk_stats, ctx->sk_stats + 3, h_stats);
-    ctx->sk_n = n;
+    ctx->sk.stats[0] = ctx->sk.host[2];
+    ctx->sk.stats[1] = iterations;
+    ctx->sk.stats[2] = deleted;
+    if (h_stats) std::copy(ctx->sk.stats, ctx->sk.stats + 3, h_stats);
+    ctx->sk.n = n;
     return 0;
 }
 

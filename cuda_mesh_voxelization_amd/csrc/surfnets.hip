@@ -314,13 +314,13 @@ int launch_surfnets_count(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int 
     const Dim d = make_dim(n);
     const size_t units = unit_count(d, algo);
     const size_t blocks = (units + kBlock - 1) / kBlock;
-    ctx->sn_words = nullptr;
-    VP_TRY(reserve(ctx, ctx->sn_cnt, blocks * 8));
-    VP_TRY(reserve(ctx, ctx->sn_off, (blocks + 1) * 16));
-    if (algo == VP_ALGO_TILED) VP_TRY(reserve(ctx, ctx->sn_rank, units * 8));          // bits, then the per-word exclusive counts
-    uint32_t* cnt_v = (uint32_t*)ctx->sn_cnt.ptr;
+    ctx->sn.words = nullptr;
+    VP_TRY(reserve(ctx, ctx->sn.cnt, blocks * 8));
+    VP_TRY(reserve(ctx, ctx->sn.off, (blocks + 1) * 16));
+    if (algo == VP_ALGO_TILED) VP_TRY(reserve(ctx, ctx->sn.rank, units * 8));          // bits, then the per-word exclusive counts
+    uint32_t* cnt_v = (uint32_t*)ctx->sn.cnt.ptr;
     uint32_t* cnt_q = cnt_v + blocks;
-    unsigned long long* off_v = (unsigned long long*)ctx->sn_off.ptr;
+    unsigned long long* off_v = (unsigned long long*)ctx->sn.off.ptr;
     unsigned long long* off_q = off_v + blocks + 1;
     {
         ProfScope p(ctx, algo == VP_ALGO_NAIVE ? VP_K_SN_CELLS_NAIVE : VP_K_SN_CELLS);
@@ -328,7 +328,7 @@ int launch_surfnets_count(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int 
             hipLaunchKernelGGL(sn_count_naive, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, d, d_words, (uint32_t)units, cnt_v, cnt_q);
         else
             hipLaunchKernelGGL(sn_count_tiled, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, d, d_words, (uint32_t)units,
-                               (uint32_t*)ctx->sn_rank.ptr, cnt_v, cnt_q);
+                               (uint32_t*)ctx->sn.rank.ptr, cnt_v, cnt_q);
     }
     {
         ProfScope p(ctx, VP_K_SN_SCAN);
@@ -339,7 +339,7 @@ int launch_surfnets_count(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int 
     VP_HIP(hipMemcpyAsync(&totals[0], off_v + blocks, 8, hipMemcpyDeviceToHost, ctx->stream));
     VP_HIP(hipMemcpyAsync(&totals[1], off_q + blocks, 8, hipMemcpyDeviceToHost, ctx->stream));
     VP_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->sn_words = d_words; ctx->sn_n = n; ctx->sn_algo = algo; ctx->sn_vertices = totals[0]; ctx->sn_quads = totals[1];
+    ctx->sn.words = d_words; ctx->sn.n = n; ctx->sn.algo = algo; ctx->sn.vertices = totals[0]; ctx->sn.quads = totals[1];
     if (h_vertices) *h_vertices = totals[0];
     if (h_quads) *h_quads = totals[1];
     return 0;
@@ -351,18 +351,18 @@ int launch_surfnets_write(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, int 
     const Dim d = make_dim(n);
     const size_t units = unit_count(d, algo);
     const size_t blocks = (units + kBlock - 1) / kBlock;
-    const size_t nv = (size_t)ctx->sn_vertices, nq = (size_t)ctx->sn_quads;
+    const size_t nv = (size_t)ctx->sn.vertices, nq = (size_t)ctx->sn.quads;
     if (nv == 0) return 0;                                                // no vertex, hence no quad
     const bool naive = algo == VP_ALGO_NAIVE;
     // the buffers below may regrow: that frees nothing the count left behind (sn_off, and the bits at the front of sn_rank, which the
     // count already reserved at full size)
-    if (naive) VP_TRY(reserve(ctx, ctx->sn_rank, units * 4, false));      // vertex-index volume, 4 (n+1)^3 bytes
-    if (iterations) VP_TRY(reserve(ctx, ctx->sn_xyz, nv * 12));
-    const unsigned long long* off_v = (const unsigned long long*)ctx->sn_off.ptr;
+    if (naive) VP_TRY(reserve(ctx, ctx->sn.rank, units * 4, false));      // vertex-index volume, 4 (n+1)^3 bytes
+    if (iterations) VP_TRY(reserve(ctx, ctx->sn.xyz, nv * 12));
+    const unsigned long long* off_v = (const unsigned long long*)ctx->sn.off.ptr;
     const unsigned long long* off_q = off_v + blocks + 1;
-    uint32_t* rank0 = (uint32_t*)ctx->sn_rank.ptr;                        // NAIVE: index volume; TILED: bits
+    uint32_t* rank0 = (uint32_t*)ctx->sn.rank.ptr;                        // NAIVE: index volume; TILED: bits
     uint32_t* prefix = naive ? nullptr : rank0 + units;
-    float* other = (float*)ctx->sn_xyz.ptr;
+    float* other = (float*)ctx->sn.xyz.ptr;
     float* cur = (iterations & 1u) ? other : d_xyz;                       // the result ends in d_xyz for any iteration count
     {
         ProfScope p(ctx, naive ? VP_K_SN_VERTS_NAIVE : VP_K_SN_VERTS);

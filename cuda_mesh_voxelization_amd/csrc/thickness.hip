@@ -228,22 +228,22 @@ int launch_thickness(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint3
     hipStream_t st = ctx->stream;
     const uint32_t n = f.n, nb = n / 8, nbricks = nb * nb * nb, rmax2 = rmax * rmax;
     const size_t nvox = (size_t)n * n * n;
-    ctx->th_n = 0;                                                 // from here on the previous result is gone
-    VP_TRY(reserve(ctx, ctx->th_t2, nvox * 4, false));
-    VP_TRY(reserve(ctx, ctx->th_thin, nvox / 8, false));
-    VP_TRY(reserve(ctx, ctx->edt_vol, nvox * 4, false));
-    if (algo == VP_ALGO_NAIVE) VP_TRY(reserve(ctx, ctx->edt_vol2, nvox * 4, false));
+    ctx->th.n = 0;                                                 // from here on the previous result is gone
+    VP_TRY(reserve(ctx, ctx->th.t2, nvox * 4, false));
+    VP_TRY(reserve(ctx, ctx->th.thin, nvox / 8, false));
+    VP_TRY(reserve(ctx, ctx->edt.vol, nvox * 4, false));
+    if (algo == VP_ALGO_NAIVE) VP_TRY(reserve(ctx, ctx->edt.vol2, nvox * 4, false));
     else {
-        VP_TRY(reserve(ctx, ctx->th_d16, nvox * 2, false));
-        VP_TRY(reserve(ctx, ctx->th_sat, nvox / 4, false));          // the saturated centres, then the saturated region
+        VP_TRY(reserve(ctx, ctx->th.d16, nvox * 2, false));
+        VP_TRY(reserve(ctx, ctx->th.sat, nvox / 4, false));          // the saturated centres, then the saturated region
     }
-    VP_TRY(reserve(ctx, ctx->th_sum, 16 + (size_t)nbricks * 8, false));  // the thin count | per brick: the largest unsaturated D | owned
-    if (h_thin_count && !ctx->th_host) VP_HIP(hipHostMalloc((void**)&ctx->th_host, sizeof(uint64_t), hipHostMallocDefault));
-    uint32_t* E = (uint32_t*)ctx->edt_vol.ptr;
-    uint32_t* T2 = (uint32_t*)ctx->th_t2.ptr;
-    uint32_t* thin = (uint32_t*)ctx->th_thin.ptr;
-    unsigned long long* counter = (unsigned long long*)ctx->th_sum.ptr;
-    uint32_t* umax = (uint32_t*)((char*)ctx->th_sum.ptr + 16);
+    VP_TRY(reserve(ctx, ctx->th.sum, 16 + (size_t)nbricks * 8, false));  // the thin count | per brick: the largest unsaturated D | owned
+    if (h_thin_count) VP_TRY(ctx->th.host.need(1));
+    uint32_t* E = (uint32_t*)ctx->edt.vol.ptr;
+    uint32_t* T2 = (uint32_t*)ctx->th.t2.ptr;
+    uint32_t* thin = (uint32_t*)ctx->th.thin.ptr;
+    unsigned long long* counter = (unsigned long long*)ctx->th.sum.ptr;
+    uint32_t* umax = (uint32_t*)((char*)ctx->th.sum.ptr + 16);
     uint32_t* own = umax + nbricks;
 
     if (algo == VP_ALGO_NAIVE) {
@@ -256,8 +256,8 @@ int launch_thickness(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint3
         ProfScope p(ctx, VP_K_EDT_THRESH);
         hipLaunchKernelGGL(th_thin_naive, dim3((unsigned)(nvox / 256)), dim3(256), 0, st, (const uint32_t*)T2, thin, thin2);
     } else {
-        uint16_t* D16 = (uint16_t*)ctx->th_d16.ptr;
-        uint32_t* satc = (uint32_t*)ctx->th_sat.ptr;
+        uint16_t* D16 = (uint16_t*)ctx->th.d16.ptr;
+        uint32_t* satc = (uint32_t*)ctx->th.sat.ptr;
         uint32_t* sat = satc + nvox / 32;
         VP_TRY(launch_edt(ctx, f, d_words, VP_EDT_SEEDS_UNSET, E, algo));
         {
@@ -286,11 +286,11 @@ int launch_thickness(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, uint3
                                (const uint32_t*)thin, nvox / 32, counter);
         }
         VP_HIP(hipGetLastError());
-        VP_HIP(hipMemcpyAsync(ctx->th_host, counter, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        VP_HIP(hipMemcpyAsync(ctx->th.host, counter, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         VP_HIP(hipStreamSynchronize(st));
-        *h_thin_count = *ctx->th_host;
+        *h_thin_count = *ctx->th.host;
     }
-    ctx->th_n = n;
+    ctx->th.n = n;
     return 0;
 }
 

@@ -445,8 +445,8 @@ int launch_voxelize(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float*
     // toggle grid: the output itself, or a scratch grid when the result is XORed into existing content
     uint32_t* tog = d_words;
     if (accumulate) {
-        VP_TRY(reserve(ctx, ctx->scratch, nwords * 4));
-        tog = (uint32_t*)ctx->scratch.ptr;
+        VP_TRY(reserve(ctx, ctx->vox.scratch, nwords * 4));
+        tog = (uint32_t*)ctx->vox.scratch.ptr;
     }
     // nwords is a multiple of 8 n (n % 32 == 0): whole uint4s; d_words is 16-byte aligned (checked at the ABI), the scratch grid is ours
     auto zero = [&](uint32_t* cnt, uint32_t ncnt) {
@@ -474,22 +474,22 @@ int launch_voxelize(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float*
     // the device and leave at once when there is nothing to do.  No read-back, no stream synchronisation in steady state.
     const uint32_t tilesY = f.n / kTile;
     const uint32_t numTiles = tilesY * (uint32_t)(nz / kTile);
-    VP_TRY(reserve(ctx, ctx->tile_cnt, ((size_t)numTiles + 1) * 4));
-    VP_TRY(reserve(ctx, ctx->tile_off, ((size_t)numTiles + 1) * 4));
-    VP_TRY(reserve(ctx, ctx->tile_cur, (size_t)numTiles * 4));
-    uint32_t* cnt = (uint32_t*)ctx->tile_cnt.ptr;
-    uint32_t* off = (uint32_t*)ctx->tile_off.ptr;
-    uint32_t* cur = (uint32_t*)ctx->tile_cur.ptr;
+    VP_TRY(reserve(ctx, ctx->vox.tile_cnt, ((size_t)numTiles + 1) * 4));
+    VP_TRY(reserve(ctx, ctx->vox.tile_off, ((size_t)numTiles + 1) * 4));
+    VP_TRY(reserve(ctx, ctx->vox.tile_cur, (size_t)numTiles * 4));
+    uint32_t* cnt = (uint32_t*)ctx->vox.tile_cnt.ptr;
+    uint32_t* off = (uint32_t*)ctx->vox.tile_off.ptr;
+    uint32_t* cur = (uint32_t*)ctx->vox.tile_cur.ptr;
     uint32_t* d_nbig = cnt + numTiles;                             // one extra counter after the tile histogram
     if (ntris) {
         // work-queue size and large-triangle count of the previous call, if their copies have landed (never waited for)
-        if (ctx->vox_total_event && ctx->vox_total_pending && hipEventQuery(ctx->vox_total_event) == hipSuccess) {
-            ctx->vox_total_pending = false;
-            ctx->vox_total_seen = std::max<uint64_t>(ctx->vox_total_seen, ctx->vox_total_host[0]);
-            ctx->vox_nbig_seen = std::max<uint64_t>(ctx->vox_nbig_seen, ctx->vox_total_host[1]);
-            ctx->vox_counts_known = true;
-            if (ctx->vox_total_host[1] == 0) ctx->vox_nolist_job = ctx->vox_pending_job;          // that job has no large triangle
-            else if (ctx->vox_nolist_job == ctx->vox_pending_job) ctx->vox_nolist_job = vp_ctx::VoxJob{};
+        if (ctx->vox.total_event && ctx->vox.total_pending && hipEventQuery(ctx->vox.total_event) == hipSuccess) {
+            ctx->vox.total_pending = false;
+            ctx->vox.total_seen = std::max<uint64_t>(ctx->vox.total_seen, ctx->vox.total_host[0]);
+            ctx->vox.nbig_seen = std::max<uint64_t>(ctx->vox.nbig_seen, ctx->vox.total_host[1]);
+            ctx->vox.counts_known = true;
+            if (ctx->vox.total_host[1] == 0) ctx->vox.nolist_job = ctx->vox.pending_job;          // that job has no large triangle
+            else if (ctx->vox.nolist_job == ctx->vox.pending_job) ctx->vox.nolist_job = vp_ctx::VoxJob{};
         }
         const vp_ctx::VoxJob job{d_tri, ntris, f.n, f.z0, f.z1};
         // A job whose large-triangle count came back as zero (a fine mesh, like the benchmark's) and that is repeated -- the same triangle
@@ -498,19 +498,19 @@ int launch_voxelize(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float*
         // mesh walked triangle by triangle in vox_setup would cost milliseconds per triangle).  Should the buffer have been refilled in place
         // with large triangles, vox_setup walks them in place (slow for that one call, correct: the path of a full record list), the count
         // comes back non-zero and the job takes the tile stage again.
-        const bool noLists = ctx->vox_nolist_job == job && ctx->vox_nolist_job.tri != nullptr;
-        const size_t want = std::max<size_t>((size_t)1 << 20, (size_t)ctx->vox_total_seen + ctx->vox_total_seen / 4);
-        VP_TRY(reserve(ctx, ctx->pairs, want * 4));
+        const bool noLists = ctx->vox.nolist_job == job && ctx->vox.nolist_job.tri != nullptr;
+        const size_t want = std::max<size_t>((size_t)1 << 20, (size_t)ctx->vox.total_seen + ctx->vox.total_seen / 4);
+        VP_TRY(reserve(ctx, ctx->vox.pairs, want * 4));
         // record list: 64 Ki records (5 MiB) or what earlier calls needed + 25 %, never more than one per triangle
-        const size_t wantRec = std::min<size_t>(ntris, std::max<size_t>((size_t)1 << 16, (size_t)ctx->vox_nbig_seen + ctx->vox_nbig_seen / 4));
-        VP_TRY(reserve(ctx, ctx->rec, wantRec * (size_t)kRecDwords * 4));
-        uint4* rec = (uint4*)ctx->rec.ptr;
-        uint32_t rcap = noLists ? 0u : (uint32_t)std::min<size_t>(ctx->rec.bytes / ((size_t)kRecDwords * 4), ntris);
+        const size_t wantRec = std::min<size_t>(ntris, std::max<size_t>((size_t)1 << 16, (size_t)ctx->vox.nbig_seen + ctx->vox.nbig_seen / 4));
+        VP_TRY(reserve(ctx, ctx->vox.rec, wantRec * (size_t)kRecDwords * 4));
+        uint4* rec = (uint4*)ctx->vox.rec.ptr;
+        uint32_t rcap = noLists ? 0u : (uint32_t)std::min<size_t>(ctx->vox.rec.bytes / ((size_t)kRecDwords * 4), ntris);
 #ifdef VP_TEST_HOOKS   // test builds only (libvphip_hooks.so): force the walk-in-place path
         if (const char* e = getenv("VP_VOX_REC_CAP")) rcap = std::min<uint32_t>(rcap, (uint32_t)strtoul(e, nullptr, 10));
 #endif
-        uint32_t* pairs = (uint32_t*)ctx->pairs.ptr;
-        uint32_t pcap = (uint32_t)std::min<size_t>(ctx->pairs.bytes / 4, 0xFFFFFFFFu);
+        uint32_t* pairs = (uint32_t*)ctx->vox.pairs.ptr;
+        uint32_t pcap = (uint32_t)std::min<size_t>(ctx->vox.pairs.bytes / 4, 0xFFFFFFFFu);
 #ifdef VP_TEST_HOOKS   // ... and the work-queue overflow path
         if (const char* e = getenv("VP_VOX_QUEUE_CAP")) pcap = std::min<uint32_t>(pcap, (uint32_t)strtoul(e, nullptr, 10));
 #endif
@@ -524,17 +524,14 @@ int launch_voxelize(vp_ctx* ctx, const Frame& f, uint32_t* d_words, const float*
             ProfScope p(ctx, VP_K_VOX_SCAN);
             hipLaunchKernelGGL(vox_scan, dim3(1), dim3(1024), 0, st, cnt, numTiles, off, cur);
         }
-        if (!ctx->vox_total_host) {
-            VP_HIP(hipHostMalloc((void**)&ctx->vox_total_host, 2 * sizeof(uint32_t), hipHostMallocDefault));
-            ctx->vox_total_host[0] = ctx->vox_total_host[1] = 0;
-            VP_HIP(hipEventCreateWithFlags(&ctx->vox_total_event, hipEventDisableTiming));
-        }
-        if (!ctx->vox_total_pending) {                             // lazily: the next call may grow the queue from it
-            if (!noLists) VP_HIP(hipMemcpyAsync(ctx->vox_total_host, off + numTiles, 4, hipMemcpyDeviceToHost, st));   // (no scan: the old figure stays)
-            VP_HIP(hipMemcpyAsync(ctx->vox_total_host + 1, d_nbig, 4, hipMemcpyDeviceToHost, st));
-            VP_HIP(hipEventRecord(ctx->vox_total_event, st));
-            ctx->vox_total_pending = true;
-            ctx->vox_pending_job = job;
+        VP_TRY(ctx->vox.total_host.need(2, true));
+        if (!ctx->vox.total_event) VP_HIP(hipEventCreateWithFlags(&ctx->vox.total_event, hipEventDisableTiming));
+        if (!ctx->vox.total_pending) {                             // lazily: the next call may grow the queue from it
+            if (!noLists) VP_HIP(hipMemcpyAsync(ctx->vox.total_host, off + numTiles, 4, hipMemcpyDeviceToHost, st));   // (no scan: the old figure stays)
+            VP_HIP(hipMemcpyAsync(ctx->vox.total_host + 1, d_nbig, 4, hipMemcpyDeviceToHost, st));
+            VP_HIP(hipEventRecord(ctx->vox.total_event, st));
+            ctx->vox.total_pending = true;
+            ctx->vox.pending_job = job;
         }
         if (!noLists) {
             ProfScope p(ctx, VP_K_VOX_SCATTER);

@@ -1,7 +1,9 @@
-// vp_internal.h -- shared declarations of libvphip.so (not part of the public ABI).
+// vp_internal.h -- shared declarations of libvphip.so (not part of the public ABI): the context, whose state is one small struct per
+// feature (each names its device buffers once), the error macros and the stage launchers.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -32,150 +34,6 @@ inline Frame make_frame(const vp_frame* f)
     return r;
 }
 
-struct ProfSpan { int kernel; hipEvent_t a, b; };
-
-struct Buffer {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-};
-
-}  // namespace vp
-
-struct vp_ctx {
-    int device = 0;
-    int cus = 256;                             // compute units of the device (workgroup slots = cus x workgroups per CU)
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    // grow-only workspaces
-    vp::Buffer rec, tile_cnt, tile_off, tile_cur, pairs, scratch, none_row;
-    vp::Buffer jfa_work;                       // vp_jfa* with d_work = NULL: two id volumes + border mask
-    // what the last vp_jfa_start left in its workspace, so that vp_jfa_run can refuse anything else (a run on a workspace that
-    // holds init ids where it expects a border mask, or nothing at all, would produce an sdf from stale memory)
-    struct JfaStarted {
-        bool valid = false;
-        bool mask = false;                     // border mask behind the two id volumes (fast sequence) / init ids in the first volume
-        uint32_t n = 0;
-        int algo = 0;
-        const void* work = nullptr;
-        size_t work_bytes = 0;
-        const uint32_t* words = nullptr;
-    } jfa_started;
-    // the tile-kernel launches of the most recent pass call (jfa_dense.hip, launch_tile; vp_jfa_last_shapes): a pass whose chains are
-    // split makes two, so four is room enough; a host-side note, no device work
-    vp_jfa_shape dense_shapes[4];
-    int dense_shape_count = 0;
-    vp::Buffer slots[VP_WORKSPACE_SLOTS];      // vp_ctx_workspace
-    // vp_extract_*: block counts / offsets of the last count call and what it was for
-    vp::Buffer ext_cnt, ext_off;
-    const uint32_t* ext_words = nullptr;
-    int ext_mode = -1;
-    uint32_t ext_n = 0;
-    uint64_t ext_total = 0;
-    // voxelizer: work-queue size of an earlier call, copied back lazily (never waited for) to size the next call's queue
-    uint32_t* vox_total_host = nullptr;
-    hipEvent_t vox_total_event = nullptr;
-    bool vox_total_pending = false;
-    uint64_t vox_total_seen = 0;
-    uint64_t vox_nbig_seen = 0;                // large triangles an earlier call counted (sizes the record list)
-    bool vox_counts_known = false;             // at least one such count has come back
-    // the job (triangle buffer, count, grid side, slab) whose large-triangle count last came back as ZERO: only that very job leaves the
-    // list kernels out (ADVICE r05: a coarse mesh that follows a fine one on the same context must not be walked triangle by triangle)
-    struct VoxJob { const void* tri = nullptr; size_t ntris = 0; uint32_t n = 0, z0 = 0, z1 = 0;
-                    bool operator==(const VoxJob& o) const { return tri == o.tri && ntris == o.ntris && n == o.n && z0 == o.z0 && z1 == o.z1; } };
-    VoxJob vox_pending_job, vox_nolist_job;
-    // conservative voxelizer (cvox.hip): its own large-triangle counter, record list and row scan, and its own lazily copied count
-    vp::Buffer cvox_cnt, cvox_rec, cvox_base;
-    uint32_t* cvox_host = nullptr;
-    hipEvent_t cvox_event = nullptr;
-    bool cvox_pending = false;
-    uint64_t cvox_nbig_seen = 0;
-    // interior fill (fill.hip): the ring of round flags (two batches) and its pinned host copy of one batch
-    vp::Buffer fill_flags;
-    uint32_t* fill_host = nullptr;
-    // ball morphology (morph.hip): the row tables of every radius (uploaded by the first tiled call) and the intermediate grid of open / close
-    vp::Buffer morph_tab, morph_tmp;
-    // connected components (components.hip): root counts per block of voxels and their scan; for vp_components_filter the label volume
-    // (4 n^3 bytes, freed by vp_ctx_release), the sizes and keep flags of the K components, the arg-max winners and the kept count;
-    // the pinned host words K and kept are read back through
-    vp::Buffer comp_cnt, comp_off, comp_labels, comp_sizes, comp_keep, comp_small;
-    uint64_t* comp_host = nullptr;
-    // surface nets (surfnets.hip): block counts of vertices and quads and their scans; the rank lookup -- NAIVE: the vertex-index volume,
-    // 4 (n+1)^3 bytes; TILED: active-cell bits + one exclusive count per word, about n^3/4 bytes -- and the second position buffer of the
-    // relaxation (sn_rank and sn_xyz are freed by vp_ctx_release); what the last vp_surfnets_count was for
-    vp::Buffer sn_cnt, sn_off, sn_rank, sn_xyz;
-    const uint32_t* sn_words = nullptr;
-    uint32_t sn_n = 0;
-    int sn_algo = 0;
-    uint64_t sn_vertices = 0, sn_quads = 0;
-    // exact distance transform (edt.hip): the border mask of SEEDS_BORDER, the distance volume of vp_edt_morph, the second volume of the NAIVE
-    // column passes (4 n^3 bytes each) and the intermediate grid of open / close; all four are freed by vp_ctx_release
-    vp::Buffer edt_mask, edt_vol, edt_vol2, edt_tmp;
-    // mesh distance (meshdist.hip): NAIVE's key volume (8 n^3 bytes), the triangle records and their row scan, the brick counts (+ write
-    // cursors and plane sums) and offsets, the brick lists; the pinned host words the plane sums are read back through and the list
-    // length of the last TILED call (vp_mesh_distance_stats); the six buffers are freed by vp_ctx_release
-    vp::Buffer md_keys, md_rec, md_base, md_cnt, md_off, md_list;
-    uint64_t* md_host = nullptr;
-    uint64_t md_last_total = 0;
-    // profiling
-    bool prof_on = false;
-    uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
-    std::vector<vp::ProfSpan> prof_pending;
-    std::vector<hipEvent_t> prof_pool;
-    double prof_ms[VP_K_ALL] = {};
-    uint64_t prof_n[VP_K_ALL] = {};
-    // iso-surface nets (isonets.hip): the inside grid of the field (n^3 / 8 bytes) and the mesh of the last vp_isonets, which the context
-    // owns and vp_isonets_result hands out -- records, positions, normals (if asked for), quads; all five are freed by vp_ctx_release
-    vp::Buffer iso_words, iso_cells, iso_xyz, iso_normals, iso_quads;
-    uint64_t iso_vertices = 0, iso_quad_count = 0;
-    bool iso_has_normals = false;
-    // generalized winding number (winding.hip): the result of the last vp_winding, which the context owns and vp_winding_result hands out
-    // -- the field w (4 n^3 bytes) and its inside grid (n^3 / 8 bytes) -- the triangle records sorted by leaf (48 B each) and the pyramid
-    // (counts, boxes, area sums, node records, leaf offsets, leaf keys); the pinned host word the inside count comes back through;
-    // wn_n = the side of the grid the result is for, 0: none.  The four buffers are freed by vp_ctx_release
-    vp::Buffer wn_w, wn_inside, wn_rec, wn_tree;
-    uint64_t* wn_host = nullptr;
-    uint32_t wn_n = 0;
-    // local thickness (thickness.hip): the result of the last vp_thickness, which the context owns and vp_thickness_result hands out -- T2
-    // (4 n^3 bytes) and the thin grid (n^3 / 8 bytes) -- TILED's capped radii as uint16 (2 n^3 bytes), the grids of the saturated centres and
-    // of the saturated region (n^3 / 8 bytes each) and the thin count with the per-brick summaries; the pinned host word the count comes
-    // back through; th_n = the side of the grid the result is for, 0: none.  The five buffers are freed by vp_ctx_release (the distance
-    // volumes are edt_vol / edt_vol2)
-    vp::Buffer th_t2, th_thin, th_d16, th_sat, th_sum;
-    uint64_t* th_host = nullptr;
-    uint32_t th_n = 0;
-    // sparse voxel octree (octree.hip): the nodes of the last vp_octree (8 bytes each, sized from the count), which the context owns and
-    // vp_octree_result hands out; the device summary (level_offset | full_leaves | nodes per level), the state bytes and ranks of the levels
-    // (NAIVE: all of them; TILED: those above the 32^3 blocks) and TILED's per-block counts and offsets; the pinned host words the summary
-    // comes back through and its copy; oc_n = the side of the grid the result is for, 0: none.  The five buffers are freed by vp_ctx_release
-    vp::Buffer oc_nodes, oc_sum, oc_state, oc_rank, oc_cnt;
-    // the grid of the last vp_octree_expand (n^3 / 8 bytes), which the context owns and vp_octree_expand_result hands out; oc_grid_n = its
-    // side, 0: none.  Freed by vp_ctx_release
-    vp::Buffer oc_grid;
-    uint32_t oc_grid_n = 0;
-    uint32_t* oc_host = nullptr;
-    uint32_t oc_n = 0;
-    uint64_t oc_count = 0;
-    uint32_t oc_level_offset[11] = {}, oc_full_leaves[11] = {};
-    // topological thinning (skeleton.hip): the grid of the last vp_skeleton (n^3 / 8 bytes), which the context owns and vp_skeleton_result
-    // hands out, and its three statistics; NAIVE's second grid, the border words of the current iteration (n^3 / 8 bytes each) and the
-    // counters with TILED's block flags and list of active blocks (8 bytes per block of 32 x 16 x 16 voxels); the pinned host words the
-    // counters come back through; sk_n = the side of the grid the result is for, 0: none.  The four buffers are freed by vp_ctx_release
-    vp::Buffer sk_grid, sk_tmp, sk_border, sk_aux;
-    uint64_t* sk_host = nullptr;
-    uint64_t sk_stats[3] = {};
-    uint32_t sk_n = 0;
-    // geodesic distance (geodesic.hip): D (4 n^3 bytes) and the reach grid (n^3 / 8 bytes) of the last vp_geodesic, which the context owns
-    // and vp_geodesic_result hands out, and its four statistics; the counters with TILED's block flags and list of active blocks (8 bytes
-    // per block of 32 x 16 x 16 voxels) or NAIVE's ring of round flags; the pinned host words they come back through; gd_n = the side the
-    // result is for, 0: none.  The three buffers are freed by vp_ctx_release
-    vp::Buffer gd_dist, gd_reach, gd_aux;
-    uint64_t* gd_host = nullptr;
-    uint64_t gd_stats[4] = {};
-    uint32_t gd_n = 0;
-};
-
-namespace vp {
-
 int set_error(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
@@ -190,6 +48,231 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
         int rc_ = (call);            \
         if (rc_ != 0) return rc_;    \
     } while (0)
+
+struct ProfSpan { int kernel; hipEvent_t a, b; };
+
+struct Buffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+};
+
+// Pinned host words that device counts are copied back through: allocated by the first need(), used like the pointer, freed with the
+// context.  The only place that allocates or frees pinned host memory.
+template <typename T>
+struct HostWords {
+    T* p = nullptr;
+    HostWords() = default;
+    HostWords(const HostWords&) = delete;
+    HostWords& operator=(const HostWords&) = delete;
+    ~HostWords() { if (p) (void)hipHostFree(p); }
+    int need(size_t count, bool zeroed = false)
+    {
+        if (p) return 0;
+        VP_HIP(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault));
+        if (zeroed) std::fill(p, p + count, T(0));
+        return 0;
+    }
+    operator T*() const { return p; }
+};
+
+// What the state of one feature offers the context.  A feature names each of its device buffers ONCE, in VP_BUFFERS(released, ...) --
+// freed by vp_ctx_release and by vp_ctx_destroy -- or VP_BUFFERS(kept, ...) -- freed by vp_ctx_destroy alone: the macro declares them
+// and the member released(f) / kept(f) that enumerates them.  forget() puts the feature back into its "no result, no record" state
+// (vp_ctx_release).  A new feature adds its struct to vp_ctx and its name to each_feature: nothing else frees, releases or resets it.
+struct Feature {
+    template <typename F> void released(F) {}
+    template <typename F> void kept(F) {}
+    void forget() {}
+};
+#define VP_BUFFERS(WHEN, ...) vp::Buffer __VA_ARGS__; template <typename F> void WHEN(F f) { vp::each(f, __VA_ARGS__); }
+template <typename F, typename... B> void each(F& f, B&... b) { (f(b), ...); }
+// the result of a feature that the context owns: n = the side of the grid it is for, 0: none
+struct OwnedResult : Feature {
+    uint32_t n = 0;
+    void forget() { n = 0; }
+};
+
+}  // namespace vp
+
+struct vp_ctx {
+    using Buffer = vp::Buffer;
+    int device = 0;
+    int cus = 256;                             // compute units of the device (workgroup slots = cus x workgroups per CU)
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    // the tile-kernel launches of the most recent pass call (jfa_dense.hip, launch_tile; vp_jfa_last_shapes): a pass whose chains are
+    // split makes two, so four is room enough; a host-side note, no device work
+    vp_jfa_shape dense_shapes[4];
+    int dense_shape_count = 0;
+    // profiling
+    bool prof_on = false;
+    uint64_t prof_mask = ~0ull;                                    // timing keys that get events (vp_prof_select)
+    std::vector<vp::ProfSpan> prof_pending;
+    std::vector<hipEvent_t> prof_pool;
+    double prof_ms[VP_K_ALL] = {};
+    uint64_t prof_n[VP_K_ALL] = {};
+
+    // vp_ctx_workspace: the slots
+    struct Workspace : vp::Feature {
+        Buffer slots[VP_WORKSPACE_SLOTS];
+        template <typename F> void released(F f) { for (Buffer& b : slots) f(b); }
+    } ws;
+    // the job (triangle buffer, count, grid side, slab) whose large-triangle count last came back as ZERO: only that very job leaves the
+    // list kernels out (ADVICE r05: a coarse mesh that follows a fine one on the same context must not be walked triangle by triangle)
+    struct VoxJob { const void* tri = nullptr; size_t ntris = 0; uint32_t n = 0, z0 = 0, z1 = 0;
+                    bool operator==(const VoxJob& o) const { return tri == o.tri && ntris == o.ntris && n == o.n && z0 == o.z0 && z1 == o.z1; } };
+    // voxelizer (vox.hip): its grow-only workspaces; the work-queue size of an earlier call, copied back lazily (never waited for) to size
+    // the next call's queue
+    struct Vox : vp::Feature {
+        VP_BUFFERS(kept, rec, tile_cnt, tile_off, tile_cur, pairs, scratch)
+        vp::HostWords<uint32_t> total_host;
+        hipEvent_t total_event = nullptr;
+        bool total_pending = false;
+        uint64_t total_seen = 0;
+        uint64_t nbig_seen = 0;                // large triangles an earlier call counted (sizes the record list)
+        bool counts_known = false;             // at least one such count has come back
+        VoxJob pending_job, nolist_job;
+    } vox;
+    // conservative voxelizer (cvox.hip): its own large-triangle counter, record list and row scan, and its own lazily copied count
+    struct Cvox : vp::Feature {
+        VP_BUFFERS(kept, cnt, rec, base)
+        vp::HostWords<uint32_t> host;
+        hipEvent_t event = nullptr;
+        bool pending = false;
+        uint64_t nbig_seen = 0;
+    } cvox;
+    // interior fill (fill.hip): the ring of round flags (two batches) and its pinned host copy of one batch
+    struct Fill : vp::Feature {
+        VP_BUFFERS(kept, flags)
+        vp::HostWords<uint32_t> host;
+    } fill;
+    // ball morphology (morph.hip): the row tables of every radius (uploaded by the first tiled call) and the intermediate grid of open / close
+    struct Morph : vp::Feature {
+        VP_BUFFERS(kept, tab, tmp)
+    } morph;
+    // connected components (components.hip): root counts per block of voxels and their scan; for vp_components_filter the label volume
+    // (4 n^3 bytes, the one buffer vp_ctx_release frees), the sizes and keep flags of the K components, the arg-max winners and the kept
+    // count; the pinned host words K and kept are read back through
+    struct Comp : vp::Feature {
+        VP_BUFFERS(released, labels)
+        VP_BUFFERS(kept, cnt, off, sizes, keep, small)
+        vp::HostWords<uint64_t> host;
+    } comp;
+    // surface nets (surfnets.hip): block counts of vertices and quads and their scans; the rank lookup -- NAIVE: the vertex-index volume,
+    // 4 (n+1)^3 bytes; TILED: active-cell bits + one exclusive count per word, about n^3/4 bytes -- and the second position buffer of the
+    // relaxation (rank and xyz are freed by vp_ctx_release); what the last vp_surfnets_count was for (words = nullptr: nothing)
+    struct Sn : vp::Feature {
+        VP_BUFFERS(released, rank, xyz)
+        VP_BUFFERS(kept, cnt, off)
+        const uint32_t* words = nullptr;
+        uint32_t n = 0;
+        int algo = 0;
+        uint64_t vertices = 0, quads = 0;
+        void forget() { words = nullptr; }
+    } sn;
+    // exact distance transform (edt.hip): the border mask of SEEDS_BORDER, the distance volume of vp_edt_morph, the second volume of the NAIVE
+    // column passes (4 n^3 bytes each) and the intermediate grid of open / close; all four are freed by vp_ctx_release
+    struct Edt : vp::Feature {
+        VP_BUFFERS(released, mask, vol, vol2, tmp)
+    } edt;
+    // mesh distance (meshdist.hip): NAIVE's key volume (8 n^3 bytes), the triangle records and their row scan, the brick counts (+ write
+    // cursors and plane sums) and offsets, the brick lists; the pinned host words the plane sums are read back through and the list
+    // length of the last TILED call (vp_mesh_distance_stats); the six buffers are freed by vp_ctx_release
+    struct Md : vp::Feature {
+        VP_BUFFERS(released, keys, rec, base, cnt, off, list)
+        vp::HostWords<uint64_t> host;
+        uint64_t last_total = 0;
+    } md;
+    // iso-surface nets (isonets.hip): the inside grid of the field (n^3 / 8 bytes) and the mesh of the last vp_isonets, which the context
+    // owns and vp_isonets_result hands out -- records, positions, normals (if asked for), quads; all five are freed by vp_ctx_release
+    struct Iso : vp::Feature {
+        VP_BUFFERS(released, words, cells, xyz, normals, quads)
+        uint64_t vertices = 0, quad_count = 0;
+        bool has_normals = false;
+        void forget() { vertices = quad_count = 0; has_normals = false; }
+    } iso;
+    // generalized winding number (winding.hip): the result of the last vp_winding, which the context owns and vp_winding_result hands out
+    // -- the field w (4 n^3 bytes) and its inside grid (n^3 / 8 bytes) -- the triangle records sorted by leaf (48 B each) and the pyramid
+    // (counts, boxes, area sums, node records, leaf offsets, leaf keys); the pinned host word the inside count comes back through
+    struct Wn : vp::OwnedResult {
+        VP_BUFFERS(released, w, inside, rec, tree)
+        vp::HostWords<uint64_t> host;
+    } wn;
+    // local thickness (thickness.hip): the result of the last vp_thickness, which the context owns and vp_thickness_result hands out -- T2
+    // (4 n^3 bytes) and the thin grid (n^3 / 8 bytes) -- TILED's capped radii as uint16 (2 n^3 bytes), the grids of the saturated centres and
+    // of the saturated region (n^3 / 8 bytes each) and the thin count with the per-brick summaries; the pinned host word the count comes
+    // back through (the distance volumes are edt.vol / edt.vol2)
+    struct Th : vp::OwnedResult {
+        VP_BUFFERS(released, t2, thin, d16, sat, sum)
+        vp::HostWords<uint64_t> host;
+    } th;
+    // sparse voxel octree (octree.hip): the nodes of the last vp_octree (8 bytes each, sized from the count), which the context owns and
+    // vp_octree_result hands out; the device summary (level_offset | full_leaves | nodes per level), the state bytes and ranks of the levels
+    // (NAIVE: all of them; TILED: those above the 32^3 blocks) and TILED's per-block counts and offsets; the pinned host words the summary
+    // comes back through and its copy
+    struct Oc : vp::OwnedResult {
+        VP_BUFFERS(released, nodes, sum, state, rank, cnt)
+        vp::HostWords<uint32_t> host;
+        uint64_t count = 0;
+        uint32_t level_offset[11] = {}, full_leaves[11] = {};
+        void forget() { OwnedResult::forget(); count = 0; }
+    } oc;
+    // the grid of the last vp_octree_expand (n^3 / 8 bytes), which the context owns and vp_octree_expand_result hands out
+    struct OcExpand : vp::OwnedResult {
+        VP_BUFFERS(released, grid)
+    } ocx;
+    // topological thinning (skeleton.hip): the grid of the last vp_skeleton (n^3 / 8 bytes), which the context owns and vp_skeleton_result
+    // hands out, and its three statistics; NAIVE's second grid, the border words of the current iteration (n^3 / 8 bytes each) and the
+    // counters with TILED's block flags and list of active blocks (block_list.h); the pinned host words the counters come back through
+    struct Sk : vp::OwnedResult {
+        VP_BUFFERS(released, grid, tmp, border, aux)
+        vp::HostWords<uint64_t> host;
+        uint64_t stats[3] = {};
+    } sk;
+    // geodesic distance (geodesic.hip): D (4 n^3 bytes) and the reach grid (n^3 / 8 bytes) of the last vp_geodesic, which the context owns
+    // and vp_geodesic_result hands out, and its four statistics; the counters with TILED's block flags and list of active blocks
+    // (block_list.h) or NAIVE's ring of round flags; the pinned host words they come back through
+    struct Gd : vp::OwnedResult {
+        VP_BUFFERS(released, dist, reach, aux)
+        vp::HostWords<uint64_t> host;
+        uint64_t stats[4] = {};
+    } gd;
+    // vp_extract_*: block counts / offsets of the last count call and what it was for (words = nullptr: nothing)
+    struct Ext : vp::Feature {
+        VP_BUFFERS(kept, cnt, off)
+        const uint32_t* words = nullptr;
+        int mode = -1;
+        uint32_t n = 0;
+        uint64_t total = 0;
+        void forget() { words = nullptr; }
+    } ext;
+    // JFA: the row of "no seed" ids (jfa_seed.hip) and the workspace of vp_jfa* with d_work = NULL -- two id volumes + border mask, freed
+    // by vp_ctx_release -- with the record of what the last vp_jfa_start left in its workspace, so that vp_jfa_run can refuse anything
+    // else (a run on a workspace that holds init ids where it expects a border mask, or nothing at all, would produce an sdf from stale
+    // memory)
+    struct Jfa : vp::Feature {
+        VP_BUFFERS(released, work)
+        VP_BUFFERS(kept, none_row)
+        struct Started {
+            bool valid = false;
+            bool mask = false;                     // border mask behind the two id volumes (fast sequence) / init ids in the first volume
+            uint32_t n = 0;
+            int algo = 0;
+            const void* work = nullptr;
+            size_t work_bytes = 0;
+            const uint32_t* words = nullptr;
+        } started;
+        void forget() { started.valid = false; }
+    } jfa;
+
+    // f(feature) for every feature of the context: how vp_ctx_release and vp_ctx_destroy find every buffer
+    template <typename F> void each_feature(F f)
+    {
+        f(ws); f(vox); f(cvox); f(fill); f(morph); f(comp); f(sn); f(edt); f(md); f(iso); f(wn); f(th); f(oc); f(ocx); f(sk); f(gd); f(ext); f(jfa);
+    }
+};
+
+namespace vp {
 
 int reserve(vp_ctx* ctx, Buffer& b, size_t bytes, bool headroom = true);
 void release(Buffer& b);

@@ -412,17 +412,17 @@ int launch_winding(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nvert
     const Pyr py = make_pyramid(f.n);
     const size_t voxels = (size_t)f.n * f.n * f.n;
     const uint32_t nleaves = py.off[1], total = py.off[py.levels];
-    ctx->wn_n = 0;                                                 // from here on the previous result is gone
-    VP_TRY(reserve(ctx, ctx->wn_w, voxels * 4, false));
-    VP_TRY(reserve(ctx, ctx->wn_inside, voxels / 8, false));
-    VP_TRY(reserve(ctx, ctx->wn_rec, std::max<size_t>(ntris, 1) * kRecU4 * 16));
+    ctx->wn.n = 0;                                                 // from here on the previous result is gone
+    VP_TRY(reserve(ctx, ctx->wn.w, voxels * 4, false));
+    VP_TRY(reserve(ctx, ctx->wn.inside, voxels / 8, false));
+    VP_TRY(reserve(ctx, ctx->wn.rec, std::max<size_t>(ntris, 1) * kRecU4 * 16));
     // the tree: [counter | sums | boxes | counts | cursors] are zeroed, [nodes | leaf offsets | keys] are written in full
     const size_t o_sum = 16, o_box = o_sum + (size_t)total * 24, o_cnt = o_box + (size_t)total * 24, o_cur = o_cnt + (size_t)total * 4;
     const size_t zeroed = align16(o_cur + (size_t)nleaves * 4);
     const size_t o_nodes = zeroed, o_off = o_nodes + (size_t)total * sizeof(WNode), o_key = align16(o_off + ((size_t)nleaves + 1) * 4);
-    VP_TRY(reserve(ctx, ctx->wn_tree, o_key + std::max<size_t>(ntris, 1) * 4));
-    if (h_inside_count && !ctx->wn_host) VP_HIP(hipHostMalloc((void**)&ctx->wn_host, sizeof(uint64_t), hipHostMallocDefault));
-    char* base = (char*)ctx->wn_tree.ptr;
+    VP_TRY(reserve(ctx, ctx->wn.tree, o_key + std::max<size_t>(ntris, 1) * 4));
+    if (h_inside_count) VP_TRY(ctx->wn.host.need(1));
+    char* base = (char*)ctx->wn.tree.ptr;
     unsigned long long* counter = (unsigned long long*)base;
     unsigned long long* sum = (unsigned long long*)(base + o_sum);
     uint32_t* box = (uint32_t*)(base + o_box);
@@ -445,7 +445,7 @@ int launch_winding(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nvert
     if (ntris) {
         ProfScope p(ctx, VP_K_MD_WRITE);
         hipLaunchKernelGGL(wn_write, dim3(tblocks), dim3(256), 0, st, d_xyz, d_tri, ntris, (const uint32_t*)key, (const uint32_t*)leaf_off, cur,
-                           (float4*)ctx->wn_rec.ptr);
+                           (float4*)ctx->wn.rec.ptr);
     }
     {
         ProfScope p(ctx, VP_K_MD_COUNT);
@@ -459,24 +459,24 @@ int launch_winding(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nvert
     if (algo == VP_ALGO_NAIVE) {
         ProfScope p(ctx, VP_K_MD_NAIVE);
         hipLaunchKernelGGL(wn_naive, dim3((unsigned)(voxels / 256)), dim3(256), 0, st, f, py, beta, level, (const WNode*)nodes,
-                           (const uint32_t*)leaf_off, (const float4*)ctx->wn_rec.ptr, (float*)ctx->wn_w.ptr, (uint32_t*)ctx->wn_inside.ptr);
+                           (const uint32_t*)leaf_off, (const float4*)ctx->wn.rec.ptr, (float*)ctx->wn.w.ptr, (uint32_t*)ctx->wn.inside.ptr);
     } else {
         ProfScope p(ctx, VP_K_MD_BRICK);
         hipLaunchKernelGGL(wn_brick, dim3(nleaves), dim3(256), 0, st, f, py, beta, level, (const WNode*)nodes, (const uint32_t*)leaf_off,
-                           (const uint4*)ctx->wn_rec.ptr, (float*)ctx->wn_w.ptr, (uint8_t*)ctx->wn_inside.ptr);
+                           (const uint4*)ctx->wn.rec.ptr, (float*)ctx->wn.w.ptr, (uint8_t*)ctx->wn.inside.ptr);
     }
     if (h_inside_count) {
         ProfScope p(ctx, VP_K_MD_SPLIT);
         hipLaunchKernelGGL(wn_count, dim3((unsigned)std::min<size_t>((voxels / 32 + 255) / 256, (size_t)ctx->cus * 4)), dim3(256), 0, st,
-                           (const uint32_t*)ctx->wn_inside.ptr, voxels / 32, counter);
+                           (const uint32_t*)ctx->wn.inside.ptr, voxels / 32, counter);
     }
     VP_HIP(hipGetLastError());
     if (h_inside_count) {
-        VP_HIP(hipMemcpyAsync(ctx->wn_host, counter, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        VP_HIP(hipMemcpyAsync(ctx->wn.host, counter, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         VP_HIP(hipStreamSynchronize(st));
-        *h_inside_count = *ctx->wn_host;
+        *h_inside_count = *ctx->wn.host;
     }
-    ctx->wn_n = f.n;
+    ctx->wn.n = f.n;
     return 0;
 }
 

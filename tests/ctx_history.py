@@ -4,32 +4,32 @@ CPU references and the order in which every call follows every other one).  test
 Nothing here touches a GPU at import; the callables of the tables do when they are called.
 
 Part 2's map of vp_ctx (csrc/vp_internal.h) -- field: nodes that grow, fill or read it.
-  rec, tile_cnt, tile_off, tile_cur, pairs      vox_d20_* (record list, queue, tile stage); vox_fine_* leave rec at its floor (noLists on repeat)
-  scratch                                       vox_acc_* (accumulate = XOR through a scratch grid)
-  none_row                                      jfa_tiled_96 / jfa_tiled_128 / jfa_startrun_128 (tile kernels: the row of "no seed" ids)
-  jfa_work, jfa_started                         every jfa_* node (context-owned workspace; start + run in jfa_startrun_*); release frees / drops
-  slots[]                                       not reached: only the host forms use them, and those are excluded (they write no caller memory)
-  ext_cnt, ext_off, ext_words/mode/n/total      extract_* (count + write)
-  vox_total_host/event/pending/seen, vox_nbig_seen, vox_counts_known, vox_pending_job, vox_nolist_job
+  vox.rec, tile_cnt, tile_off, tile_cur, pairs  vox_d20_* (record list, queue, tile stage); vox_fine_* leave rec at its floor (noLists on repeat)
+  vox.scratch                                   vox_acc_* (accumulate = XOR through a scratch grid)
+  jfa.none_row                                  jfa_tiled_96 / jfa_tiled_128 / jfa_startrun_128 (tile kernels: the row of "no seed" ids)
+  jfa.work, jfa.started                         every jfa_* node (context-owned workspace; start + run in jfa_startrun_*); release frees / drops
+  ws.slots[]                                    not reached: only the host forms use them, and those are excluded (they write no caller memory)
+  ext.cnt, ext.off, ext.words/mode/n/total      extract_* (count + write)
+  vox.total_host/event/pending/seen, vox.nbig_seen, vox.counts_known, vox.pending_job, vox.nolist_job
                                                 every vox_*_tiled node: traversal (i) lets every count land, (ii) lets them land late or never; the
-                                                self-loops are the "repeated job" of vox_nolist_job, every other predecessor is "another job"
-  cvox_cnt, cvox_rec, cvox_base, cvox_host/event/pending, cvox_nbig_seen
+                                                self-loops are the "repeated job" of vox.nolist_job, every other predecessor is "another job"
+  cvox.cnt, cvox.rec, cvox.base, cvox.host/event/pending, cvox.nbig_seen
                                                 cvox_tiled_* (cvox_naive_* reads none of them)
-  fill_flags, fill_host                         fill_*
-  morph_tab, morph_tmp                          morph_dilate_* (table), morph_close_* (table + intermediate grid); morph_naive_* reads neither
-  comp_cnt, comp_off, comp_host                 comp_label_*, comp_filter_*
-  comp_labels, comp_sizes, comp_keep, comp_small   comp_filter_* (comp_sizes also comp_label_*: vp_components_sizes)
-  sn_cnt, sn_off, sn_rank, sn_xyz, sn_words/n/algo/vertices/quads
-                                                surfnets_tiled_* (2 relaxation steps: sn_xyz), surfnets_naive_* (rank volume of another size)
-  edt_mask                                      edt_border_* ; edt_vol: edt_morph_* ; edt_vol2: edt_sdf_naive_* ; edt_tmp: edt_morph_* (close)
-  md_keys                                       meshdist_naive_* ; md_rec, md_base, md_cnt, md_off, md_list, md_host, md_last_total: meshdist_tiled_*
+  fill.flags, fill.host                         fill_*
+  morph.tab, morph.tmp                          morph_dilate_* (table), morph_close_* (table + intermediate grid); morph_naive_* reads neither
+  comp.cnt, comp.off, comp.host                 comp_label_*, comp_filter_*
+  comp.labels, comp.sizes, comp.keep, comp.small   comp_filter_* (comp.sizes also comp_label_*: vp_components_sizes)
+  sn.cnt, sn.off, sn.rank, sn.xyz, sn.words/n/algo/vertices/quads
+                                                surfnets_tiled_* (2 relaxation steps: sn.xyz), surfnets_naive_* (rank volume of another size)
+  edt.mask                                      edt_border_* ; edt.vol: edt_morph_* ; edt.vol2: edt_sdf_naive_* ; edt.tmp: edt_morph_* (close)
+  md.keys                                       meshdist_naive_* ; md.rec, md.base, md.cnt, md.off, md.list, md.host, md.last_total: meshdist_tiled_*
   prof_on, prof_mask, prof_pending, prof_pool   traversal (ii): every ProfScope of every node
   device, cus, own_stream, stream               constant during a traversal (the tests run on the caller's stream)
-The node `release` frees jfa_work, comp_labels, sn_rank, sn_xyz, edt_*, md_* between any two calls, so every op also runs as the first
+The node `release` frees jfa.work, comp.labels, sn.rank, sn.xyz, edt.*, md.* between any two calls, so every op also runs as the first
 after a release and regrows them.
 No node: the tile kernels started from init ids.  On a whole grid the library starts every tile-kernel sequence (n >= 96) from the border
 mask with the first two passes fused (jfa_tile_sequence in csrc/capi.hip); init ids feed the tile kernels only in the slab and window calls
-of the multi-GPU drivers, which keep no state in a vp_ctx beyond none_row and are covered by tests/test_multi_gpu.py."""
+of the multi-GPU drivers, which keep no state in a vp_ctx beyond jfa.none_row and are covered by tests/test_multi_gpu.py."""
 import collections
 import functools
 import math

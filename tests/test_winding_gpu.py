@@ -2,7 +2,8 @@
 bit: NAIVE and TILED, the field and the inside grid, on the hand cases and the small meshes at n = 32 with beta 0, 1 and 2 and the levels
 0.5 and 1.5, on d20 and torus at n = 64 and 96 (the uneven pyramid) with the same betas and levels, on a mesh scaled out of the frame (clamped leaves) and on one far from
 the origin; bunny at n = 96 and 128 against the host form; the hand-over of the inside grid to vp_mesh_distance; the result pointers before
-a build and after a release; refusals that leave the previous result alone; two grid sides in one context.
+a build and after a release; refusals that leave the previous result alone; two grid sides in one context; the counts and the start that
+stood on an inside grid whose buffers a larger build frees.
 The brute force (beta = 0) of the torus at n = 64 and 96 is compared with the host form, like bunny: its numpy restatement takes tens of
 seconds there.  The empty mesh also goes through vp_winding_host."""
 import functools
@@ -242,3 +243,77 @@ def test_two_sides_in_one_context_equal_a_fresh_context():
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), algo
     exp_w, exp_g = R.winding_f32(xyz, tri, 32, *M.frame([xyz], 32)[::-1], 2.0, 0.5)
     assert np.array_equal(got[((32,), 32, ALGO_TILED)][0], exp_w.view(np.uint32)) and np.array_equal(got[((32,), 32, ALGO_TILED)][1], exp_g)
+
+
+def test_pending_records_are_dropped_when_the_result_buffers_grow():
+    """The inside grid is a grid like any other: a vp_surfnets_count, a vp_extract_count and a vp_jfa_start may stand on it.  A vp_winding
+    at a larger side frees the bytes they stood on (n = 32 -> 64 is the smallest pair of sides at which the 4 n^3 and the n^3 / 8 buffer
+    both have to grow: 8 x the bytes against 25 % head-room), so the records go BEFORE the launch: each dependent call is refused and
+    writes nothing."""
+    ctx = capi.Context(0)
+    try:
+        xyz, tri, _, _ = _case("d20.obj", 32)
+        dx, dt = ctx.malloc(xyz.nbytes), ctx.malloc(tri.nbytes)
+        ctx.upload(dx, xyz)
+        ctx.upload(dt, tri)
+        fr, big = (Frame.make(n, *M.frame([xyz], n)[::-1]) for n in (32, 64))
+
+        def build(frame):
+            ctx.winding(frame, dx, len(xyz), dt, len(tri), 2.0, 0.5, ALGO_TILED)
+            _, inside, side = ctx.winding_result()
+            assert inside and side == frame.n
+            return inside
+
+        def pattern(nbytes):
+            p = ctx.malloc(nbytes)
+            ctx.memset(p, 0xA5, nbytes)
+            return p, nbytes
+
+        def untouched(*bufs):
+            ctx.sync()
+            for p, nbytes in bufs:
+                h = np.empty(nbytes, np.uint8)
+                ctx.download(h, p)
+                assert (h == 0xA5).all()
+                ctx.free(p)
+
+        def refused(fn):
+            with pytest.raises(capi.VPError) as e:
+                fn()
+            assert e.value.code == 10001
+
+        inside = build(fr)
+        nv, nq = ctx.surfnets_count(fr, inside)
+        total = ctx.extract_count(fr, inside, 0)
+        assert nv and nq and total
+        mine = np.empty(fr.voxels // 32, np.uint32)                  # a copy for the grid of the caller's own below
+        ctx.download(mine, inside)
+        build(big)                                                   # the buffers grow: the bytes the counts stood on are freed
+        cells, pos, quads, records = pattern(nv * 8), pattern(nv * 12), pattern(nq * 16), pattern(total * 8)
+        refused(lambda: ctx.surfnets(fr, inside, ALGO_TILED, 0, cells[0], pos[0], quads[0], nv, nq))
+        refused(lambda: ctx.extract(fr, inside, 0, 0, records[0], 0, total))
+        untouched(cells, pos, quads, records)
+        # the start, through a second build: released, the buffers are those of n = 32 again and have to grow again
+        ctx.release()
+        inside = build(fr)
+        ctx.jfa_start(fr, inside, None, 0, ALGO_TILED)
+        build(big)
+        sdf = pattern(fr.voxels * 4)
+        refused(lambda: ctx.jfa_run(fr, inside, -np.inf, sdf[0], None, 0, ALGO_TILED))
+        untouched(sdf)
+        # a count on a grid of the caller's own stands through a build
+        own = ctx.malloc(mine.nbytes)
+        ctx.upload(own, mine)
+        assert ctx.surfnets_count(fr, own) == (nv, nq)
+        build(fr)
+        build(big)
+        cells, pos, quads = pattern(nv * 8), pattern(nv * 12), pattern(nq * 16)
+        ctx.surfnets(fr, own, ALGO_TILED, 0, cells[0], pos[0], quads[0], nv, nq)
+        ctx.sync()
+        h = np.empty(nq * 16, np.uint8)
+        ctx.download(h, quads[0])
+        assert not (h == 0xA5).all()                                 # served: the quads are written
+        for p in (cells[0], pos[0], quads[0], own, dx, dt):
+            ctx.free(p)
+    finally:
+        ctx.close()
