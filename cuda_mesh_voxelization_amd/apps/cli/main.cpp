@@ -43,6 +43,14 @@
 //                            writes PREFIX.skel.u32 (a grid).  One device only (-g > 1 is refused)
 //         --skeleton-only    (extension, with --skeleton) the grid is replaced by the skeleton before the exports that follow, --octree and
 //                            -s: -e writes out/skel_<type>_<output>, and -d PREFIX.grid.u32 holds it
+//         --watershed R[:Q[:C]]  (extension) seeded watershed of every grid, after --morph and --fill: the parts that erosion by R voxels separates
+//                            are grown back over the exact distance map and cut where they meet (include/vphip.h, vp_watershed;
+//                            vox/watershed.h).  priority = D2 inside the solid (vp_edt, UNSET seeds), flooded from the high end in levels
+//                            of Q (default 1); markers = the components (connectivity C = 6 | 26, default 6) of inset:R of the grid.
+//                            THE CUT GRID REPLACES THE WORKING GRID: -e, --surface-nets, --octree, --thickness, --skeleton, --geodesic, CSG
+//                            and -s act on the separated parts.  Prints "watershed: n N, markers K, marker voxels U, labelled L, levels
+//                            H, cut X"; with -e writes out/<mesh stem>_<type>_labels.raw (n^3 uint32, x fastest); -d PREFIX additionally
+//                            writes PREFIX.labels.u32 (the labels of the first grid).
 //         --geodesic S[:M]   (extension) geodesic distance inside the FINAL grid -- where --octree sits, after --thin-only and --skeleton-only, so
 //                            that "--skeleton curve --skeleton-only --geodesic zmin" measures the centre line: the length of the shortest path
 //                            that stays inside the grid from the seed voxels to every set voxel (include/vphip.h, vp_geodesic;
@@ -112,6 +120,7 @@
 #include "mesh/mesh_io.h"
 #include "proc_utils.h"
 #include "vox/geodesic.h"
+#include "vox/watershed.h"
 #include "vox/octree.h"
 #include "vox/skeleton.h"
 #include "vox/vox.h"
@@ -147,6 +156,9 @@ struct Options {
     int skeleton = -1;                                      // --skeleton curve|kernel[:ITERS]: VOX::SkeletonMode, -1 = not asked for
     unsigned skeletonIters = 0;
     bool skeletonOnly = false;
+    bool watershed = false;                                 // --watershed R[:Q[:C]]
+    unsigned wsRadius = 0, wsQuantum = 1;
+    int wsConn = 6;
     bool geodesic = false;                                  // --geodesic SEED[:METRIC]
     int geoSeed = 0, geoMetric = 2;                         // 0: zmin, 1: zmax, 2: the voxel geoVoxel; VOX::GeodesicMetric
     unsigned geoVoxel[3] = {0, 0, 0};
@@ -255,6 +267,11 @@ const char* kUsage =
     "                        the skeleton.  -d PREFIX adds PREFIX.skel.u32.  One device only: not with -g > 1 (extension)\n"
     "      --skeleton-only   With --skeleton: replace the grid by the skeleton, so that -e (out/skel_<type>_<output>), --octree, -s\n"
     "                        and -d see it (extension)\n"
+    "      --watershed arg   Seeded watershed of every grid, after --morph and --fill: arg = R[:Q[:C]].  The components (connectivity\n"
+    "                        C = 6 or 26, default 6) of the grid eroded by R voxels are the markers; they are grown back over the exact\n"
+    "                        squared distance map, from its high end in levels of Q (default 1), and cut where they meet.  The cut grid\n"
+    "                        replaces the working grid, so every later step and export acts on the separated parts; -e also writes\n"
+    "                        out/<mesh>_<type>_labels.raw, -d PREFIX.labels.u32.  One device (extension)\n"
     "      --geodesic arg    Geodesic distance inside the final grid (where --octree sits, after --thin-only and --skeleton-only): arg =\n"
     "                        SEED[:METRIC], SEED = zmin or zmax (the set voxels of the lowest / highest occupied z plane) or X,Y,Z (one set\n"
     "                        voxel), METRIC = 6 (face steps), 26 (all steps at cost 1) or chamfer (costs 3, 4, 5: divide by 3; default).\n"
@@ -301,7 +318,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"skeleton", 'K'}, {"skeleton-only", 'Q'}, {"geodesic", 'G'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"skeleton", 'K'}, {"skeleton-only", 'Q'}, {"geodesic", 'G'}, {"watershed", 'Z'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -391,6 +408,26 @@ Options Parse(int argc, char** argv)
                     o.geoSeed = 2;
                 }
                 o.geodesic = true;
+                break;
+            }
+            case 'Z': {
+                // R[:Q[:6|26]]: the erosion radius 1 .. 65535, the quantum 1 .. 2^32 - 1, the connectivity
+                std::vector<std::string> fields;
+                for (size_t at = 0;;) {
+                    const size_t end = value.find(':', at);
+                    fields.push_back(value.substr(at, end == std::string::npos ? end : end - at));
+                    if (end == std::string::npos) break;
+                    at = end + 1;
+                }
+                auto digits = [](const std::string& t, size_t most) { return !t.empty() && t.size() <= most && t.find_first_not_of("0123456789") == std::string::npos; };
+                bool ok = fields.size() >= 1 && fields.size() <= 3 && digits(fields[0], 5) && std::stoul(fields[0]) >= 1 && std::stoul(fields[0]) <= 65535;
+                ok = ok && (fields.size() < 2 || (digits(fields[1], 10) && std::stoull(fields[1]) >= 1 && std::stoull(fields[1]) <= 0xFFFFFFFFull));
+                ok = ok && (fields.size() < 3 || fields[2] == "6" || fields[2] == "26");
+                cpuAssert(ok, "--watershed: '" + value + "' is not R[:Q[:C]] with R in 1..65535 voxels, a quantum Q >= 1 and C = 6 or 26\n");
+                o.watershed = true;
+                o.wsRadius = static_cast<unsigned>(std::stoul(fields[0]));
+                o.wsQuantum = fields.size() >= 2 ? static_cast<unsigned>(std::stoull(fields[1])) : 1u;
+                o.wsConn = fields.size() >= 3 ? std::stoi(fields[2]) : 6;
                 break;
             }
             case 'K': {
@@ -530,6 +567,36 @@ void OctreeOut(const HostVoxelsGrid<gridType>& grid, const std::string& path)
     std::printf("], %zu bytes, grid %.0f bytes, ratio %.2f, %s\n", tree.Bytes(), gridBytes, gridBytes / static_cast<double>(tree.Bytes()), path.c_str());
 }
 
+// --watershed: `grid` is replaced by the cut grid of its watershed -- markers = the components of the grid eroded by `radius`, priority =
+// the squared distance to the nearest unset voxel, flooded from the high end; `labels` gets the label volume; prints what the flag promises
+template <Types T>
+void WatershedSplit(unsigned radius, unsigned quantum, int conn, HostVoxelsGrid<gridType>& grid, HostGrid<uint32_t>& labels)
+{
+    const size_t n = grid.View().VoxelsPerSide();
+    HostVoxelsGrid<gridType> cores(n, grid.View().VoxelSize());
+    cores.View().SetOrigin(grid.View().OriginX(), grid.View().OriginY(), grid.View().OriginZ());
+    std::memcpy(cores.View().Data(), grid.View().Data(), grid.View().StorageSize() * sizeof(gridType));
+    VOX::MorphExact<T>(cores, VOX::MorphOp::ERODE, radius);
+    HostGrid<uint32_t> markers, dist;
+    const uint32_t count = VOX::LabelComponents<T>(cores, markers, conn);
+    cpuAssert(count <= VOX::WATERSHED_LABEL_MAX, "--watershed: more than 2^20 - 1 markers: erode further\n");
+    VOX::DistanceTransform<T>(grid, dist, VOX::EdtSeeds::UNSET);
+    // a grid without an unset voxel has no distance (VP_EDT_NONE everywhere): one level then
+    const uint32_t* d = dist.View().Data();
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    const uint32_t* bits = reinterpret_cast<const uint32_t*>(grid.View().Data());
+    for (size_t i = 0; i < n * n * n; ++i)
+        if ((bits[i >> 5] >> (i & 31)) & 1u) { lo = std::min(lo, d[i]); hi = std::max(hi, d[i]); }
+    cpuAssert(lo > hi || hi / quantum - lo / quantum < VOX::WATERSHED_MAX_SPAN,
+              "--watershed: the distance map spans 16384 levels or more at this quantum: give a larger Q\n");
+    HostVoxelsGrid<gridType> cut;
+    const VOX::WatershedStats st = VOX::Watershed<T>(grid, markers, &dist, VOX::WATERSHED_DESCENDING, quantum, conn, labels, &cut);
+    std::memcpy(grid.View().Data(), cut.View().Data(), grid.View().StorageSize() * sizeof(gridType));
+    std::printf("watershed: n %zu, markers %u, marker voxels %llu, labelled %llu, levels %llu, cut %llu\n", n, count,
+                static_cast<unsigned long long>(st.markers), static_cast<unsigned long long>(st.labelled), static_cast<unsigned long long>(st.levels),
+                static_cast<unsigned long long>(st.cutVoxels));
+}
+
 // --geodesic: the distance inside `grid` from the seeds `seed` names (0: the lowest occupied z plane, 1: the highest, 2: the voxel xyz) into
 // `dist` and `reach`; prints what the flag promises
 template <Types T>
@@ -627,6 +694,7 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.skeleton >= 0 && opt.gpus > 1), "--skeleton runs on one device: -g must be 1\n");
     cpuAssert(!(opt.skeletonOnly && opt.skeleton < 0), "--skeleton-only needs --skeleton curve|kernel\n");
     cpuAssert(!(opt.geodesic && opt.gpus > 1), "--geodesic runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.watershed && opt.gpus > 1), "--watershed runs on one device: -g must be 1\n");
     cpuAssert(!(opt.geodesic && opt.geoSeed == 2 && (opt.geoVoxel[0] >= opt.numVoxels || opt.geoVoxel[1] >= opt.numVoxels || opt.geoVoxel[2] >= opt.numVoxels)),
               "--geodesic: the seed voxel lies outside the grid\n");
     cpuAssert(!(opt.octree && (opt.numVoxels % 32 != 0 || opt.numVoxels > 1024)), "--octree needs -n to be a multiple of 32 up to 1024\n");
@@ -680,7 +748,7 @@ int main(int argc, char** argv)
     HostGrid<float> sdf;
     HostGrid<uint32_t> thick;
     HostVoxelsGrid<gridType> thinGrid, skelGrid, geoReach;
-    HostGrid<uint32_t> geoDist;
+    HostGrid<uint32_t> geoDist, wsLabels, wsFirst;
     const std::string typeName = GetTypesString(TYPE);
     if (EXPORT || opt.octree) std::filesystem::create_directories("out");
 
@@ -726,6 +794,18 @@ int main(int argc, char** argv)
                     case Types::NAIVE:      VOX::FillInterior<Types::NAIVE>(grid); break;
                     case Types::TILED:      VOX::FillInterior<Types::TILED>(grid); break;
                 }
+            }
+            if (opt.watershed) {
+                switch (TYPE) {
+                    case Types::SEQUENTIAL: WatershedSplit<Types::SEQUENTIAL>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                    case Types::OPENMP:     WatershedSplit<Types::OPENMP>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                    case Types::NAIVE:      WatershedSplit<Types::NAIVE>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                    case Types::TILED:      WatershedSplit<Types::TILED>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                }
+                if (EXPORT)
+                    WriteRaw("out/" + std::filesystem::path(GetFilename(opt.filenames[i])).stem().string() + "_" + typeName + "_labels.raw",
+                             wsLabels.View().Data(), wsLabels.View().Size() * sizeof(uint32_t));
+                if (i == 0) wsFirst = wsLabels;
             }
             if (EXPORT) {                                                                               // main.cpp:118-124
                 Mesh outMesh;
@@ -881,6 +961,7 @@ int main(int argc, char** argv)
         WriteRaw(opt.dump + ".grid.u32", grids[0].View().Data(), grids[0].View().StorageSize() * sizeof(gridType));
         if (opt.sdf) WriteRaw(opt.dump + ".sdf.f32", sdf.View().Data(), sdf.View().Size() * sizeof(float));
         if (opt.thickness) WriteRaw(opt.dump + ".thick.u32", thick.View().Data(), thick.View().Size() * sizeof(uint32_t));
+        if (opt.watershed) WriteRaw(opt.dump + ".labels.u32", wsFirst.View().Data(), wsFirst.View().Size() * sizeof(uint32_t));
         if (opt.geodesic) {
             WriteRaw(opt.dump + ".geo.u32", geoDist.View().Data(), geoDist.View().Size() * sizeof(uint32_t));
             WriteRaw(opt.dump + ".reach.u32", geoReach.View().Data(), geoReach.View().StorageSize() * sizeof(gridType));

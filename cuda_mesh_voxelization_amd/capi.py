@@ -21,6 +21,8 @@ ISO_LINEAR, ISO_SIGNED_SQUARE = 0, 1                                # vp_isonets
 CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
 SKEL_KERNEL, SKEL_CURVE = 0, 1                                      # vp_skeleton: the homotopy kernel / the centre line (line ends stay)
 GEO_6, GEO_26, GEO_CHAMFER = 0, 1, 2                                # vp_geodesic: face steps / all 26 steps at cost 1 / at cost 3, 4, 5
+WS_ASCENDING, WS_DESCENDING = 0, 1                                  # vp_watershed: flood from low / from high priority
+WS_LABEL_MAX, WS_MAX_SPAN = 0xFFFFF, 16384                          # vp_watershed: the largest marker label, the bound of the level span
 GEO_NONE = 0xFFFFFFFF                                               # vp_geodesic: "no path from a seed arrives here"
 COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
@@ -75,6 +77,7 @@ SYMBOLS = [
     "vp_octree", "vp_octree_result", "vp_octree_expand", "vp_octree_expand_result", "vp_octree_host", "vp_octree_expand_host", "vp_octree_validate_host",
     "vp_skeleton", "vp_skeleton_result", "vp_skeleton_host", "vp_skeleton_table_host",
     "vp_geodesic", "vp_geodesic_result", "vp_geodesic_host",
+    "vp_watershed", "vp_watershed_result", "vp_watershed_host",
 ]
 
 
@@ -230,6 +233,9 @@ def lib():
         "vp_geodesic": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
         "vp_geodesic_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
         "vp_geodesic_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+        "vp_watershed": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp]),
+        "vp_watershed_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_watershed_host": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -662,7 +668,38 @@ class Context:
         check(lib().vp_geodesic_result(self._h, ctypes.byref(d), ctypes.byref(r), s, ctypes.byref(n)))
         return d.value or 0, r.value or 0, tuple(int(v) for v in s), int(n.value)
 
+    def watershed(self, frame: Frame, d_mask: int, d_markers: int, d_priority: int = 0, order: int = WS_DESCENDING, quantum: int = 1,
+                  connectivity: int = CONN_6, algo: int = ALGO_TILED):
+        """Seeded watershed of the mask from the marker volume (uint32 per voxel, 0 = none) over the priority field (uint32 per voxel;
+        0: none -- the geodesic influence zones) of a whole grid (n <= 1024) into buffers the context owns; watershed_result() hands them
+        out.  Blocks (a pre-pass and the convergence of every level are read back) and returns (markers used, voxels labelled, levels
+        present, voxels cut)."""
+        s = (ctypes.c_uint64 * 4)()
+        check(lib().vp_watershed(self._h, ctypes.byref(frame), _vp(d_mask or None), _vp(d_markers or None), _vp(d_priority or None), order, quantum,
+                                 connectivity, algo, s))
+        return tuple(int(v) for v in s)
+
+    def watershed_result(self):
+        """(d_labels, d_cut, stats, n) of the last watershed(): the device pointers as ints (0 where there is none), the four statistics
+        and the side they are for.  Valid until the next watershed(), release() or close()."""
+        d, r, s, n = _vp(), _vp(), (ctypes.c_uint64 * 4)(), ctypes.c_uint32()
+        check(lib().vp_watershed_result(self._h, ctypes.byref(d), ctypes.byref(r), s, ctypes.byref(n)))
+        return d.value or 0, r.value or 0, tuple(int(v) for v in s), int(n.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
+    def watershed_host(self, frame: Frame, h_mask, h_markers, h_priority=None, order: int = WS_DESCENDING, quantum: int = 1,
+                       connectivity: int = CONN_6, algo: int = ALGO_TILED, want=(True, True, True)):
+        """numpy in, numpy out: (labels uint32[n^3], cut words uint32[n^3 / 32], statistics); want = which of the three are asked for (the
+        others go in as NULL and come back as None)."""
+        np = __import__("numpy")
+        w = np.empty(frame.voxels, np.uint32) if want[0] else None
+        c = np.empty(frame.voxels // 32, np.uint32) if want[1] else None
+        s = (ctypes.c_uint64 * 4)() if want[2] else None
+        check(lib().vp_watershed_host(self._h, ctypes.byref(frame), h_mask.ctypes.data_as(_vp), h_markers.ctypes.data_as(_vp),
+                                      None if h_priority is None else h_priority.ctypes.data_as(_vp), order, quantum, connectivity, algo,
+                                      None if w is None else w.ctypes.data_as(_vp), None if c is None else c.ctypes.data_as(_vp), s))
+        return w, c, None if s is None else tuple(int(v) for v in s)
+
     def geodesic_host(self, frame: Frame, h_mask, h_seeds, metric: int = GEO_CHAMFER, algo: int = ALGO_TILED, want=(True, True, True)):
         """numpy in, numpy out: (dist uint32[n^3], reach words uint32[n^3 / 32], statistics); want = which of the three are asked for (the
         others go in as NULL and come back as None)."""

@@ -177,7 +177,7 @@ static int host_round_trip(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_wor
 }
 
 // One path for the calls that build a result the context owns (vp_isonets, vp_winding, vp_thickness, vp_octree, vp_octree_expand,
-// vp_skeleton, vp_geodesic): `ft` is the feature that is built, `also` what the call writes besides that feature's buffers, launch() the
+// vp_skeleton, vp_geodesic, vp_watershed): `ft` is the feature that is built, `also` what the call writes besides that feature's buffers, launch() the
 // work.  The inputs are read while every one of those buffers is written: an input that lies in one is refused (the last result has to be
 // copied before it goes back in); `inputs` is empty for the calls that have never refused it.  The context's own buffers are outputs
 // like any other: whatever was recorded about their bytes is gone -- about the bytes they hold now (a buffer that has to grow is freed
@@ -1338,6 +1338,44 @@ int vp_geodesic_result(vp_ctx* ctx, uint32_t** d_dist, uint32_t** d_reach, uint6
     return 0;
 }
 
+// ---- seeded watershed -------------------------------------------------------------------------------
+// what vp_watershed and its host form share: whole grids up to n = 1024, order and quantum (where there is a priority field), the
+// connectivity and the algo
+static int check_watershed(const vp_frame* f, const char* who, bool priority, int order, uint32_t quantum, int conn, int algo)
+{
+    VP_TRY(check_grid_1024(f, who, algo));
+    if (priority && order != VP_WS_ASCENDING && order != VP_WS_DESCENDING) return set_error(VP_ERR_INVALID, "%s: unknown order %d", who, order);
+    if (priority && quantum == 0) return set_error(VP_ERR_INVALID, "%s: quantum must be at least 1", who);
+    if (conn != VP_CONN_6 && conn != VP_CONN_26) return set_error(VP_ERR_INVALID, "%s: unknown connectivity %d", who, conn);
+    return 0;
+}
+
+int vp_watershed(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_mask, const uint32_t* d_markers, const uint32_t* d_priority, int order,
+                 uint32_t quantum, int connectivity, int algo, uint64_t* h_stats)
+{
+    const char* who = "vp_watershed";
+    if (!ctx || !f || !d_mask || !d_markers) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_watershed(f, who, d_priority != nullptr, order, quantum, connectivity, algo));
+    VP_TRY(check_aligned(who, {d_mask, d_markers, d_priority}));
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;   // (a null priority field overlaps nothing)
+    return build_owned(ctx, who, ctx->wsd, {}, {{d_mask, wb}, {d_markers, vb}, {d_priority, vb}}, [&] {
+        return launch_watershed(ctx, make_frame(f), d_mask, d_markers, d_priority, order, quantum, connectivity, algo, h_stats);
+    });
+}
+
+int vp_watershed_result(vp_ctx* ctx, uint32_t** d_labels, uint32_t** d_cut, uint64_t* h_stats, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_watershed_result: null ctx");
+    const bool any = ctx->wsd.n != 0;
+    if (d_labels) *d_labels = any ? (uint32_t*)ctx->wsd.labels.ptr : nullptr;
+    if (d_cut) *d_cut = any ? (uint32_t*)ctx->wsd.cut.ptr : nullptr;
+    if (h_stats)
+        for (int i = 0; i < 4; ++i) h_stats[i] = any ? ctx->wsd.stats[i] : 0;
+    if (h_n) *h_n = ctx->wsd.n;
+    return 0;
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1519,6 +1557,22 @@ int vp_geodesic_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, con
     VP_TRY(vp_geodesic(ctx, f, (const uint32_t*)dm, (const uint32_t*)ds, metric, algo, h_stats));
     if (h_dist) VP_TRY(vp_download(ctx, h_dist, ctx->gd.dist.ptr, vp_grid_voxels(f) * 4));
     return h_reach ? vp_download(ctx, h_reach, ctx->gd.reach.ptr, wb) : 0;
+}
+
+int vp_watershed_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, const uint32_t* h_markers, const uint32_t* h_priority, int order,
+                      uint32_t quantum, int connectivity, int algo, uint32_t* h_labels, uint32_t* h_cut, uint64_t* h_stats)
+{
+    const char* who = "vp_watershed_host";
+    if (!ctx || !f || !h_mask || !h_markers || (!h_labels && !h_cut && !h_stats)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_watershed(f, who, h_priority != nullptr, order, quantum, connectivity, algo));
+    void *dm = nullptr, *dl = nullptr, *dp = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    VP_TRY(stage(ctx, SLOT_GRID_A, h_mask, wb, &dm));
+    VP_TRY(stage(ctx, SLOT_SDF, h_markers, vb, &dl));
+    if (h_priority) VP_TRY(stage(ctx, SLOT_NEAREST, h_priority, vb, &dp));
+    VP_TRY(vp_watershed(ctx, f, (const uint32_t*)dm, (const uint32_t*)dl, (const uint32_t*)dp, order, quantum, connectivity, algo, h_stats));
+    if (h_labels) VP_TRY(vp_download(ctx, h_labels, ctx->wsd.labels.ptr, vb));
+    return h_cut ? vp_download(ctx, h_cut, ctx->wsd.cut.ptr, wb) : 0;
 }
 
 int vp_skeleton_table_host(vp_ctx* ctx, int algo, uint32_t* h_table)

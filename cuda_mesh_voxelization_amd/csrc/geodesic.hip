@@ -56,7 +56,6 @@ constexpr uint32_t kNone = VP_GEO_NONE, kMax = VP_GEO_MAX;
 // the counters in front of the flags: kAuxHead bytes, of which seeds used (u64) | voxels reached (u64) | key of the farthest voxel (u64) |
 // active blocks (u32) are in use; kCnt* = where each starts, in 32-bit words
 constexpr uint32_t kCntSeeds = 0, kCntReached = 2, kCntKey = 4, kCntActive = 6;
-constexpr uint32_t kFaceBlocks = (1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22);   // of bit dx+1 + 3 (dy+1) + 9 (dz+1)
 
 template <int METRIC> struct Weights;
 template <> struct Weights<VP_GEO_6> { static constexpr uint32_t w1 = 1, w2 = 0, w3 = 0; static constexpr bool diagonal = false; };
@@ -65,17 +64,6 @@ template <> struct Weights<VP_GEO_CHAMFER> { static constexpr uint32_t w1 = 3, w
 
 // min(d + w, VP_GEO_MAX); VP_GEO_NONE stays
 __device__ __forceinline__ uint32_t gd_add(uint32_t d, uint32_t w) { return d == kNone ? kNone : (d > kMax - w ? kMax : d + w); }
-
-// The blocks whose staged tile holds one of the voxels `bits` of the row (ly, lz) of a block, bit dx+1 + 3 (dy+1) + 9 (dz+1) per block offset,
-// the block itself (bit 13) included: -1 / +1 along an axis needs the voxel on that face.  Face neighbours only where no step is diagonal.
-__device__ __forceinline__ uint32_t gd_seen_by(uint32_t bits, uint32_t ly, uint32_t lz, bool diagonal)
-{
-    if (bits == 0u) return 0u;
-    const uint32_t xm = (bits & 1u) | 2u | ((bits >> 31) << 2);
-    const uint32_t xy = (ly == 0u ? xm : 0u) | (xm << 3) | (ly == kBlockY - 1u ? xm << 6 : 0u);
-    const uint32_t see = (lz == 0u ? xy : 0u) | (xy << 9) | (lz == kBlockZ - 1u ? xy << 18 : 0u);
-    return diagonal ? see : see & (kFaceBlocks | 1u << 13);
-}
 
 // ---- both --------------------------------------------------------------------------------------------------------------------------
 
@@ -92,7 +80,7 @@ gd_init(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ seeds, u
     D[i] = make_uint4((s & 1u) ? 0u : kNone, (s & 2u) ? 0u : kNone, (s & 4u) ? 0u : kNone, (s & 8u) ? 0u : kNone);
     if ((i & 7u) == 0 && used != 0u && flags) {
         const uint32_t w = n / 32, nb = n / kBlockY, xw = (uint32_t)(word % w), y = (uint32_t)((word / w) % n), z = (uint32_t)(word / ((size_t)w * n));
-        const uint32_t by = y / kBlockY, bz = z / kBlockZ, see = gd_seen_by(used, y % kBlockY, z % kBlockZ, diagonal != 0);
+        const uint32_t by = y / kBlockY, bz = z / kBlockZ, see = block_seen_by(used, y % kBlockY, z % kBlockZ, diagonal != 0);
         for (uint32_t k = 0; k < 27u; ++k) {
             const uint32_t nx = xw + k % 3u - 1u, ny = by + (k / 3u) % 3u - 1u, nz = bz + k / 9u - 1u;   // wraps below 0: >= the count
             if (((see >> k) & 1u) && nx < w && ny < nb && nz < nb) flags[nx + w * (ny + nb * nz)] = 1u;
@@ -238,7 +226,7 @@ gd_relax(const uint32_t* __restrict__ mask, uint32_t* D, const uint32_t* __restr
     }
 
     lowered[t] = chg;
-    const uint32_t see = gd_seen_by(chg, ly, lz, W::diagonal) & ~(1u << 13);   // the neighbour blocks that see a changed voxel
+    const uint32_t see = block_seen_by(chg, ly, lz, W::diagonal) & ~(1u << 13);   // the neighbour blocks that see a changed voxel
     if (see) atomicOr(&seen, see);
     __syncthreads();
 #pragma unroll 4

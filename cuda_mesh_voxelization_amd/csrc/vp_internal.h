@@ -237,6 +237,15 @@ struct vp_ctx {
         vp::HostWords<uint64_t> host;
         uint64_t stats[4] = {};
     } gd;
+    // seeded watershed (watershed.hip): W (4 n^3 bytes) and the cut grid (n^3 / 8 bytes) of the last vp_watershed, which the context owns and
+    // vp_watershed_result hands out, and its four statistics; the key volume (8 n^3 bytes) and the counters with the presence bitmap of the
+    // levels, the range of P per block and TILED's block flags and list (block_list.h) or NAIVE's ring of round flags; the pinned host
+    // words they come back through
+    struct Wsd : vp::OwnedResult {
+        VP_BUFFERS(released, labels, cut, keys, aux)
+        vp::HostWords<uint32_t> host;
+        uint64_t stats[4] = {};
+    } wsd;
     // vp_extract_*: block counts / offsets of the last count call and what it was for (words = nullptr: nothing)
     struct Ext : vp::Feature {
         VP_BUFFERS(kept, cnt, off)
@@ -268,7 +277,7 @@ struct vp_ctx {
     // f(feature) for every feature of the context: how vp_ctx_release and vp_ctx_destroy find every buffer
     template <typename F> void each_feature(F f)
     {
-        f(ws); f(vox); f(cvox); f(fill); f(morph); f(comp); f(sn); f(edt); f(md); f(iso); f(wn); f(th); f(oc); f(ocx); f(sk); f(gd); f(ext); f(jfa);
+        f(ws); f(vox); f(cvox); f(fill); f(morph); f(comp); f(sn); f(edt); f(md); f(iso); f(wn); f(th); f(oc); f(ocx); f(sk); f(gd); f(wsd); f(ext); f(jfa);
     }
 };
 
@@ -340,6 +349,10 @@ void skeleton_table_cpu(int algo, uint32_t* h_table);
 // geodesic.hip: geodesic distances inside a mask from seed voxels and the reach grid, into the context's own buffers (blocks: the round
 // flags or the length of the block list are read back)
 int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const uint32_t* d_seeds, int metric, int algo, uint64_t* h_stats);
+// watershed.hip: seeded watershed / influence zones of a mask from a marker volume, labels and the cut grid into the context's own buffers
+// (blocks: a pre-pass, then the round flags or the length of the block list per level, are read back); d_priority may be null
+int launch_watershed(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const uint32_t* d_markers, const uint32_t* d_priority, int order,
+                     uint32_t quantum, int conn, int algo, uint64_t* h_stats);
 // meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,

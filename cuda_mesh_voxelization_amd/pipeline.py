@@ -228,6 +228,24 @@ class Engine:
         return (torch.as_tensor(_DeviceView(dd, frame.voxels, "<i4", self), device=self.device),
                 torch.as_tensor(_DeviceView(dr, frame.voxels // 32, "<i4", self), device=self.device), stats)
 
+    def watershed(self, frame: Frame, mask, markers, priority=None, order: int = capi.WS_DESCENDING, quantum: int = 1,
+                  connectivity: int = capi.CONN_6, algo: int = ALGO_TILED):
+        """Seeded watershed of a grid (n <= 1024): returns (labels, cut, stats) -- a tensor of n^3 labels, x fastest (0 where no marker
+        arrives and outside `mask`), the cut grid in the library's bit layout -- the labelled voxels that no neighbour with a larger
+        label touches: the parts, separated, ready for components(), thickness(), octree(), surface_nets() ... -- and (marker voxels used,
+        voxels labelled, levels present, voxels cut).  `markers` is an int32 tensor of n^3 labels (0 = none, 1 .. capi.WS_LABEL_MAX), as
+        components_label() writes it; `priority` an int32 tensor of n^3 values read as uint32, as edt() writes it, flooded in levels
+        priority // quantum from the high end (capi.WS_DESCENDING: what a distance map needs) or the low end (capi.WS_ASCENDING).
+        priority = None gives the geodesic influence zones of the markers: every voxel takes the label of the marker that is nearest
+        through the mask, the smaller label at equal hops.  Both tensors are VIEWS of buffers the context owns: they are overwritten by
+        the next watershed() and die with release() / close() -- clone() what has to live longer (also before one goes back in).
+        Blocking."""
+        stats = self.ctx.watershed(frame, mask.data_ptr(), markers.data_ptr(), 0 if priority is None else priority.data_ptr(), order, quantum,
+                                   connectivity, algo)
+        dl, dc, _, _ = self.ctx.watershed_result()
+        return (torch.as_tensor(_DeviceView(dl, frame.voxels, "<i4", self), device=self.device),
+                torch.as_tensor(_DeviceView(dc, frame.voxels // 32, "<i4", self), device=self.device), stats)
+
     def octree(self, frame: Frame, words, algo: int = ALGO_TILED):
         """Sparse voxel octree of a grid (n <= 1024): returns (nodes, level_offset, full_leaves) -- an int32 tensor of M x 2 words, the
         records (valid | full << 8, index of the first mixed child) breadth-first and in Morton order within a level, and two lists of 11:

@@ -710,6 +710,69 @@ int vp_geodesic_result(vp_ctx* ctx, uint32_t** d_dist, uint32_t** d_reach, uint6
 int vp_geodesic_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, const uint32_t* h_seeds, int metric, int algo,
                      uint32_t* h_dist, uint32_t* h_reach, uint64_t* h_stats /* any two may be NULL, not all three */);
 
+/* ---- seeded watershed and geodesic influence zones: split touching parts (no reference counterpart) ----------------
+ * Every operator above that produces regions stops at connectivity: two grains that touch are one component.  This is the marker-controlled
+ * watershed that MorphoLibJ calls "Distance Transform Watershed 3D": a priority field is flooded level by level from one marker per object
+ * and cut where the floods meet.  Without a priority field it gives the geodesic influence zones of the markers.
+ *   inputs      a whole-grid frame, n % 32 == 0, n <= 1024; a mask M, a bit grid (OUTSIDE THE GRID COUNTS AS NOT IN M); a marker volume L0,
+ *               one uint32 per voxel, x fastest like vp_components_label's output: 0 = no marker, labels 1 .. VP_WS_LABEL_MAX = 2^20 - 1;
+ *               markers outside M are ignored (their labels are not looked at); a label may cover several voxels and several blobs; an
+ *               optional priority field P, one uint32 per voxel in vp_edt's layout (its output can be passed as it is).
+ *   order       VP_WS_ASCENDING floods from low P, VP_WS_DESCENDING from high P (what a distance map needs: the caller inverts nothing).
+ *   levels      level(v) = P(v) / quantum (integer division, quantum >= 1) for v in M; the levels present in M are run in flood order.
+ *               P == NULL: ONE level that holds all of M -- the influence-zones mode; quantum and order are then ignored.  max - min of
+ *               the levels over M must be < VP_WS_MAX_SPAN = 16384: otherwise VP_ERR_INVALID, and the message names the smallest
+ *               quantum that fits.
+ *   flooding    W = L0 on M, 0 elsewhere.  For each present level h in flood order: A = { v in M : W(v) = 0, level(v) not later than h };
+ *               the sources are the voxels with W != 0 at the start of the level.  A path is a source u0 followed by v1 .. vk in A,
+ *               consecutive voxels being neighbours under `connectivity` (VP_CONN_6 / VP_CONN_26; a diagonal step needs no other voxel
+ *               set).  Its key is (k, level(u0), W(u0)), compared lexicographically, "level" in flood order: fewer hops win, then the
+ *               source that lies earlier in flood order, then the smaller label.  Every v in A that some path reaches takes the label of
+ *               its minimum key; all assignments of a level take effect together, and a voxel labelled in level h is a source, with its
+ *               own level(v), from the next level on.  After the last level the voxels of M with W = 0 are exactly those that no path in
+ *               M joins to a marker.
+ *               The source-level term keeps the lower label from creeping sideways along an interface one voxel per level (two equal
+ *               balls, exact D^2, quantum 1: no voxel off the symmetry plane with it, thousands without it).  At a coarse quantum the
+ *               sources share levels and the term does nothing: that is the contract, not a defect.
+ *   output W    the label volume, one uint32 per voxel (4 n^3 bytes).
+ *   output C    the CUT GRID, a bit grid: bit v is set iff W(v) != 0 and no neighbour u (same connectivity) has W(u) > W(v).  A
+ *               one-sided, one-voxel cut: no two voxels of C with different labels are neighbours, so C feeds vp_components_*,
+ *               vp_thickness, vp_octree and the meshers as "the parts, separated".
+ *   h_stats     { marker voxels used |L0 != 0 & M|, voxels labelled, distinct levels present in M (1 in zones mode, 0 for an empty M),
+ *               voxels cut = labelled - |C| }.  Nothing that depends on the number of rounds is reported.  With no marker in M: W = 0,
+ *               C empty, { 0, 0, levels, 0 }.
+ * Integer keys and a minimum over paths that is unique level by level: numpy, the C++ host form, VP_ALGO_NAIVE and VP_ALGO_TILED give the
+ * same bytes and statistics whatever the order of execution (the argument is in csrc/watershed.hip and DESIGN.md section 22).
+ *   vp_watershed         builds W and C into grow-only buffers that the CONTEXT owns; vp_ctx_release frees them.  BLOCKS: a pre-pass over
+ *                        M, L0 and P is read back once (min / max level, largest label, the levels present), then per present level the
+ *                        round flags (NAIVE) or the list length (TILED).
+ *   vp_watershed_result  pointers to the last W and C, the statistics and the side they are for; any argument may be NULL.  Before a
+ *                        build and after a release: NULL, zeros and side 0.
+ *   vp_watershed_host    host in, host out (staged through workspace slots); h_priority may be NULL; any two of h_labels / h_cut /
+ *                        h_stats may be NULL, not all three.
+ * A slab frame and n > 1024: VP_ERR_UNSUPPORTED.  Null ctx / f / mask / markers, a buffer that is not 16-byte aligned, an input
+ * overlapping a buffer the context writes in this call (the last W and C among them: copy them first), an unknown order (with P),
+ * connectivity or algo, quantum 0 (with P), a marker label in M above VP_WS_LABEL_MAX, a level span of VP_WS_MAX_SPAN or more:
+ * VP_ERR_INVALID.  The last two are found by the pre-pass, which writes scratch only: every refusal leaves the previous result as it was.
+ *   algo: both keep one 64-bit key per voxel (8 n^3 bytes of scratch), [arrival time : 30 | level rank of the source : 14 | label : 20],
+ *   read and written across workgroups with single 8-byte accesses.  VP_ALGO_NAIVE -- one lane per voxel from global memory, in place;
+ *   per level whole-grid launches repeat until one changes nothing.  VP_ALGO_TILED -- one workgroup per active block of 32 x 16 x 16
+ *   voxels, the keys and a one-voxel halo staged in LDS (about 90 KB: one workgroup per CU), swept until nothing changes or a fixed
+ *   number of sweeps ran; neighbour blocks are flagged as in vp_geodesic; the first list of a level is the blocks whose recorded range
+ *   of P meets the level.  Kernel boundaries are the only synchronisation between workgroups, and they separate the levels.
+ *   Timing books under existing keys: the pre-pass under VP_K_MD_FILL, the final W / C / counts launch under VP_K_MD_SPLIT, the block
+ *   lists under VP_K_MD_SCAN, the TILED rounds under VP_K_MD_BRICK, the NAIVE rounds under VP_K_MD_NAIVE. */
+enum { VP_WS_ASCENDING = 0, VP_WS_DESCENDING = 1 };
+#define VP_WS_LABEL_MAX 0xFFFFFu
+#define VP_WS_MAX_SPAN 16384u
+int vp_watershed(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_mask, const uint32_t* d_markers, const uint32_t* d_priority /* may be NULL */,
+                 int order, uint32_t quantum, int connectivity, int algo,
+                 uint64_t* h_stats /* 4, may be NULL: markers used, voxels labelled, levels present, voxels cut */);
+int vp_watershed_result(vp_ctx* ctx, uint32_t** d_labels, uint32_t** d_cut, uint64_t* h_stats /* 4 */, uint32_t* h_n);
+int vp_watershed_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, const uint32_t* h_markers, const uint32_t* h_priority /* may be NULL */,
+                      int order, uint32_t quantum, int connectivity, int algo, uint32_t* h_labels, uint32_t* h_cut,
+                      uint64_t* h_stats /* any two may be NULL, not all three */);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
