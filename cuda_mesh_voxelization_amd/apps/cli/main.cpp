@@ -51,6 +51,13 @@
 //                            and -s act on the separated parts.  Prints "watershed: n N, markers K, marker voxels U, labelled L, levels
 //                            H, cut X"; with -e writes out/<mesh stem>_<type>_labels.raw (n^3 uint32, x fastest); -d PREFIX additionally
 //                            writes PREFIX.labels.u32 (the labels of the first grid).
+//         --regions [C]      (extension) region analysis of the working grid after every grid operator (--morph, --fill, --watershed, CSG) and
+//                            before --thickness, --skeleton, --octree, --geodesic: its components (connectivity C = 6 | 26, default 26) are
+//                            labelled and measured (include/vphip.h, vp_regions; vox/regions.h) with the exact squared distance to the nearest
+//                            unset voxel as the value field (vp_edt, UNSET seeds: the per-region maximum is the squared radius, in voxels, of
+//                            the largest inscribed ball).  Writes out/<output stem>_<type>_regions.csv: one row per label -- the label, the 26
+//                            integers, then the derived columns with %.9g -- and prints "regions: n N, labels K, voxels V, non-empty L,
+//                            ignored I, interfaces F"; -d PREFIX additionally writes PREFIX.regions.u64 (K x 26 uint64).  One device only
 //         --geodesic S[:M]   (extension) geodesic distance inside the FINAL grid -- where --octree sits, after --thin-only and --skeleton-only, so
 //                            that "--skeleton curve --skeleton-only --geodesic zmin" measures the centre line: the length of the shortest path
 //                            that stays inside the grid from the seed voxels to every set voxel (include/vphip.h, vp_geodesic;
@@ -121,6 +128,7 @@
 #include "proc_utils.h"
 #include "vox/geodesic.h"
 #include "vox/watershed.h"
+#include "vox/regions.h"
 #include "vox/octree.h"
 #include "vox/skeleton.h"
 #include "vox/vox.h"
@@ -159,6 +167,8 @@ struct Options {
     bool watershed = false;                                 // --watershed R[:Q[:C]]
     unsigned wsRadius = 0, wsQuantum = 1;
     int wsConn = 6;
+    bool regions = false;                                   // --regions [6|26]
+    int regionsConn = 26;
     bool geodesic = false;                                  // --geodesic SEED[:METRIC]
     int geoSeed = 0, geoMetric = 2;                         // 0: zmin, 1: zmax, 2: the voxel geoVoxel; VOX::GeodesicMetric
     unsigned geoVoxel[3] = {0, 0, 0};
@@ -272,6 +282,10 @@ const char* kUsage =
     "                        squared distance map, from its high end in levels of Q (default 1), and cut where they meet.  The cut grid\n"
     "                        replaces the working grid, so every later step and export acts on the separated parts; -e also writes\n"
     "                        out/<mesh>_<type>_labels.raw, -d PREFIX.labels.u32.  One device (extension)\n"
+    "      --regions [arg]   Region analysis of the working grid after --morph, --fill, --watershed and the CSG: its components\n"
+    "                        (connectivity arg = 6 or 26, default 26) are measured -- volume, box, centroid, ellipsoid, surface, contact,\n"
+    "                        Euler number, and the squared radius of the largest inscribed ball from the exact distance map -- into\n"
+    "                        out/<output>_<type>_regions.csv, one row per label; -d PREFIX adds PREFIX.regions.u64.  One device (extension)\n"
     "      --geodesic arg    Geodesic distance inside the final grid (where --octree sits, after --thin-only and --skeleton-only): arg =\n"
     "                        SEED[:METRIC], SEED = zmin or zmax (the set voxels of the lowest / highest occupied z plane) or X,Y,Z (one set\n"
     "                        voxel), METRIC = 6 (face steps), 26 (all steps at cost 1) or chamfer (costs 3, 4, 5: divide by 3; default).\n"
@@ -318,7 +332,7 @@ Options Parse(int argc, char** argv)
 {
     static const std::map<std::string, char> longNames = {
         {"filenames", 'i'}, {"num-voxels", 'n'}, {"type", 't'}, {"output", 'o'}, {"operation", 'p'}, {"export", 'e'},
-        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"skeleton", 'K'}, {"skeleton-only", 'Q'}, {"geodesic", 'G'}, {"watershed", 'Z'}, {"help", 'h'}};
+        {"sdf", 's'}, {"block-size", 'b'}, {"benckmark", 'm'}, {"benchmark", 'm'}, {"dump", 'd'}, {"gpus", 'g'}, {"multi", 'M'}, {"verify", 'V'}, {"surface-only", 'S'}, {"conservative", 'C'}, {"fill", 'F'}, {"morph", 'R'}, {"surface-nets", 'N'}, {"exact-sdf", 'X'}, {"mesh-sdf", 'D'}, {"iso-nets", 'I'}, {"winding", 'W'}, {"thickness", 'T'}, {"thin-only", 'O'}, {"octree", 'Y'}, {"skeleton", 'K'}, {"skeleton-only", 'Q'}, {"geodesic", 'G'}, {"watershed", 'Z'}, {"regions", 'A'}, {"help", 'h'}};
     Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -357,6 +371,14 @@ Options Parse(int argc, char** argv)
                             (bt == 0.0 || (bt >= 1.0 && bt <= 64.0));
             cpuAssert(ok, "--winding: '" + v + "' is not LEVEL[:BETA] with a finite level and beta 0 or 1..64\n");
             o.windingLevel = static_cast<float>(lv); o.windingBeta = static_cast<float>(bt);
+            continue;
+        }
+        if (key == 'A') {
+            // the value is optional: the next argument is taken only if it is 6 or 26
+            o.regions = true;
+            if (!hasValue && i + 1 < argc && (std::strcmp(argv[i + 1], "6") == 0 || std::strcmp(argv[i + 1], "26") == 0)) { value = argv[++i]; hasValue = true; }
+            cpuAssert(!hasValue || value == "6" || value == "26", "--regions: '" + value + "' is not a connectivity: 6 or 26\n");
+            if (hasValue) o.regionsConn = std::stoi(value);
             continue;
         }
         const bool isSwitch = key == 'e' || key == 's' || key == 'h' || key == 'V' || key == 'S' || key == 'C' || key == 'F' || key == 'X' || key == 'O' || key == 'Y' || key == 'Q';
@@ -597,6 +619,41 @@ void WatershedSplit(unsigned radius, unsigned quantum, int conn, HostVoxelsGrid<
                 static_cast<unsigned long long>(st.cutVoxels));
 }
 
+// --regions: the components of `grid` are labelled and measured, with the squared distance to the nearest unset voxel as the value field;
+// writes the CSV, fills `table` and prints what the flag promises
+template <Types T>
+void Regions(int conn, const HostVoxelsGrid<gridType>& grid, const std::string& path, std::vector<VOX::RegionStats>& table)
+{
+    const size_t n = grid.View().VoxelsPerSide();
+    const double vs = grid.View().VoxelSize();
+    const float origin[3] = {grid.View().OriginX(), grid.View().OriginY(), grid.View().OriginZ()};
+    HostGrid<uint32_t> labels, dist;
+    const uint32_t count = VOX::LabelComponents<T>(grid, labels, conn);
+    cpuAssert(count <= VOX::REGIONS_MAX, "--regions: more than 2^20 - 1 components: remove the small ones first (--morph open:R)\n");
+    VOX::DistanceTransform<T>(grid, dist, VOX::EdtSeeds::UNSET);
+    VOX::RegionTotals totals{};
+    table = VOX::AnalyzeRegions<T>(labels, count, &dist, &totals);
+    std::FILE* f = std::fopen(path.c_str(), "w");
+    cpuAssert(f != nullptr, "Cannot write " + path + "\n");
+    std::fprintf(f, "label");
+    for (unsigned j = 0; j < VOX::REGION_WORDS; ++j) std::fprintf(f, ",w%u", j);
+    std::fprintf(f, ",volume,cx,cy,cz,cov_xx,cov_yy,cov_zz,cov_xy,cov_xz,cov_yz,surface,contact_area,sphericity,euler,value_mean\n");
+    for (uint32_t k = 0; k < count; ++k) {
+        const VOX::RegionStats& r = table[k];
+        std::fprintf(f, "%u", k + 1);
+        for (unsigned j = 0; j < VOX::REGION_WORDS; ++j) std::fprintf(f, ",%llu", static_cast<unsigned long long>(r.w[j]));
+        const auto c = r.Centroid(vs, origin);
+        const auto cov = r.Covariance(vs);
+        std::fprintf(f, ",%.9g,%.9g,%.9g,%.9g", r.Volume(vs), c[0], c[1], c[2]);
+        for (double v : cov) std::fprintf(f, ",%.9g", v);
+        std::fprintf(f, ",%.9g,%.9g,%.9g,%lld,%.9g\n", r.SurfaceArea(vs), r.ContactArea(vs), r.Sphericity(), static_cast<long long>(r.EulerNumber()), r.ValueMean());
+    }
+    std::fclose(f);
+    std::printf("regions: n %zu, labels %u, voxels %llu, non-empty %llu, ignored %llu, interfaces %llu, %s\n", n, count,
+                static_cast<unsigned long long>(totals.voxels), static_cast<unsigned long long>(totals.labels),
+                static_cast<unsigned long long>(totals.ignored), static_cast<unsigned long long>(totals.interfaces), path.c_str());
+}
+
 // --geodesic: the distance inside `grid` from the seeds `seed` names (0: the lowest occupied z plane, 1: the highest, 2: the voxel xyz) into
 // `dist` and `reach`; prints what the flag promises
 template <Types T>
@@ -695,6 +752,7 @@ int main(int argc, char** argv)
     cpuAssert(!(opt.skeletonOnly && opt.skeleton < 0), "--skeleton-only needs --skeleton curve|kernel\n");
     cpuAssert(!(opt.geodesic && opt.gpus > 1), "--geodesic runs on one device: -g must be 1\n");
     cpuAssert(!(opt.watershed && opt.gpus > 1), "--watershed runs on one device: -g must be 1\n");
+    cpuAssert(!(opt.regions && opt.gpus > 1), "--regions runs on one device: -g must be 1\n");
     cpuAssert(!(opt.geodesic && opt.geoSeed == 2 && (opt.geoVoxel[0] >= opt.numVoxels || opt.geoVoxel[1] >= opt.numVoxels || opt.geoVoxel[2] >= opt.numVoxels)),
               "--geodesic: the seed voxel lies outside the grid\n");
     cpuAssert(!(opt.octree && (opt.numVoxels % 32 != 0 || opt.numVoxels > 1024)), "--octree needs -n to be a multiple of 32 up to 1024\n");
@@ -749,8 +807,9 @@ int main(int argc, char** argv)
     HostGrid<uint32_t> thick;
     HostVoxelsGrid<gridType> thinGrid, skelGrid, geoReach;
     HostGrid<uint32_t> geoDist, wsLabels, wsFirst;
+    std::vector<VOX::RegionStats> regionTable;
     const std::string typeName = GetTypesString(TYPE);
-    if (EXPORT || opt.octree) std::filesystem::create_directories("out");
+    if (EXPORT || opt.octree || opt.regions) std::filesystem::create_directories("out");
 
     for (unsigned iter = 0; iter < opt.iterations; ++iter) {
         for (size_t i = 0; i < meshes.size(); ++i) {
@@ -823,6 +882,16 @@ int main(int argc, char** argv)
                 }
             }
             if (BENCHMARK) break;
+        }
+
+        if (opt.regions) {
+            const std::string path = "out/" + std::filesystem::path(opt.output).stem().string() + "_" + typeName + "_regions.csv";
+            switch (TYPE) {
+                case Types::SEQUENTIAL: Regions<Types::SEQUENTIAL>(opt.regionsConn, grids[0], path, regionTable); break;
+                case Types::OPENMP:     Regions<Types::OPENMP>(opt.regionsConn, grids[0], path, regionTable); break;
+                case Types::NAIVE:      Regions<Types::NAIVE>(opt.regionsConn, grids[0], path, regionTable); break;
+                case Types::TILED:      Regions<Types::TILED>(opt.regionsConn, grids[0], path, regionTable); break;
+            }
         }
 
         if (opt.thickness) {
@@ -962,6 +1031,7 @@ int main(int argc, char** argv)
         if (opt.sdf) WriteRaw(opt.dump + ".sdf.f32", sdf.View().Data(), sdf.View().Size() * sizeof(float));
         if (opt.thickness) WriteRaw(opt.dump + ".thick.u32", thick.View().Data(), thick.View().Size() * sizeof(uint32_t));
         if (opt.watershed) WriteRaw(opt.dump + ".labels.u32", wsFirst.View().Data(), wsFirst.View().Size() * sizeof(uint32_t));
+        if (opt.regions) WriteRaw(opt.dump + ".regions.u64", regionTable.data(), regionTable.size() * sizeof(VOX::RegionStats));
         if (opt.geodesic) {
             WriteRaw(opt.dump + ".geo.u32", geoDist.View().Data(), geoDist.View().Size() * sizeof(uint32_t));
             WriteRaw(opt.dump + ".reach.u32", geoReach.View().Data(), geoReach.View().StorageSize() * sizeof(gridType));

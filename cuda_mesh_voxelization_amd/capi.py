@@ -23,6 +23,7 @@ SKEL_KERNEL, SKEL_CURVE = 0, 1                                      # vp_skeleto
 GEO_6, GEO_26, GEO_CHAMFER = 0, 1, 2                                # vp_geodesic: face steps / all 26 steps at cost 1 / at cost 3, 4, 5
 WS_ASCENDING, WS_DESCENDING = 0, 1                                  # vp_watershed: flood from low / from high priority
 WS_LABEL_MAX, WS_MAX_SPAN = 0xFFFFF, 16384                          # vp_watershed: the largest marker label, the bound of the level span
+REGION_WORDS, REGIONS_MAX = 26, 0xFFFFF                             # vp_regions: uint64 words per record, the largest label count
 GEO_NONE = 0xFFFFFFFF                                               # vp_geodesic: "no path from a seed arrives here"
 COMP_KEEP_LARGEST, COMP_MIN_VOXELS = 0, 1                           # vp_components_filter modes
 EXTRACT_SET, EXTRACT_EXPOSED, EXTRACT_FACES = 0, 1, 2
@@ -78,6 +79,7 @@ SYMBOLS = [
     "vp_skeleton", "vp_skeleton_result", "vp_skeleton_host", "vp_skeleton_table_host",
     "vp_geodesic", "vp_geodesic_result", "vp_geodesic_host",
     "vp_watershed", "vp_watershed_result", "vp_watershed_host",
+    "vp_regions", "vp_regions_result", "vp_regions_host",
 ]
 
 
@@ -236,6 +238,9 @@ def lib():
         "vp_watershed": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp]),
         "vp_watershed_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
         "vp_watershed_host": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+        "vp_regions": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, _vp, ctypes.c_int, _vp]),
+        "vp_regions_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32), _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_regions_host": (ctypes.c_int, [_vp, fp, _vp, ctypes.c_uint32, _vp, ctypes.c_int, _vp, _vp]),
         "vp_csg": (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int]),
         "vp_jfa_workspace_bytes": (_sz, [fp]),
         "vp_jfa_id_bytes": (_sz, [fp]),
@@ -308,6 +313,59 @@ def skeleton_table(algo: int = ALGO_TILED, _ctx=None):
     t = np.empty(1 << 21, np.uint32)
     check(lib().vp_skeleton_table_host(_ctx, algo, t.ctypes.data_as(_vp)))
     return t
+
+
+REGION_DTYPE = [("label", "<u4"), ("voxels", "<u8"), ("volume", "<f8"), ("centroid", "<f8", 3), ("box_min", "<f8", 3), ("box_max", "<f8", 3),
+                ("covariance", "<f8", (3, 3)), ("eigenvalues", "<f8", 3), ("radii", "<f8", 3), ("surface", "<f8"), ("contact_area", "<f8"),
+                ("sphericity", "<f8"), ("euler", "<i8"), ("value_mean", "<f8"), ("value_min", "<f8"), ("value_max", "<f8"), ("first", "<u4", 3)]
+
+
+def region_table(raw, frame: Frame):
+    """The derived quantities of a vp_regions table (uint64, K x 26) in float64, a numpy structured array of K rows (REGION_DTYPE), in the
+    world units of `frame`: the volume V vs^3; the centroid (sum / V + 0.5) vs + origin; the bounding box (the low corner of the lowest
+    voxel, the high corner of the highest); the covariance matrix of the voxel centres plus 1/12 per axis for the voxel's own extent, times
+    vs^2; its eigenvalues in ascending order and the radii sqrt(5 lambda) of the ellipsoid with the same moments; the surface estimate
+    S = (2 / 3) F vs^2 from the exposed faces F of the three axis directions (Crofton: anisotropic, a few per cent on round shapes -- DESIGN.md
+    section 23); the contact area (contact faces x vs^2); the sphericity pi^(1/3) (6 volume)^(2/3) / S; the Euler number
+    n0 - n1 + (6 V + F) / 2 - V of the closed-cube complex (26-connected); mean / min / max of the value field; the first voxel (x, y, z).
+    An empty label (V = 0) reads zero everywhere.  These floats are NOT part of the byte contract: only the uint64 table is."""
+    np = __import__("numpy")
+    t = np.ascontiguousarray(raw).view(np.uint64).reshape(-1, REGION_WORDS).astype(np.int64)
+    out = np.zeros(t.shape[0], REGION_DTYPE)
+    n, vs = int(frame.n), float(frame.voxel_size)
+    origin = np.array([frame.origin[0], frame.origin[1], frame.origin[2]], np.float64)
+    v = t[:, 0]
+    some = v > 0
+    d = np.maximum(v, 1).astype(np.float64)
+    out["label"] = np.arange(1, t.shape[0] + 1)
+    out["voxels"] = v
+    out["volume"] = v * vs ** 3
+    out["centroid"] = np.where(some[:, None], (t[:, 7:10] / d[:, None] + 0.5) * vs + origin, 0.0)
+    out["box_min"] = np.where(some[:, None], t[:, 1:4] * vs + origin, 0.0)
+    out["box_max"] = np.where(some[:, None], (t[:, 4:7] + 1) * vs + origin, 0.0)
+    # second moments about an integer point near the middle of the box first, in exact int64 arithmetic (every term < 2^53): what is left for
+    # float64 is small numbers, so the subtraction of the squared mean loses nothing that matters
+    c = (t[:, 1:4] + t[:, 4:7]) // 2
+    s1 = t[:, 7:10] - c * v[:, None]
+    cov = np.zeros((t.shape[0], 3, 3), np.float64)
+    for a, b, word in ((0, 0, 10), (1, 1, 11), (2, 2, 12), (0, 1, 13), (0, 2, 14), (1, 2, 15)):
+        s2 = t[:, word] - c[:, a] * t[:, 7 + b] - c[:, b] * t[:, 7 + a] + c[:, a] * c[:, b] * v
+        cov[:, a, b] = cov[:, b, a] = s2 / d - (s1[:, a] / d) * (s1[:, b] / d) + (1.0 / 12.0 if a == b else 0.0)
+    cov[~some] = 0.0
+    out["covariance"] = cov * vs * vs
+    out["eigenvalues"] = np.linalg.eigvalsh(out["covariance"]) if t.shape[0] else 0.0
+    out["radii"] = np.sqrt(5.0 * np.maximum(out["eigenvalues"], 0.0))
+    faces = t[:, 16] + t[:, 17] + t[:, 18]
+    out["surface"] = (2.0 / 3.0) * faces * vs * vs
+    out["contact_area"] = t[:, 19] * vs * vs
+    out["sphericity"] = np.where(some, np.pi ** (1.0 / 3.0) * (6.0 * out["volume"]) ** (2.0 / 3.0) / np.maximum(out["surface"], 1e-300), 0.0)
+    out["euler"] = t[:, 20] - t[:, 21] + (6 * v + faces) // 2 - v
+    u = np.ascontiguousarray(raw).view(np.uint64).reshape(-1, REGION_WORDS)
+    out["value_mean"] = np.where(some, u[:, 22].astype(np.float64) / d, 0.0)
+    out["value_min"] = u[:, 23]
+    out["value_max"] = u[:, 24]
+    out["first"] = np.stack([t[:, 25] % n, (t[:, 25] // n) % n, t[:, 25] // (n * n)], 1)
+    return out
 
 
 class Context:
@@ -686,7 +744,34 @@ class Context:
         check(lib().vp_watershed_result(self._h, ctypes.byref(d), ctypes.byref(r), s, ctypes.byref(n)))
         return d.value or 0, r.value or 0, tuple(int(v) for v in s), int(n.value)
 
+    def regions(self, frame: Frame, d_labels: int, count: int, d_values: int = 0, algo: int = ALGO_TILED):
+        """Region analysis of a label volume (uint32 per voxel; labels 1 .. count, anything above is ignored) of a whole grid (n <= 1024),
+        with an optional value field (uint32 per voxel; 0: none), into a table the context owns: count records of REGION_WORDS uint64
+        (include/vphip.h, vp_regions); regions_result() hands it out.  Blocks (the totals are read back) and returns (sum of V, labels
+        with V > 0, voxels ignored, interfaces)."""
+        s = (ctypes.c_uint64 * 4)()
+        check(lib().vp_regions(self._h, ctypes.byref(frame), _vp(d_labels or None), count, _vp(d_values or None), algo, s))
+        return tuple(int(v) for v in s)
+
+    def regions_result(self):
+        """(d_table, count, stats, n) of the last regions(): the device pointer as an int (0 where there is none), the number of records,
+        the four statistics and the side they are for.  Valid until the next regions(), release() or close()."""
+        d, k, s, n = _vp(), ctypes.c_uint32(), (ctypes.c_uint64 * 4)(), ctypes.c_uint32()
+        check(lib().vp_regions_result(self._h, ctypes.byref(d), ctypes.byref(k), s, ctypes.byref(n)))
+        return d.value or 0, int(k.value), tuple(int(v) for v in s), int(n.value)
+
     # -- host-in / host-out (numpy arrays), the reference's Compute() convention
+    def regions_host(self, frame: Frame, h_labels, count: int, h_values=None, algo: int = ALGO_TILED, want=(True, True)):
+        """numpy in, numpy out: (table uint64[count, 26], statistics); want = which of the two are asked for (the other goes in as NULL and
+        comes back as None)."""
+        np = __import__("numpy")
+        t = np.zeros((count, REGION_WORDS), np.uint64) if want[0] else None
+        s = (ctypes.c_uint64 * 4)() if want[1] else None
+        check(lib().vp_regions_host(self._h, ctypes.byref(frame), h_labels.ctypes.data_as(_vp), count,
+                                    None if h_values is None else h_values.ctypes.data_as(_vp), algo,
+                                    None if t is None else t.ctypes.data_as(_vp), s))
+        return t, None if s is None else tuple(int(v) for v in s)
+
     def watershed_host(self, frame: Frame, h_mask, h_markers, h_priority=None, order: int = WS_DESCENDING, quantum: int = 1,
                        connectivity: int = CONN_6, algo: int = ALGO_TILED, want=(True, True, True)):
         """numpy in, numpy out: (labels uint32[n^3], cut words uint32[n^3 / 32], statistics); want = which of the three are asked for (the

@@ -177,7 +177,7 @@ static int host_round_trip(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_wor
 }
 
 // One path for the calls that build a result the context owns (vp_isonets, vp_winding, vp_thickness, vp_octree, vp_octree_expand,
-// vp_skeleton, vp_geodesic, vp_watershed): `ft` is the feature that is built, `also` what the call writes besides that feature's buffers, launch() the
+// vp_skeleton, vp_geodesic, vp_watershed, vp_regions): `ft` is the feature that is built, `also` what the call writes besides that feature's buffers, launch() the
 // work.  The inputs are read while every one of those buffers is written: an input that lies in one is refused (the last result has to be
 // copied before it goes back in); `inputs` is empty for the calls that have never refused it.  The context's own buffers are outputs
 // like any other: whatever was recorded about their bytes is gone -- about the bytes they hold now (a buffer that has to grow is freed
@@ -1376,6 +1376,42 @@ int vp_watershed_result(vp_ctx* ctx, uint32_t** d_labels, uint32_t** d_cut, uint
     return 0;
 }
 
+// ---- region analysis ----------------------------------------------------------------------------------
+// what vp_regions and its host form share: whole grids up to n = 1024, the algo, the bound of the label count
+static int check_regions(const vp_frame* f, const char* who, uint32_t count, int algo)
+{
+    VP_TRY(check_grid_1024(f, who, algo));
+    if (count > VP_REGIONS_MAX)
+        return set_error(VP_ERR_INVALID, "%s: count %u above VP_REGIONS_MAX = %u: filter the small components out first (minsize)", who, count,
+                         (uint32_t)VP_REGIONS_MAX);
+    return 0;
+}
+
+int vp_regions(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_labels, uint32_t count, const uint32_t* d_values, int algo, uint64_t* h_stats)
+{
+    const char* who = "vp_regions";
+    if (!ctx || !f || !d_labels) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_regions(f, who, count, algo));
+    VP_TRY(check_aligned(who, {d_labels, d_values}));
+    const size_t vb = vp_grid_voxels(f) * 4;                          // (a null value field overlaps nothing)
+    return build_owned(ctx, who, ctx->rg, {}, {{d_labels, vb}, {d_values, vb}}, [&] {
+        return launch_regions(ctx, make_frame(f), d_labels, count, d_values, algo, h_stats);
+    });
+}
+
+int vp_regions_result(vp_ctx* ctx, uint64_t** d_table, uint32_t* h_count, uint64_t* h_stats, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_regions_result: null ctx");
+    const bool any = ctx->rg.n != 0;
+    if (d_table) *d_table = any && ctx->rg.count ? (uint64_t*)ctx->rg.table.ptr : nullptr;
+    if (h_count) *h_count = any ? ctx->rg.count : 0;
+    if (h_stats)
+        for (int i = 0; i < 4; ++i) h_stats[i] = any ? ctx->rg.stats[i] : 0;
+    if (h_n) *h_n = ctx->rg.n;
+    return 0;
+}
+
 // ---- host-in / host-out ----------------------------------------------------------------------
 // Device buffers come from the context's workspace slots (grow-only): steady-state calls allocate nothing, where the
 // reference's Compute() does ~15 cudaMalloc/cudaFree per call.
@@ -1573,6 +1609,20 @@ int vp_watershed_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, co
     VP_TRY(vp_watershed(ctx, f, (const uint32_t*)dm, (const uint32_t*)dl, (const uint32_t*)dp, order, quantum, connectivity, algo, h_stats));
     if (h_labels) VP_TRY(vp_download(ctx, h_labels, ctx->wsd.labels.ptr, vb));
     return h_cut ? vp_download(ctx, h_cut, ctx->wsd.cut.ptr, wb) : 0;
+}
+
+int vp_regions_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_labels, uint32_t count, const uint32_t* h_values, int algo, uint64_t* h_table,
+                    uint64_t* h_stats)
+{
+    const char* who = "vp_regions_host";
+    if (!ctx || !f || !h_labels || (!h_table && !h_stats)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_regions(f, who, count, algo));
+    void *dl = nullptr, *dv = nullptr;
+    const size_t vb = vp_grid_voxels(f) * 4;
+    VP_TRY(stage(ctx, SLOT_SDF, h_labels, vb, &dl));
+    if (h_values) VP_TRY(stage(ctx, SLOT_NEAREST, h_values, vb, &dv));
+    VP_TRY(vp_regions(ctx, f, (const uint32_t*)dl, count, (const uint32_t*)dv, algo, h_stats));
+    return h_table && count ? vp_download(ctx, h_table, ctx->rg.table.ptr, (size_t)count * VP_REGION_WORDS * 8) : 0;
 }
 
 int vp_skeleton_table_host(vp_ctx* ctx, int algo, uint32_t* h_table)

@@ -246,6 +246,15 @@ struct vp_ctx {
         vp::HostWords<uint32_t> host;
         uint64_t stats[4] = {};
     } wsd;
+    // region analysis (regions.hip): the table of the last vp_regions (26 x 8 bytes per label), which the context owns and
+    // vp_regions_result hands out, its label count and four statistics; the four device totals and the pinned host words they come back through
+    struct Rg : vp::OwnedResult {
+        VP_BUFFERS(released, table, aux)
+        vp::HostWords<uint64_t> host;
+        uint32_t count = 0;
+        uint64_t stats[4] = {};
+        void forget() { OwnedResult::forget(); count = 0; }
+    } rg;
     // vp_extract_*: block counts / offsets of the last count call and what it was for (words = nullptr: nothing)
     struct Ext : vp::Feature {
         VP_BUFFERS(kept, cnt, off)
@@ -277,7 +286,7 @@ struct vp_ctx {
     // f(feature) for every feature of the context: how vp_ctx_release and vp_ctx_destroy find every buffer
     template <typename F> void each_feature(F f)
     {
-        f(ws); f(vox); f(cvox); f(fill); f(morph); f(comp); f(sn); f(edt); f(md); f(iso); f(wn); f(th); f(oc); f(ocx); f(sk); f(gd); f(wsd); f(ext); f(jfa);
+        f(ws); f(vox); f(cvox); f(fill); f(morph); f(comp); f(sn); f(edt); f(md); f(iso); f(wn); f(th); f(oc); f(ocx); f(sk); f(gd); f(wsd); f(rg); f(ext); f(jfa);
     }
 };
 
@@ -353,6 +362,9 @@ int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const u
 // (blocks: a pre-pass, then the round flags or the length of the block list per level, are read back); d_priority may be null
 int launch_watershed(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const uint32_t* d_markers, const uint32_t* d_priority, int order,
                      uint32_t quantum, int conn, int algo, uint64_t* h_stats);
+// regions.hip: the per-label records of a label volume (volume, box, moments, faces, lattice points and edges, values) into the context's own
+// table (blocks once: the four totals are read back); d_values may be null
+int launch_regions(vp_ctx* ctx, const Frame& f, const uint32_t* d_labels, uint32_t count, const uint32_t* d_values, int algo, uint64_t* h_stats);
 // meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,

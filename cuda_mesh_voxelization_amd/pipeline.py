@@ -246,6 +246,20 @@ class Engine:
         return (torch.as_tensor(_DeviceView(dl, frame.voxels, "<i4", self), device=self.device),
                 torch.as_tensor(_DeviceView(dc, frame.voxels // 32, "<i4", self), device=self.device), stats)
 
+    def regions(self, frame: Frame, labels, count: int, values=None, algo: int = ALGO_TILED):
+        """Region analysis of a label volume (n <= 1024): returns (table, stats) -- an int64 tensor (count, 26), one record per label
+        1 .. count as include/vphip.h lays it out (read the words as uint64: voxels, bounding box, first and second moments, exposed and
+        contact faces, lattice points and edges, sum / min / max of `values`, first voxel; capi.region_table(table.cpu().numpy(), frame)
+        derives centroid, ellipsoid, surface, Euler number ...), and (sum of V, labels with V > 0, voxels ignored, interfaces).  `labels` is
+        an int32 tensor of n^3 labels as components_label() and watershed() write it (labels above `count` are ignored), `values` an
+        optional int32 tensor of n^3 values read as uint32, as edt() writes it.  The tensor is a VIEW of a buffer the context owns: it is
+        overwritten by the next regions() and dies with release() / close() -- clone() what has to live longer.  Blocking."""
+        stats = self.ctx.regions(frame, labels.data_ptr(), count, 0 if values is None else values.data_ptr(), algo)
+        dt, k, _, _ = self.ctx.regions_result()
+        if k == 0:
+            return torch.zeros((0, capi.REGION_WORDS), dtype=torch.int64, device=self.device), stats
+        return torch.as_tensor(_DeviceView(dt, k * capi.REGION_WORDS, "<i8", self), device=self.device).view(k, capi.REGION_WORDS), stats
+
     def octree(self, frame: Frame, words, algo: int = ALGO_TILED):
         """Sparse voxel octree of a grid (n <= 1024): returns (nodes, level_offset, full_leaves) -- an int32 tensor of M x 2 words, the
         records (valid | full << 8, index of the first mixed child) breadth-first and in Morton order within a level, and two lists of 11:

@@ -773,6 +773,57 @@ int vp_watershed_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, co
                       int order, uint32_t quantum, int connectivity, int algo, uint32_t* h_labels, uint32_t* h_cut,
                       uint64_t* h_stats /* any two may be NULL, not all three */);
 
+/* ---- region analysis: per-label volume, moments, surface, Euler number (no reference counterpart) -------------------
+ * The last step of voxelize -> repair -> split -> measure: what MorphoLibJ calls "Analyze Regions 3D".  vp_components_sizes stops at one
+ * voxel count per label; this gives, per label of a label volume, everything that is an integer sum, minimum or maximum over voxels.
+ *   inputs      a whole-grid frame, n % 32 == 0, n <= 1024; a label volume W, one uint32 per voxel, x fastest: what vp_components_label
+ *               and vp_watershed write; count = K <= VP_REGIONS_MAX = 2^20 - 1 (= VP_WS_LABEL_MAX); an optional value field, one uint32 per
+ *               voxel in vp_edt's layout (D^2, T2, a geodesic distance: any uint32).
+ *   label       the EFFECTIVE LABEL of a voxel is l(v) = W(v) if 1 <= W(v) <= K, else 0: labels above K are ignored, as
+ *               vp_components_sizes ignores them; A VOXEL OUTSIDE THE GRID HAS l = 0.  Voxel coordinates are the integers x, y, z in
+ *               0 .. n - 1; the frame's origin and voxel size enter only the derived quantities of the wrappers.
+ *   output      a table of K records of VP_REGION_WORDS = 26 uint64; record k - 1 belongs to label k:
+ *                 0        V: voxels with l = k
+ *                 1 - 3    min x, y, z over them            4 - 6    max x, y, z
+ *                 7 - 9    sum x, y, z                      10 - 15  sum x^2, y^2, z^2, xy, xz, yz
+ *                 16 - 18  exposed faces with normal +-x, +-y, +-z: faces of a voxel of k whose neighbour across the face has l != k
+ *                          (background, another label or outside the grid)
+ *                 19       contact faces: those exposed faces (all axes) whose neighbour has l != 0
+ *                 20       n0: lattice points with at least one of their 8 incident voxels in k
+ *                 21       n1: lattice edges with at least one of their 4 incident voxels in k
+ *                 22 - 24  sum, min, max of the value field over k (0, 0, 0 when d_values is NULL)
+ *                 25       the lowest linear index x + n (y + n z) of a voxel of k
+ *               A label with V = 0 has an ALL-ZERO record.  The Euler number of the closed-cube complex of k (26-connected foreground,
+ *               the convention of vp_skeleton) is chi = n0 - n1 + n2 - V with n2 = (6 V + F) / 2, F = words 16 + 17 + 18: the faces of
+ *               the complex follow from the exposed ones, so n2 is not stored.  Every sum fits: sum x^2 <= 1023^2 * 2^30 < 2^51, the sum
+ *               of the values <= (2^32 - 1) * 2^30 < 2^62.
+ *   h_stats     { sum of V, labels with V > 0, voxels with W > K (ignored), interfaces = sum of the contact faces / 2 }.
+ * Every word is an integer sum, minimum or maximum, so numpy, the C++ host form, VP_ALGO_NAIVE and VP_ALGO_TILED give the same bytes whatever
+ * the order of execution.
+ *   vp_regions         builds the table into a grow-only buffer that the CONTEXT owns; vp_ctx_release frees it.  BLOCKS: the four totals
+ *                      are read back.  count = 0 is legal: an empty table, and the statistics still report the ignored voxels.
+ *   vp_regions_result  the last table, its K, the statistics and the side they are for; any argument may be NULL.  Before a build and
+ *                      after a release: NULL, zeros and side 0.
+ *   vp_regions_host    host in, host out (staged through workspace slots); h_values may be NULL; one of h_table / h_stats may be NULL,
+ *                      not both.
+ * A slab frame and n > 1024: VP_ERR_UNSUPPORTED.  Null ctx / f / labels, a buffer that is not 16-byte aligned, count above VP_REGIONS_MAX
+ * (filter with vp_components_filter's minsize first), an unknown algo, an input overlapping the context's table: VP_ERR_INVALID.  Every
+ * refusal leaves the previous result as it was.
+ *   algo: VP_ALGO_NAIVE -- one lane per voxel from global memory: its 26 neighbours, then up to 26 global 64-bit atomics.  VP_ALGO_TILED --
+ *   one workgroup per block of 32 x 16 x 16 voxels, labels and a one-voxel halo staged in LDS; a lane walks an x row and keeps the run of
+ *   its current label in registers in block-local coordinates (every block-local sum but the value sum fits 32 bits), flushes it at a
+ *   change of label into one of 16 label slots in LDS, and the occupied slots are shifted to grid coordinates in 64-bit arithmetic and
+ *   go out with 26 global atomics per (block, label); a label that finds no free slot sends its runs straight to the table.
+ *   Timing books under existing keys: the clear launch under VP_K_MD_FILL, the finishing launch under VP_K_MD_SPLIT, the TILED kernel
+ *   under VP_K_MD_BRICK, the NAIVE kernel under VP_K_MD_NAIVE. */
+#define VP_REGION_WORDS 26
+#define VP_REGIONS_MAX 0xFFFFFu
+int vp_regions(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_labels, uint32_t count, const uint32_t* d_values /* may be NULL */, int algo,
+               uint64_t* h_stats /* 4, may be NULL: sum of V, labels with V > 0, voxels ignored, interfaces */);
+int vp_regions_result(vp_ctx* ctx, uint64_t** d_table, uint32_t* h_count, uint64_t* h_stats /* 4 */, uint32_t* h_n);
+int vp_regions_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_labels, uint32_t count, const uint32_t* h_values /* may be NULL */, int algo,
+                    uint64_t* h_table /* count * 26, may be NULL */, uint64_t* h_stats /* may be NULL, not both */);
+
 /* ---- CSG ----------------------------------------------------------------------------------
  * Stands behind CSG::Compute<Types::NAIVE,T,func>(grid1, grid2, Op) (vplib/src/csg/csg.h:35-36,
  * csg/naive.cu:26-64): d_a[i] = d_a[i] op d_b[i] with the functors of csg.h:14-30. */
