@@ -54,7 +54,7 @@ def build_lib(force: bool = False, verbose: bool = False, hooks: bool = False) -
     """libvphip.so; hooks=True: also libvphip_hooks.so -- the same objects except vox.hip / multi.hip / cvox.hip / meshdist.hip compiled with -DVP_TEST_HOOKS, the
     build the tests that force rare paths load (the default library reads no environment variable on any call path)."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "vp_internal.h"), os.path.join(CSRC, "jfa_common.h"), os.path.join(CSRC, "wg_scan.h"), os.path.join(CSRC, "block_list.h"), os.path.join(CSRC, "skeleton_simple.h"), os.path.join(ROOT, "include", "vphip.h")]
+    deps = srcs + sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(ROOT, "include", "vphip.h")]
     objdir = os.path.join(PKG, "build")
     flags = [f for f in HIP_FLAGS if f != "-shared"]
 

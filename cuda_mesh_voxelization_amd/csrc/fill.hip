@@ -2,7 +2,7 @@
 //
 // A voxel is EXTERIOR if it is not set and lies on the grid boundary or is face-adjacent (6-connectivity) to an exterior voxel; the
 // result is the complement of the exterior set E (= scipy.ndimage.binary_fill_holes with its default structure).  d_out holds E while
-// the fill runs; fill_final writes NOT E over it.  The only other memory is the context's flag ring (2 kFillBatch words).
+// the fill runs; fill_final writes NOT E over it.  The only other memory is the context's flag ring (2 kFillBatch words, round_ring.h).
 //
 // A ROUND is three sweeps, each of which carries E through the runs of empty voxels (p = NOT W) along one axis, over the whole length of
 // the axis, in both directions, in one launch:
@@ -18,17 +18,14 @@
 //            of a plane (z sweep) or of a row x several z (y sweep).
 //   fill_final  out = NOT E, 16 B per lane.
 //
-// Convergence without a sync per round: round r has its own flag word in a ring of 2 kFillBatch words, zeroed (hipMemsetAsync) when its
-// batch is enqueued.  A kernel that changes a word of E stores 1 into its round's flag (a plain store: the value is idempotent and the
-// kernel boundary makes it visible); every kernel of round r + 1 reads flag r first and returns at once if it is 0.  The host enqueues
-// kFillBatch rounds, reads the batch's flags back once, and stops at the first round that changed nothing.  The last flag of a batch lives
-// in the other half of the ring, so the next batch's first round can still read it.  No persistent kernel, grid barrier or hand-off
-// between workgroups: kernel boundaries are the only synchronisation.
+// Convergence without a sync per round: the flag ring and the batched host loop of round_ring.h, kFillBatch rounds per read-back; every
+// kernel of a round is handed the previous round's flag and its own.
 //
 // Order-free: within one launch every word of E has exactly one writer (its row lane / its column segment) and is stored only when it
 // changed; a sweep only adds bits of NOT W that a 6-path inside NOT W connects to bits already in E.  E therefore only grows and stays a
 // subset of the exterior; the carries combined from other segments are lower bounds, so anything missed in one round is found by a
 // later one, and a round that changes nothing proves E closed under the 6-neighbour step, i.e. E is the exterior.
+#include "round_ring.h"
 #include "vp_internal.h"
 
 #include <algorithm>
@@ -49,18 +46,12 @@ __device__ __forceinline__ uint32_t fill_word(uint32_t s, uint32_t p)
     return run_up(p, s) | __builtin_bitreverse32(run_up(__builtin_bitreverse32(p), __builtin_bitreverse32(s)));
 }
 
-// the round's flag: one plain store per wave that changed a word
-__device__ __forceinline__ void mark(bool changed, uint32_t* cur)
-{
-    if (__any(changed) && (threadIdx.x & 63) == 0) *cur = 1u;
-}
-
 // Row sweep (x).  Lane `sub` of a segment of L = 1 << lshift lanes holds word `sub` of a row (lanes >= w hold p = e = 0).
 __global__ void __launch_bounds__(256)
 fill_x(const uint32_t* __restrict__ W, uint32_t* __restrict__ E, uint32_t n, uint32_t w, uint32_t lshift, int seed,
        const uint32_t* prev, uint32_t* cur)
 {
-    if (prev && *prev == 0u) return;
+    if (round_skip(prev)) return;
     const uint32_t L = 1u << lshift;
     const uint32_t sub = threadIdx.x & (L - 1);
     const uint64_t rows = (uint64_t)n * n;
@@ -104,7 +95,7 @@ fill_x(const uint32_t* __restrict__ W, uint32_t* __restrict__ E, uint32_t n, uin
             changed |= res != 0u;
         }
     }
-    mark(changed, cur);
+    round_mark(changed, cur);
 }
 
 // Column sweep along y (AXIS 1) or z (AXIS 2).  Column c in [0, n w): z sweep -- word c of a plane, stride n w; y sweep -- word c % w of
@@ -114,7 +105,7 @@ __global__ void __launch_bounds__(kYZThreads)
 fill_yz(const uint32_t* __restrict__ W, uint32_t* __restrict__ E, uint32_t n, uint32_t w, uint32_t C,
         const uint32_t* prev, uint32_t* cur)
 {
-    if (prev && *prev == 0u) return;
+    if (round_skip(prev)) return;
     __shared__ uint32_t s_gu[kYZThreads], s_gd[kYZThreads], s_p[kYZThreads];
     const uint32_t S = kYZThreads / C;
     const uint32_t Ls = n / S;
@@ -184,7 +175,7 @@ fill_yz(const uint32_t* __restrict__ W, uint32_t* __restrict__ E, uint32_t n, ui
             }
         }
     }
-    mark(changed, cur);
+    round_mark(changed, cur);
 }
 
 __global__ void __launch_bounds__(256)
@@ -206,7 +197,7 @@ int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint3
     const size_t nwords = (size_t)n * n * w;
     VP_TRY(reserve(ctx, ctx->fill.flags, 2 * kFillBatch * sizeof(uint32_t), false));
     VP_TRY(ctx->fill.host.need(kFillBatch));
-    uint32_t* flags = (uint32_t*)ctx->fill.flags.ptr;
+    const RoundRing ring{(uint32_t*)ctx->fill.flags.ptr, kFillBatch, ctx->fill.host.p};
 
     uint32_t lshift = 0;
     while ((1u << lshift) < w) ++lshift;
@@ -216,33 +207,20 @@ int launch_fill_interior(vp_ctx* ctx, uint32_t n, const uint32_t* d_words, uint3
     const unsigned yzblocks = (unsigned)std::min<size_t>((nwords / n + C - 1) / C, (size_t)ctx->cus * 4);
 
     uint32_t rounds = 0;
-    for (uint32_t batch = 0;; ++batch) {
-        uint32_t* fl = flags + (batch & 1) * kFillBatch;
-        const uint32_t* last = flags + ((batch + 1) & 1) * kFillBatch + kFillBatch - 1;   // previous batch's last round
-        VP_HIP(hipMemsetAsync(fl, 0, kFillBatch * sizeof(uint32_t), st));
-        for (uint32_t i = 0; i < kFillBatch; ++i) {
-            const uint32_t r = batch * kFillBatch + i;
-            const uint32_t* prev = r == 0 ? nullptr : (i == 0 ? last : fl + i - 1);
-            {
-                ProfScope p(ctx, VP_K_FILL_X);
-                hipLaunchKernelGGL(fill_x, dim3(xblocks), dim3(256), 0, st, d_words, d_out, n, w, lshift, r == 0 ? 1 : 0, prev, fl + i);
-            }
-            {
-                ProfScope p(ctx, VP_K_FILL_Y);
-                hipLaunchKernelGGL(fill_yz<1>, dim3(yzblocks), dim3(kYZThreads), 0, st, d_words, d_out, n, w, C, prev, fl + i);
-            }
-            {
-                ProfScope p(ctx, VP_K_FILL_Z);
-                hipLaunchKernelGGL(fill_yz<2>, dim3(yzblocks), dim3(kYZThreads), 0, st, d_words, d_out, n, w, C, prev, fl + i);
-            }
+    VP_TRY(run_rounds(st, ring, &rounds, nullptr, [&](uint32_t r, const uint32_t* prev, uint32_t* cur) {
+        {
+            ProfScope p(ctx, VP_K_FILL_X);
+            hipLaunchKernelGGL(fill_x, dim3(xblocks), dim3(256), 0, st, d_words, d_out, n, w, lshift, r == 0 ? 1 : 0, prev, cur);
         }
-        VP_HIP(hipGetLastError());
-        VP_HIP(hipMemcpyAsync(ctx->fill.host, fl, kFillBatch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        VP_HIP(hipStreamSynchronize(st));
-        uint32_t i = 0;
-        while (i < kFillBatch && ctx->fill.host[i]) ++i;
-        if (i < kFillBatch) { rounds = batch * kFillBatch + i + 1; break; }
-    }
+        {
+            ProfScope p(ctx, VP_K_FILL_Y);
+            hipLaunchKernelGGL(fill_yz<1>, dim3(yzblocks), dim3(kYZThreads), 0, st, d_words, d_out, n, w, C, prev, cur);
+        }
+        {
+            ProfScope p(ctx, VP_K_FILL_Z);
+            hipLaunchKernelGGL(fill_yz<2>, dim3(yzblocks), dim3(kYZThreads), 0, st, d_words, d_out, n, w, C, prev, cur);
+        }
+    }));
     {
         const size_t nvec = nwords / 4;      // n % 32 == 0: whole uint4s; d_out is 16-byte aligned (checked at the ABI)
         const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, (size_t)ctx->cus * 16));

@@ -7,23 +7,19 @@
 //          gd_final   one lane per voxel: the reach grid (one ballot = 64 bits = two words), the reached count and the key
 //                     (D << 32 | ~index) of the farthest voxel, reduced over the workgroup and then with one atomicMax: the larger D wins,
 //                     among equal D the lower index, whichever workgroup comes first
-//   NAIVE  gd_naive   one lane per voxel of M, global memory only, in place.  Whole-grid launches repeat until one changes nothing; round r
-//                     has its own flag word in a ring of 2 kGeoBatch words (fill.hip): a launch that lowers a value stores 1 into its
-//                     round's flag, the launches of round r + 1 read flag r first and return at once if it is 0, the host reads a batch
-//                     of flags back at a time.
+//   NAIVE  gd_naive   one lane per voxel of M, global memory only, in place.  Whole-grid launches repeat until one changes nothing, kGeoBatch
+//                     rounds per read-back of their flags (round_ring.h).
 //   TILED  gd_relax   one workgroup per ACTIVE block of 32 x 16 x 16 voxels, 256 lanes = one per x row.  The block's D and a one-voxel halo
-//                     are staged in LDS (18 x 18 rows of 34 values, row pitch 35 words = 45,360 B: three workgroups per CU; the odd pitch
-//                     keeps the 32 rows that a half-wave reads on distinct banks but for two), the lane's mask row is a register.  One
+//                     are staged in LDS (the tile of block_list.h: 45,360 B, three workgroups per CU), the lane's mask row is a register.  One
 //                     sweep: the lane walks along its row with a sliding window of column minima over the eight rows around it (9 LDS
 //                     reads per voxel), then relaxes forward and backward along its own row in registers (exact for the face weight) and
 //                     stores what it lowered.  Sweeps repeat until one lowers nothing in the block or kGeoSweeps have run; then the
 //                     values that changed are written back, by the lanes along x.
-//          block_list (block_list.h)  the list of active blocks by count -> scan -> write from the block flags, which it clears (one workgroup).  A block
-//                     whose face, edge or corner voxel changed raises, with plain stores of 1, the flags of exactly the neighbour blocks
-//                     whose halo holds that voxel (face neighbours only for VP_GEO_6); a block that was still changing at the sweep cap
-//                     raises its own.  The first list is the blocks whose tile holds a used seed, in its interior OR in its halo (gd_init
-//                     raises them by the same rule: a seed reads 0 from the start and is never "changed"); the host loop ends with the
-//                     first empty list.
+//          block_list (block_list.h)  the list of active blocks from the block flags.  A block whose face, edge or corner voxel changed
+//                     raises the flags of exactly the neighbour blocks whose halo holds that voxel (face neighbours only for VP_GEO_6);
+//                     a block that was still changing at the sweep cap raises its own.  The first list is the blocks whose tile holds a
+//                     used seed, in its interior OR in its halo (gd_init raises them by the same rule: a seed reads 0 from the start and
+//                     is never "changed"); the host loop ends with the first empty list.
 // Order-free, for both: (1) every voxel of D has one writer in any launch -- its own lane (NAIVE), the workgroup of its block, which the
 // list names once (TILED).  (2) Values only decrease: a value is stored only where it is smaller than the one read.  (3) Every value ever
 // stored is 0 at a used seed or D[q] + w for a stored D[q] and an allowed step, so by induction it is the cost of a real path from a seed
@@ -39,6 +35,7 @@
 // is monotone and changes none of it.
 // Kernel boundaries are the only synchronisation between workgroups; every device loop has a compile-time bound.
 #include "block_list.h"
+#include "round_ring.h"
 #include "vp_internal.h"
 
 #include <algorithm>
@@ -49,9 +46,6 @@ namespace {
 
 constexpr uint32_t kGeoSweeps = 64;  // TILED: sweeps over a block per launch at most (tests/test_geodesic_gpu.py reads this line)
 constexpr uint32_t kGeoBatch = 8;    // NAIVE: rounds enqueued between two read-backs of their flags
-constexpr uint32_t kHalo = 18;                                    // staged rows per axis of a block (block_list.h: one lane per x row)
-constexpr uint32_t kRowVals = 34, kRowPitch = 35;                 // staged values per row (x - 1 .. x + 32) and the pitch in words
-constexpr uint32_t kStaged = kHalo * kHalo * kRowVals;            // 11,016 values
 constexpr uint32_t kNone = VP_GEO_NONE, kMax = VP_GEO_MAX;
 // the counters in front of the flags: kAuxHead bytes, of which seeds used (u64) | voxels reached (u64) | key of the farthest voxel (u64) |
 // active blocks (u32) are in use; kCnt* = where each starts, in 32-bit words
@@ -79,12 +73,10 @@ gd_init(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ seeds, u
     const uint32_t used = mask[word] & seeds[word], s = used >> ((uint32_t)(i & 7u) * 4u);
     D[i] = make_uint4((s & 1u) ? 0u : kNone, (s & 2u) ? 0u : kNone, (s & 4u) ? 0u : kNone, (s & 8u) ? 0u : kNone);
     if ((i & 7u) == 0 && used != 0u && flags) {
-        const uint32_t w = n / 32, nb = n / kBlockY, xw = (uint32_t)(word % w), y = (uint32_t)((word / w) % n), z = (uint32_t)(word / ((size_t)w * n));
-        const uint32_t by = y / kBlockY, bz = z / kBlockZ, see = block_seen_by(used, y % kBlockY, z % kBlockZ, diagonal != 0);
-        for (uint32_t k = 0; k < 27u; ++k) {
-            const uint32_t nx = xw + k % 3u - 1u, ny = by + (k / 3u) % 3u - 1u, nz = bz + k / 9u - 1u;   // wraps below 0: >= the count
-            if (((see >> k) & 1u) && nx < w && ny < nb && nz < nb) flags[nx + w * (ny + nb * nz)] = 1u;
-        }
+        const uint32_t w = n / 32, y = (uint32_t)((word / w) % n), z = (uint32_t)(word / ((size_t)w * n));
+        const BlockAt at{(uint32_t)(word % w), y / kBlockY, z / kBlockZ, w, n / kBlockY};
+        const uint32_t see = block_seen_by(used, y % kBlockY, z % kBlockZ, diagonal != 0);
+        for (uint32_t k = 0; k < 27u; ++k) block_raise(flags, see, at, k);
     }
     const unsigned long long sum = wg_sum_256((unsigned long long)__popc(s & 15u), smem);
     if (threadIdx.x == 0 && sum) atomicAdd(&counters[kCntSeeds / 2], sum);
@@ -96,11 +88,7 @@ gd_final(const uint32_t* __restrict__ D, uint32_t* __restrict__ reach, unsigned 
     __shared__ unsigned long long smem[4], kmem[4];
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t d = D[i];
-    const unsigned long long hit = __ballot(d != kNone);
-    if ((threadIdx.x & 63u) == 0) {
-        reach[i >> 5] = (uint32_t)hit;
-        reach[(i >> 5) + 1] = (uint32_t)(hit >> 32);
-    }
+    store_ballot(reach, i, d != kNone);
     unsigned long long key = d != kNone ? ((unsigned long long)d << 32) | (0xFFFFFFFFu - (uint32_t)i) : 0ull;   // i < 2^30
     for (int s = 32; s >= 1; s >>= 1) key = max(key, (unsigned long long)__shfl_xor(key, s));
     if ((threadIdx.x & 63u) == 0) kmem[threadIdx.x >> 6] = key;
@@ -117,7 +105,7 @@ template <int METRIC>
 __global__ void __launch_bounds__(256)
 gd_naive(const uint32_t* __restrict__ mask, uint32_t* D, uint32_t n, const uint32_t* prev, uint32_t* cur)
 {
-    if (prev && *prev == 0u) return;
+    if (round_skip(prev)) return;
     using W = Weights<METRIC>;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     bool changed = false;
@@ -138,7 +126,7 @@ gd_naive(const uint32_t* __restrict__ mask, uint32_t* D, uint32_t n, const uint3
             changed = true;
         }
     }
-    if (__any(changed) && (threadIdx.x & 63u) == 0) *cur = 1u;
+    round_mark(changed, cur);
 }
 
 // ---- TILED -------------------------------------------------------------------------------------------------------------------------
@@ -170,20 +158,15 @@ gd_relax(const uint32_t* __restrict__ mask, uint32_t* D, const uint32_t* __restr
     __shared__ uint32_t tile[kHalo * kHalo * kRowPitch];
     __shared__ uint32_t lowered[256];                              // per row: the voxels that changed in this launch
     __shared__ uint32_t seen;                                      // the neighbour blocks whose halo holds a changed voxel
-    const uint32_t t = threadIdx.x, w = n / 32, nb = n / kBlockY, b = list[blockIdx.x];
-    const uint32_t bx = b % w, by = (b / w) % nb, bz = b / (w * nb);
-    for (uint32_t k = 0; k < (kStaged + 255u) / 256u; ++k) {
-        const uint32_t e = k * 256u + t;
-        if (e < kStaged) {
-            const uint32_t c = e % kRowVals, r = e / kRowVals;
-            const uint32_t x = bx * 32u + c - 1u, y = by * kBlockY + r % kHalo - 1u, z = bz * kBlockZ + r / kHalo - 1u;   // wraps below 0: >= n
-            tile[r * kRowPitch + c] = (x < n && y < n && z < n) ? D[x + (size_t)n * (y + (size_t)n * z)] : kNone;
-        }
-    }
+    const uint32_t t = threadIdx.x;
+    const BlockAt at = block_at(list[blockIdx.x], n);
+    stage_halo(tile, at, n, [&](uint32_t x, uint32_t y, uint32_t z, bool inside, uint32_t, uint32_t, uint32_t) {
+        return inside ? D[x + (size_t)n * (y + (size_t)n * z)] : kNone;
+    });
     if (t == 0) seen = 0u;
-    const uint32_t ly = t & 15u, lz = t >> 4, y = by * kBlockY + ly, z = bz * kBlockZ + lz;
-    const uint32_t m = mask[bx + (size_t)w * (y + (size_t)n * z)];
-    uint32_t* row = tile + ((lz + 1u) * kHalo + ly + 1u) * kRowPitch;   // column c = voxel c - 1 of the lane's row
+    const uint32_t ly = t & 15u, lz = t >> 4;
+    const uint32_t m = mask[at.word(n, ly, lz)];
+    uint32_t* row = tile_row(tile, ly, lz);
     __syncthreads();
 
     uint32_t chg = 0u;
@@ -229,30 +212,8 @@ gd_relax(const uint32_t* __restrict__ mask, uint32_t* D, const uint32_t* __restr
     const uint32_t see = block_seen_by(chg, ly, lz, W::diagonal) & ~(1u << 13);   // the neighbour blocks that see a changed voxel
     if (see) atomicOr(&seen, see);
     __syncthreads();
-#pragma unroll 4
-    for (uint32_t k = 0; k < 32u; ++k) {                           // lanes along x: row r of the block, voxel x
-        const uint32_t e = k * 256u + t, x = e & 31u, r = e >> 5;
-        if ((lowered[r] >> x) & 1u)
-            D[bx * 32u + x + (size_t)n * (by * kBlockY + (r & 15u) + (size_t)n * (bz * kBlockZ + (r >> 4)))] =
-                tile[((r >> 4) + 1u) * kHalo * kRowPitch + ((r & 15u) + 1u) * kRowPitch + x + 1u];
-    }
-    if (t < 27u) {
-        const uint32_t raise = seen | (still ? 1u << 13 : 0u);      // still changing at the cap: this block again
-        const uint32_t nx = bx + t % 3u - 1u, ny = by + (t / 3u) % 3u - 1u, nz = bz + t / 9u - 1u;
-        if (((raise >> t) & 1u) && nx < w && ny < nb && nz < nb) flags[nx + w * (ny + nb * nz)] = 1u;
-    }
-}
-
-template <int METRIC>
-void relax_launch(hipStream_t st, uint32_t active, const uint32_t* mask, uint32_t* D, const uint32_t* list, uint32_t* flags, uint32_t n)
-{
-    hipLaunchKernelGGL(gd_relax<METRIC>, dim3(active), dim3(256), 0, st, mask, D, list, flags, n);
-}
-
-template <int METRIC>
-void naive_launch(hipStream_t st, unsigned wgs, const uint32_t* mask, uint32_t* D, uint32_t n, const uint32_t* prev, uint32_t* cur)
-{
-    hipLaunchKernelGGL(gd_naive<METRIC>, dim3(wgs), dim3(256), 0, st, mask, D, n, prev, cur);
+    store_lowered(lowered, at, n, [&](uint32_t, uint32_t, size_t i, uint32_t in_tile) { D[i] = tile[in_tile]; });
+    if (t < 27u) block_raise(flags, seen | (still ? 1u << 13 : 0u), at, t);   // still changing at the cap: this block again
 }
 
 }  // namespace
@@ -275,47 +236,28 @@ int launch_geodesic(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const u
     uint32_t* list = flags + nblocks;
     volatile uint32_t* host = (volatile uint32_t*)ctx->gd.host.p;
 
-    VP_HIP(hipMemsetAsync(ctx->gd.aux.ptr, 0, kAuxHead + (size_t)(algo == VP_ALGO_TILED ? nblocks : 2u * kGeoBatch) * 4, st));
+    VP_HIP(hipMemsetAsync(ctx->gd.aux.ptr, 0, kAuxHead + (size_t)(algo == VP_ALGO_TILED ? nblocks : 0u) * 4, st));
     {
         ProfScope p(ctx, VP_K_MD_FILL);
         hipLaunchKernelGGL(gd_init, dim3(wgs / 4), dim3(256), 0, st, d_mask, d_seeds, (uint4*)D, n, algo == VP_ALGO_TILED ? flags : nullptr,
                            metric == VP_GEO_6 ? 0 : 1, (unsigned long long*)counters);
     }
+    const auto relax = metric == VP_GEO_6 ? gd_relax<VP_GEO_6> : metric == VP_GEO_26 ? gd_relax<VP_GEO_26> : gd_relax<VP_GEO_CHAMFER>;
+    const auto naive = metric == VP_GEO_6 ? gd_naive<VP_GEO_6> : metric == VP_GEO_26 ? gd_naive<VP_GEO_26> : gd_naive<VP_GEO_CHAMFER>;
     if (algo == VP_ALGO_TILED) {
         for (;;) {
-            {
-                ProfScope p(ctx, VP_K_MD_SCAN);
-                hipLaunchKernelGGL(block_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters + kCntActive);
-            }
-            VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->gd.host, counters + kCntActive, 4, hipMemcpyDeviceToHost, st));
-            VP_HIP(hipStreamSynchronize(st));
-            const uint32_t active = host[0];
+            uint32_t active = 0;
+            VP_TRY(list_active(ctx, flags, nblocks, list, counters + kCntActive, host, 4, &active));
             if (active == 0) break;                                // no block's halo or interior changed since it last ran: the fixed point
             ProfScope p(ctx, VP_K_MD_BRICK);
-            if (metric == VP_GEO_6) relax_launch<VP_GEO_6>(st, active, d_mask, D, list, flags, n);
-            else if (metric == VP_GEO_26) relax_launch<VP_GEO_26>(st, active, d_mask, D, list, flags, n);
-            else relax_launch<VP_GEO_CHAMFER>(st, active, d_mask, D, list, flags, n);
+            hipLaunchKernelGGL(relax, dim3(active), dim3(256), 0, st, d_mask, D, (const uint32_t*)list, flags, n);
         }
     } else {
-        for (uint32_t batch = 0;; ++batch) {
-            uint32_t* fl = flags + (batch & 1u) * kGeoBatch;
-            const uint32_t* last = flags + ((batch + 1u) & 1u) * kGeoBatch + kGeoBatch - 1u;   // previous batch's last round
-            if (batch) VP_HIP(hipMemsetAsync(fl, 0, kGeoBatch * 4, st));
-            for (uint32_t i = 0; i < kGeoBatch; ++i) {
-                const uint32_t* prev = batch == 0 && i == 0 ? nullptr : (i == 0 ? last : fl + i - 1);
-                ProfScope p(ctx, VP_K_MD_NAIVE);
-                if (metric == VP_GEO_6) naive_launch<VP_GEO_6>(st, wgs, d_mask, D, n, prev, fl + i);
-                else if (metric == VP_GEO_26) naive_launch<VP_GEO_26>(st, wgs, d_mask, D, n, prev, fl + i);
-                else naive_launch<VP_GEO_CHAMFER>(st, wgs, d_mask, D, n, prev, fl + i);
-            }
-            VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->gd.host, fl, kGeoBatch * 4, hipMemcpyDeviceToHost, st));
-            VP_HIP(hipStreamSynchronize(st));
-            uint32_t i = 0;
-            while (i < kGeoBatch && host[i]) ++i;
-            if (i < kGeoBatch) break;                              // a round that lowered nothing: the fixed point
-        }
+        // rounds until one lowers nothing: the fixed point
+        VP_TRY(run_rounds(st, RoundRing{flags, kGeoBatch, host}, nullptr, nullptr, [&](uint32_t, const uint32_t* prev, uint32_t* cur) {
+            ProfScope p(ctx, VP_K_MD_NAIVE);
+            hipLaunchKernelGGL(naive, dim3(wgs), dim3(256), 0, st, d_mask, D, n, prev, cur);
+        }));
     }
     {
         ProfScope p(ctx, VP_K_MD_SPLIT);

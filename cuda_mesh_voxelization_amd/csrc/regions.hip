@@ -10,7 +10,7 @@
 //                     without a value field; the totals of the statistics (workgroup sums, one atomic each)
 //   NAIVE  rg_naive   one lane per voxel from global memory: its 26 neighbours, then the 26 global 64-bit atomics of a run of one voxel
 //   TILED  rg_tiled   one workgroup per block of 32 x 16 x 16 voxels, 256 lanes.  The effective labels of the block and a one-voxel halo are
-//                     staged in LDS (18 x 18 rows of 34 labels, row pitch 35 = 45,360 B), the values of the block beside them (256 rows,
+//                     staged in LDS (the tile of block_list.h = 45,360 B), the values of the block beside them (256 rows,
 //                     pitch 33 = 33,792 B).  A lane whose x row holds no label does nothing; every other lane walks its row with the three
 //                     columns of nine labels around the voxel in registers and keeps
 //                     the RUN of its current label -- consecutive voxels of one label in that row -- in registers, in coordinates local to
@@ -35,8 +35,6 @@ namespace vp {
 namespace {
 
 constexpr uint32_t kWords = VP_REGION_WORDS;
-constexpr uint32_t kHalo = 18, kRowVals = 34, kRowPitch = 35;      // staged rows per axis, labels per row (x - 1 .. x + 32), pitch in labels
-constexpr uint32_t kStaged = kHalo * kHalo * kRowVals;
 constexpr uint32_t kValPitch = 33;                                 // values of one x row of the block, pitch in values
 constexpr uint32_t kSlots = 16;                                    // label slots of a block
 // the words that take a minimum / a maximum; every other word is a sum
@@ -219,31 +217,22 @@ rg_tiled(const uint32_t* __restrict__ W, const uint32_t* __restrict__ values, ui
     __shared__ uint32_t slots[kSlots][kWords];                     // its record in block coordinates, word 22 unused
     __shared__ unsigned long long slot_values[kSlots];             // its value sum
     __shared__ unsigned long long smem[4];
-    const uint32_t t = threadIdx.x, w = n / 32, nb = n / kBlockY, b = blockIdx.x;
-    const uint32_t bx = b % w, by = (b / w) % nb, bz = b / (w * nb);
-    const uint32_t x0 = bx * 32u, y0 = by * kBlockY, z0 = bz * kBlockZ;
+    const uint32_t t = threadIdx.x;
+    const BlockAt at = block_at(blockIdx.x, n);
+    const uint32_t x0 = at.x0(), y0 = at.y0(), z0 = at.z0();
     uint32_t ignored = 0u;
-    for (uint32_t k = 0; k < (kStaged + 255u) / 256u; ++k) {
-        const uint32_t e = k * 256u + t;
-        if (e < kStaged) {
-            const uint32_t c = e % kRowVals, r = e / kRowVals, ry = r % kHalo, rz = r / kHalo;
-            const uint32_t x = x0 + c - 1u, y = y0 + ry - 1u, z = z0 + rz - 1u;   // wraps below 0: >= n
-            uint32_t l = 0u;
-            if (x < n && y < n && z < n) {
-                l = W[x + (size_t)n * (y + (size_t)n * z)];
-                if (l > count) {
-                    l = 0u;
-                    ignored += c >= 1u && c <= 32u && ry >= 1u && ry <= kBlockY && rz >= 1u && rz <= kBlockZ;   // counted by its own block
-                }
-            }
-            tile[r * kRowPitch + c] = l;
-        }
-    }
+    stage_halo(tile, at, n, [&](uint32_t x, uint32_t y, uint32_t z, bool inside, uint32_t c, uint32_t ry, uint32_t rz) {
+        if (!inside) return 0u;
+        const uint32_t l = W[x + (size_t)n * (y + (size_t)n * z)];
+        if (l <= count) return l;
+        ignored += c >= 1u && c <= 32u && ry >= 1u && ry <= kBlockY && rz >= 1u && rz <= kBlockZ;   // counted by its own block
+        return 0u;
+    });
     if (values) {
 #pragma unroll 4
         for (uint32_t k = 0; k < 32u; ++k) {                       // lanes along x: row r of the block, voxel x
             const uint32_t e = k * 256u + t, x = e & 31u, r = e >> 5;
-            vtile[r * kValPitch + x] = values[x0 + x + (size_t)n * (y0 + (r & 15u) + (size_t)n * (z0 + (r >> 4)))];
+            vtile[r * kValPitch + x] = values[at.voxel(n, x, r & 15u, r >> 4)];
         }
     }
     if (t < kSlots) { keys[t] = 0u; slot_values[t] = 0ull; }
@@ -251,7 +240,7 @@ rg_tiled(const uint32_t* __restrict__ W, const uint32_t* __restrict__ values, ui
     __syncthreads();
 
     const uint32_t ly = t & 15u, lz = t >> 4;
-    const uint32_t* row = tile + ((lz + 1u) * kHalo + ly + 1u) * kRowPitch;   // column c = voxel c - 1 of the lane's row
+    const uint32_t* row = tile_row(tile, ly, lz);
     const uint32_t* vrow = vtile + t * kValPitch;
     uint32_t any = 0u;                                             // a row without a label (most rows of most grids) is not walked
 #pragma unroll

@@ -7,11 +7,10 @@
 //          sk_sub_naive     one lane per word of 32 voxels, global memory only: the words of the wrong y / z parity are copied, the others
 //                           examine their candidate bits one by one with the plain simple() and write the word into the OTHER grid (eight
 //                           launches: the result is back in the first).  The deleted count is read back after every iteration.
-//   TILED  sk_mark_nonempty / block_list (block_list.h)   the list of active blocks by count -> scan -> write: a block of 32 x 16 x 16 voxels is active when it or a
+//   TILED  sk_mark_nonempty / block_list (block_list.h)   the list of active blocks: a block of 32 x 16 x 16 voxels is active when it or a
 //                           26-neighbour block lost a voxel in the previous iteration (every non-empty block in the first).  A block
-//                           that lost a voxel raises the flags of its 27 blocks with plain stores of 1; one workgroup scans the flags
-//                           into the list and clears them.  The list length comes back with the deleted count, so every launch has
-//                           exactly one workgroup per active block.
+//                           that lost a voxel raises the flags of its 27 blocks.  The list length comes back with the deleted count, so
+//                           every launch has exactly one workgroup per active block.
 //          sk_border_tiled  the border words of the active blocks
 //          sk_sub_tiled     one workgroup per active block, 256 lanes = one per word.  The block's rows and a one-voxel halo are staged
 //                           in LDS as 34-bit rows (bit 0 = x - 1 from the word before, bit 33 = x + 32 from the word after: the fetch
@@ -36,8 +35,9 @@ namespace vp {
 
 namespace {
 
-constexpr uint32_t kHalo = 18;                                    // staged rows per axis of a block (block_list.h: one lane per word)
-// the counters in front of the block flags (kAuxHead bytes): deleted | active blocks | - | - | voxels left (u64)
+// the counters in front of the block flags (kAuxHead bytes): active blocks | deleted | - | - | voxels left (u64); kCnt* = where each starts,
+// in 32-bit words.  The rows of a block and its halo are staged as kHalo x kHalo 34-bit rows (block_list.h: one lane per word).
+constexpr uint32_t kCntActive = 0, kCntDeleted = 1, kCntLeft = 4;
 
 // the row of word xw at (y, z) with its two x neighbours: bit 0 = voxel 32 xw - 1, bits 1 .. 32 the word, bit 33 = voxel 32 xw + 32;
 // rows and voxels outside the grid are unset
@@ -87,7 +87,7 @@ sk_border_naive(const uint32_t* __restrict__ g, const uint32_t* __restrict__ anc
 
 __global__ void __launch_bounds__(256)
 sk_sub_naive(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const uint32_t* __restrict__ border, uint32_t n, uint32_t s, int mode,
-             uint32_t* __restrict__ counters)
+             uint32_t* __restrict__ deleted)
 {
     __shared__ uint32_t smem[4];
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -107,7 +107,7 @@ sk_sub_naive(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const
     }
     dst[i] = cur & ~del;
     const uint32_t sum = wg_sum_256((uint32_t)__popc(del), smem);
-    if (threadIdx.x == 0 && sum) atomicAdd(&counters[0], sum);
+    if (threadIdx.x == 0 && sum) atomicAdd(deleted, sum);
 }
 
 // ---- TILED -------------------------------------------------------------------------------------------------------------------------
@@ -126,37 +126,37 @@ __global__ void __launch_bounds__(256)
 sk_border_tiled(const uint32_t* __restrict__ g, const uint32_t* __restrict__ anchor, uint32_t* __restrict__ border, const uint32_t* __restrict__ list,
                 uint32_t n)
 {
-    const uint32_t w = n / 32, nb = n / kBlockY, b = list[blockIdx.x];
-    const uint32_t xw = b % w, y = (b / w) % nb * kBlockY + (threadIdx.x & 15u), z = b / (w * nb) * kBlockZ + (threadIdx.x >> 4);
-    border[xw + (size_t)w * ((size_t)y + (size_t)n * z)] = sk_border_word(g, anchor, n, w, xw, y, z);
+    const BlockAt at = block_at(list[blockIdx.x], n);
+    const uint32_t ly = threadIdx.x & 15u, lz = threadIdx.x >> 4;
+    border[at.word(n, ly, lz)] = sk_border_word(g, anchor, n, at.w, at.bx, at.y0() + ly, at.z0() + lz);
 }
 
 __global__ void __launch_bounds__(256)
 sk_sub_tiled(uint32_t* __restrict__ g, const uint32_t* __restrict__ border, const uint32_t* __restrict__ list, uint32_t* __restrict__ flags,
-             uint32_t n, uint32_t s, int mode, uint32_t* __restrict__ counters)
+             uint32_t n, uint32_t s, int mode, uint32_t* __restrict__ deleted)
 {
     __shared__ uint64_t rows[kHalo * kHalo];
     __shared__ uint32_t del[256];
     __shared__ uint16_t cands[1024];                               // (lane << 5) | x of every candidate: 64 rows of the parity x 16 bits
     __shared__ uint32_t smem[4];
-    const uint32_t t = threadIdx.x, w = n / 32, nb = n / kBlockY, b = list[blockIdx.x];
-    const uint32_t bx = b % w, by = (b / w) % nb, bz = b / (w * nb);
+    const uint32_t t = threadIdx.x;
+    const BlockAt at = block_at(list[blockIdx.x], n);
 #pragma unroll
     for (uint32_t r = 0; r < 2; ++r) {
         const uint32_t j = t + 256u * r;
-        if (j < kHalo * kHalo) rows[j] = sk_row(g, n, w, bx, (int)(by * kBlockY + j % kHalo) - 1, (int)(bz * kBlockZ + j / kHalo) - 1);
+        if (j < kHalo * kHalo) rows[j] = sk_row(g, n, at.w, at.bx, (int)(at.y0() + j % kHalo) - 1, (int)(at.z0() + j / kHalo) - 1);
     }
     del[t] = 0u;
-    const uint32_t ly = t & 15u, lz = t >> 4, y = by * kBlockY + ly, z = bz * kBlockZ + lz;
-    const size_t i = bx + (size_t)w * ((size_t)y + (size_t)n * z);
+    const uint32_t ly = t & 15u, lz = t >> 4, y = at.y0() + ly, z = at.z0() + lz;
+    const size_t i = at.word(n, ly, lz);
     __syncthreads();
     const uint32_t own = (uint32_t)(rows[(lz + 1u) * kHalo + ly + 1u] >> 1);
     uint32_t cand = 0u;
     if ((y & 1u) == ((s >> 1) & 1u) && (z & 1u) == (s >> 2) && own != 0u) cand = own & border[i] & sk_xmask(s);
     uint32_t total = 0u;
-    uint32_t at = wg_exclusive_256((uint32_t)__popc(cand), smem, &total);
+    uint32_t put = wg_exclusive_256((uint32_t)__popc(cand), smem, &total);
     for (int k = 0; k < 16 && cand != 0u; ++k) {
-        cands[at++] = (uint16_t)((t << 5) | (uint32_t)__builtin_ctz(cand));
+        cands[put++] = (uint16_t)((t << 5) | (uint32_t)__builtin_ctz(cand));
         cand &= cand - 1u;
     }
     __syncthreads();
@@ -176,11 +176,8 @@ sk_sub_tiled(uint32_t* __restrict__ g, const uint32_t* __restrict__ border, cons
     if (d) g[i] = own & ~d;
     const uint32_t sum = wg_sum_256((uint32_t)__popc(d), smem);
     if (sum == 0u) return;
-    if (t == 0) atomicAdd(&counters[0], sum);
-    if (t < 27u) {                                                 // this block and its 26 neighbours are active in the next iteration
-        const uint32_t nx = bx + t % 3u - 1u, ny = by + (t / 3u) % 3u - 1u, nz = bz + t / 9u - 1u;
-        if (nx < w && ny < nb && nz < nb) flags[nx + w * (ny + nb * nz)] = 1u;
-    }
+    if (t == 0) atomicAdd(deleted, sum);
+    if (t < 27u) block_raise(flags, ~0u, at, t);                   // this block and its 26 neighbours are active in the next iteration
 }
 
 // ---- both --------------------------------------------------------------------------------------------------------------------------
@@ -238,21 +235,14 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
     }
     uint32_t active = 0;
     if (algo == VP_ALGO_TILED) {
-        {
-            ProfScope p(ctx, VP_K_MD_SCAN);
-            hipLaunchKernelGGL(sk_mark_nonempty, dim3(wgs), dim3(256), 0, st, (const uint32_t*)grid, n, flags);
-            hipLaunchKernelGGL(block_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters + 1);
-        }
-        VP_HIP(hipGetLastError());
-        VP_HIP(hipMemcpyAsync(ctx->sk.host, counters, 8, hipMemcpyDeviceToHost, st));
-        VP_HIP(hipStreamSynchronize(st));
-        active = host[1];
+        VP_TRY(list_active(ctx, flags, nblocks, list, counters + kCntActive, host, 4, &active,
+                           [&] { hipLaunchKernelGGL(sk_mark_nonempty, dim3(wgs), dim3(256), 0, st, (const uint32_t*)grid, n, flags); }));
     }
     uint64_t iterations = 0, deleted = 0;
     while (max_iters == 0 || iterations < max_iters) {
         uint32_t lost = 0;
         if (algo == VP_ALGO_NAIVE) {
-            VP_HIP(hipMemsetAsync(counters, 0, 4, st));
+            VP_HIP(hipMemsetAsync(counters + kCntDeleted, 0, 4, st));
             {
                 ProfScope p(ctx, VP_K_SURFACE);
                 hipLaunchKernelGGL(sk_border_naive, dim3(wgs), dim3(256), 0, st, (const uint32_t*)grid, d_anchor, border, n);
@@ -260,14 +250,14 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
             for (uint32_t s = 0; s < 8; ++s) {
                 ProfScope p(ctx, VP_K_MORPH_NAIVE);
                 hipLaunchKernelGGL(sk_sub_naive, dim3(wgs), dim3(256), 0, st, (const uint32_t*)((s & 1u) ? other : grid), (s & 1u) ? grid : other,
-                                   (const uint32_t*)border, n, s, mode, counters);
+                                   (const uint32_t*)border, n, s, mode, counters + kCntDeleted);
             }
             VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->sk.host, counters, 8, hipMemcpyDeviceToHost, st));
+            VP_HIP(hipMemcpyAsync(ctx->sk.host, counters + kCntDeleted, 4, hipMemcpyDeviceToHost, st));
             VP_HIP(hipStreamSynchronize(st));
             lost = host[0];
         } else if (active) {
-            VP_HIP(hipMemsetAsync(counters, 0, 4, st));
+            VP_HIP(hipMemsetAsync(counters + kCntDeleted, 0, 4, st));
             {
                 ProfScope p(ctx, VP_K_SURFACE);
                 hipLaunchKernelGGL(sk_border_tiled, dim3(active), dim3(256), 0, st, (const uint32_t*)grid, d_anchor, border, (const uint32_t*)list, n);
@@ -275,29 +265,22 @@ int launch_skeleton(vp_ctx* ctx, const Frame& f, const uint32_t* d_words, const 
             for (uint32_t s = 0; s < 8; ++s) {
                 ProfScope p(ctx, VP_K_MORPH);
                 hipLaunchKernelGGL(sk_sub_tiled, dim3(active), dim3(256), 0, st, grid, (const uint32_t*)border, (const uint32_t*)list, flags, n, s,
-                                   mode, counters);
+                                   mode, counters + kCntDeleted);
             }
-            {
-                ProfScope p(ctx, VP_K_MD_SCAN);
-                hipLaunchKernelGGL(block_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters + 1);
-            }
-            VP_HIP(hipGetLastError());
-            VP_HIP(hipMemcpyAsync(ctx->sk.host, counters, 8, hipMemcpyDeviceToHost, st));
-            VP_HIP(hipStreamSynchronize(st));
-            lost = host[0];
-            active = host[1];
+            VP_TRY(list_active(ctx, flags, nblocks, list, counters + kCntActive, host, 8, &active));   // active blocks | deleted
+            lost = host[kCntDeleted];
         }
         ++iterations;
         deleted += lost;
         if (lost == 0) break;                                      // the state is a fixed point: every further iteration would delete nothing
     }
-    VP_HIP(hipMemsetAsync(counters + 4, 0, 8, st));
+    VP_HIP(hipMemsetAsync(counters + kCntLeft, 0, 8, st));
     {
         ProfScope p(ctx, VP_K_MD_SPLIT);
-        hipLaunchKernelGGL(sk_count, dim3(wgs), dim3(256), 0, st, (const uint32_t*)grid, (unsigned long long*)(counters + 4));
+        hipLaunchKernelGGL(sk_count, dim3(wgs), dim3(256), 0, st, (const uint32_t*)grid, (unsigned long long*)(counters + kCntLeft));
     }
     VP_HIP(hipGetLastError());
-    VP_HIP(hipMemcpyAsync(ctx->sk.host + 2, counters + 4, 8, hipMemcpyDeviceToHost, st));
+    VP_HIP(hipMemcpyAsync(ctx->sk.host + 2, counters + kCntLeft, 8, hipMemcpyDeviceToHost, st));
     VP_HIP(hipStreamSynchronize(st));
     ctx->sk.stats[0] = ctx->sk.host[2];
     ctx->sk.stats[1] = iterations;

@@ -13,9 +13,9 @@
 //                     refusals and walks the present levels only.
 //          ws_final   one lane per voxel: W, the cut grid (one ballot = 64 bits = two words) and the two counts (wg_scan.h)
 //   NAIVE  ws_naive   one lane per voxel, global memory only, in place; per level whole-grid launches repeat until one changes nothing
-//                     (the flag ring of fill.hip / geodesic.hip).
+//                     (the flag ring of round_ring.h, restarted per level).
 //   TILED  ws_relax   one workgroup per ACTIVE block (block_list.h), 256 lanes = one per x row.  The CONTRIBUTIONS of the block and a
-//                     one-voxel halo are staged in LDS (18 x 18 rows of 34 values of 8 bytes, row pitch 35 = 90,720 B: one workgroup per
+//                     one-voxel halo are staged in LDS (the tile of block_list.h with values of 8 bytes = 90,720 B: one workgroup per
 //                     CU of the 160 KiB).  A sweep: every lane walks its row with column minima over the eight (four) rows around
 //                     it, left to right with the value it just made, then right to left in registers; barrier; the lanes store what
 //                     they lowered; barrier.  Sweeps repeat until one lowers nothing or kWsSweeps ran; the changed keys are written back.
@@ -30,6 +30,7 @@
 // key leads to a contradiction, so the fixed point of a level is unique whatever the order of execution.  T < 2^30: the hops of all
 // levels together are at most the voxels labelled.  Every device loop has a compile-time bound.
 #include "block_list.h"
+#include "round_ring.h"
 #include "vp_internal.h"
 
 #include <algorithm>
@@ -40,8 +41,6 @@ namespace {
 
 constexpr uint32_t kWsSweeps = 64;   // TILED: sweeps over a block per launch at most
 constexpr uint32_t kWsBatch = 8;     // NAIVE: rounds enqueued between two read-backs of their flags
-constexpr uint32_t kHalo = 18, kRowVals = 34, kRowPitch = 35;      // staged rows per axis, values per row (x - 1 .. x + 32), pitch in values
-constexpr uint32_t kStaged = kHalo * kHalo * kRowVals;
 constexpr uint32_t kLabelBits = 20, kRankBits = 14, kTShift = kLabelBits + kRankBits;
 constexpr uint32_t kLabelMask = VP_WS_LABEL_MAX, kBitmapWords = VP_WS_MAX_SPAN / 32;
 constexpr unsigned long long kHop = 1ull << kTShift, kInf = ~0ull;
@@ -79,8 +78,8 @@ ws_pre(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ markers, 
     __shared__ uint32_t present[kBitmapWords];
     __shared__ uint32_t red[4][4];
     __shared__ unsigned long long smem[4];
-    const uint32_t t = threadIdx.x, w = n / 32, nb = n / kBlockY, b = blockIdx.x;
-    const uint32_t bx = b % w, by = (b / w) % nb, bz = b / (w * nb);
+    const uint32_t t = threadIdx.x, b = blockIdx.x;
+    const BlockAt at = block_at(b, n);
     present[t] = 0u;
     present[t + 256u] = 0u;
     __syncthreads();
@@ -88,8 +87,7 @@ ws_pre(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ markers, 
 #pragma unroll 4
     for (uint32_t k = 0; k < 32u; ++k) {
         const uint32_t e = k * 256u + t, x = e & 31u, r = e >> 5;
-        const uint32_t y = by * kBlockY + (r & 15u), z = bz * kBlockZ + (r >> 4);
-        const size_t i = bx * 32u + x + (size_t)n * (y + (size_t)n * z);
+        const size_t i = at.voxel(n, x, r & 15u, r >> 4);
         const bool in = (mask[i >> 5] >> x) & 1u;
         const uint32_t l = in ? markers[i] : 0u;
         K[i] = l <= kLabelMask ? l : 0ull;                           // a label above the bound is refused by the host: nothing is flooded then
@@ -139,11 +137,7 @@ ws_final(const unsigned long long* __restrict__ K, uint32_t* __restrict__ W, uin
             keep = keep && ((uint32_t)K[qx + (size_t)n * (qy + (size_t)n * qz)] & kLabelMask) <= l;
         }
     }
-    const unsigned long long hit = __ballot(keep);
-    if ((threadIdx.x & 63u) == 0) {
-        cut[i >> 5] = (uint32_t)hit;
-        cut[(i >> 5) + 1] = (uint32_t)(hit >> 32);
-    }
+    store_ballot(cut, i, keep);
     const unsigned long long labelled = wg_sum_256((unsigned long long)(l != 0u), smem);
     const unsigned long long kept = wg_sum_256((unsigned long long)keep, cmem);
     if (threadIdx.x == 0) {
@@ -159,7 +153,7 @@ __global__ void __launch_bounds__(256)
 ws_naive(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ P, unsigned long long* K, uint32_t n, Levels lv, uint32_t rank, uint32_t base,
          const uint32_t* prev, uint32_t* cur, uint32_t* tmax)
 {
-    if (prev && *prev == 0u) return;
+    if (round_skip(prev)) return;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t stamp = 0u;                                           // T of the key stored, 0: none
     if ((mask[i >> 5] >> (i & 31u)) & 1u) {
@@ -183,10 +177,8 @@ ws_naive(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ P, unsi
         }
     }
     for (int s = 32; s >= 1; s >>= 1) stamp = max(stamp, (uint32_t)__shfl_xor(stamp, s));
-    if (stamp && (threadIdx.x & 63u) == 0) {
-        *cur = 1u;
-        atomicMax(tmax, stamp);
-    }
+    round_mark(stamp != 0u, cur);
+    if (stamp && (threadIdx.x & 63u) == 0) atomicMax(tmax, stamp);
 }
 
 // ---- TILED -------------------------------------------------------------------------------------------------------------------------
@@ -219,32 +211,23 @@ ws_relax(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ P, unsi
     __shared__ uint32_t open[256];                                 // per row: the voxels of M whose level has come (the level's set A, once unlabelled)
     __shared__ uint32_t lowered[256];                              // per row: the voxels that changed in this launch
     __shared__ uint32_t seen, newest;                              // neighbour blocks whose halo holds a changed voxel; the largest T stored
-    const uint32_t t = threadIdx.x, w = n / 32, nb = n / kBlockY, b = list[blockIdx.x];
-    const uint32_t bx = b % w, by = (b / w) % nb, bz = b / (w * nb);
-    for (uint32_t k = 0; k < (kStaged + 255u) / 256u; ++k) {
-        const uint32_t e = k * 256u + t;
-        if (e < kStaged) {
-            const uint32_t c = e % kRowVals, r = e / kRowVals;
-            const uint32_t x = bx * 32u + c - 1u, y = by * kBlockY + r % kHalo - 1u, z = bz * kBlockZ + r / kHalo - 1u;   // wraps below 0: >= n
-            unsigned long long v = kInf;
-            if (x < n && y < n && z < n) {
-                const size_t i = x + (size_t)n * (y + (size_t)n * z);
-                v = ws_contribution(ws_load(K + i), P, i, lv, base);
-            }
-            tile[r * kRowPitch + c] = v;
-        }
-    }
+    const uint32_t t = threadIdx.x;
+    const BlockAt at = block_at(list[blockIdx.x], n);
+    stage_halo(tile, at, n, [&](uint32_t x, uint32_t y, uint32_t z, bool inside, uint32_t, uint32_t, uint32_t) {
+        if (!inside) return kInf;
+        const size_t i = x + (size_t)n * (y + (size_t)n * z);
+        return ws_contribution(ws_load(K + i), P, i, lv, base);
+    });
 #pragma unroll 4
     for (uint32_t k = 0; k < 32u; ++k) {                           // lanes along x: a wave makes the words of two rows by one ballot
         const uint32_t e = k * 256u + t, x = e & 31u, r = e >> 5;
-        const size_t i = bx * 32u + x + (size_t)n * (by * kBlockY + (r & 15u) + (size_t)n * (bz * kBlockZ + (r >> 4)));
+        const size_t i = at.voxel(n, x, r & 15u, r >> 4);
         const bool in = ((mask[i >> 5] >> x) & 1u) && ws_rank(P, i, lv) <= rank;
-        const unsigned long long bits = __ballot(in);
-        if ((t & 63u) == 0) { open[r] = (uint32_t)bits; open[r + 1u] = (uint32_t)(bits >> 32); }
+        store_ballot(open, e, in);
     }
     if (t == 0) { seen = 0u; newest = 0u; }
     const uint32_t ly = t & 15u, lz = t >> 4;
-    unsigned long long* row = tile + ((lz + 1u) * kHalo + ly + 1u) * kRowPitch;   // column c = voxel c - 1 of the lane's row
+    unsigned long long* row = tile_row(tile, ly, lz);
     __syncthreads();
     const uint32_t m = open[t];
     const unsigned long long frozen = (unsigned long long)(base + 1u);   // T of a frozen source's contribution, and of nothing else
@@ -294,23 +277,15 @@ ws_relax(const uint32_t* __restrict__ mask, const uint32_t* __restrict__ P, unsi
     if (see) atomicOr(&seen, see);
     __syncthreads();
     uint32_t stamp = 0u;
-#pragma unroll 4
-    for (uint32_t k = 0; k < 32u; ++k) {                           // lanes along x: row r of the block, voxel x
-        const uint32_t e = k * 256u + t, x = e & 31u, r = e >> 5;
-        if ((lowered[r] >> x) & 1u) {
-            const unsigned long long key = tile[((r >> 4) + 1u) * kHalo * kRowPitch + ((r & 15u) + 1u) * kRowPitch + x + 1u] - kHop;
-            ws_store(K + (bx * 32u + x + (size_t)n * (by * kBlockY + (r & 15u) + (size_t)n * (bz * kBlockZ + (r >> 4)))), key);
-            stamp = max(stamp, (uint32_t)(key >> kTShift));
-        }
-    }
+    store_lowered(lowered, at, n, [&](uint32_t, uint32_t, size_t i, uint32_t in_tile) {
+        const unsigned long long key = tile[in_tile] - kHop;
+        ws_store(K + i, key);
+        stamp = max(stamp, (uint32_t)(key >> kTShift));
+    });
     if (stamp) atomicMax(&newest, stamp);
     __syncthreads();
     if (t == 0 && newest) atomicMax(tmax, newest);
-    if (t < 27u) {
-        const uint32_t raise = seen | (still ? 1u << 13 : 0u);      // still changing at the cap: this block again
-        const uint32_t nx = bx + t % 3u - 1u, ny = by + (t / 3u) % 3u - 1u, nz = bz + t / 9u - 1u;
-        if (((raise >> t) & 1u) && nx < w && ny < nb && nz < nb) flags[nx + w * (ny + nb * nz)] = 1u;
-    }
+    if (t < 27u) block_raise(flags, seen | (still ? 1u << 13 : 0u), at, t);   // still changing at the cap: this block again
 }
 
 // the smallest quantum >= q whose levels of [lo, hi] span less than VP_WS_MAX_SPAN
@@ -380,10 +355,8 @@ int launch_watershed(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const 
     VP_TRY(reserve(ctx, ctx->wsd.labels, voxels * 4, false));
     VP_TRY(reserve(ctx, ctx->wsd.cut, voxels / 8, false));
     uint32_t base = 0;                                             // the largest T stored so far
-    auto naive = [&](uint32_t rank, const uint32_t* prev, uint32_t* cur) {
-        if (conn == VP_CONN_6) hipLaunchKernelGGL(ws_naive<6>, dim3(wgs), dim3(256), 0, st, d_mask, d_priority, K, n, lv, rank, base, prev, cur, counters + kCntT);
-        else hipLaunchKernelGGL(ws_naive<26>, dim3(wgs), dim3(256), 0, st, d_mask, d_priority, K, n, lv, rank, base, prev, cur, counters + kCntT);
-    };
+    const auto naive = conn == VP_CONN_6 ? ws_naive<6> : ws_naive<26>;
+    const auto relax = conn == VP_CONN_6 ? ws_relax<6> : ws_relax<26>;
     for (size_t at = 0; used != 0 && at < levels.size(); ++at) {
         const uint32_t level = levels[at], rank = flip ? last - level : level - first;
         if (algo == VP_ALGO_TILED) {
@@ -393,47 +366,25 @@ int launch_watershed(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const 
                 hipLaunchKernelGGL(ws_first, dim3((nblocks + 255u) / 256u), dim3(256), 0, st, lohi, nblocks, (uint32_t)plo, (uint32_t)phi, flags);
             }
             for (;;) {
-                {
-                    ProfScope p(ctx, VP_K_MD_SCAN);
-                    hipLaunchKernelGGL(block_list, dim3(1), dim3(1024), 0, st, flags, nblocks, list, counters + kCntActive);
-                }
-                VP_HIP(hipGetLastError());
-                VP_HIP(hipMemcpyAsync(ctx->wsd.host, counters + kCntActive, 8, hipMemcpyDeviceToHost, st));   // active blocks | largest T
-                VP_HIP(hipStreamSynchronize(st));
-                const uint32_t active = host[0];
+                uint32_t active = 0;
+                VP_TRY(list_active(ctx, flags, nblocks, list, counters + kCntActive, host, 8, &active));   // active blocks | largest T
                 if (active == 0) { base = host[1]; break; }         // the level's fixed point: what it stored is frozen from now on
                 ProfScope p(ctx, VP_K_MD_BRICK);
-                if (conn == VP_CONN_6)
-                    hipLaunchKernelGGL(ws_relax<6>, dim3(active), dim3(256), 0, st, d_mask, d_priority, K, list, flags, n, lv, rank, base, counters + kCntT);
-                else
-                    hipLaunchKernelGGL(ws_relax<26>, dim3(active), dim3(256), 0, st, d_mask, d_priority, K, list, flags, n, lv, rank, base, counters + kCntT);
+                hipLaunchKernelGGL(relax, dim3(active), dim3(256), 0, st, d_mask, d_priority, K, (const uint32_t*)list, flags, n, lv, rank, base, counters + kCntT);
             }
         } else {
-            VP_HIP(hipMemsetAsync(flags, 0, 2u * kWsBatch * 4, st));
-            for (uint32_t batch = 0;; ++batch) {
-                uint32_t* fl = flags + (batch & 1u) * kWsBatch;
-                const uint32_t* tail = flags + ((batch + 1u) & 1u) * kWsBatch + kWsBatch - 1u;   // previous batch's last round
-                if (batch) VP_HIP(hipMemsetAsync(fl, 0, kWsBatch * 4, st));
-                for (uint32_t i = 0; i < kWsBatch; ++i) {
-                    ProfScope p(ctx, VP_K_MD_NAIVE);
-                    naive(rank, batch == 0 && i == 0 ? nullptr : (i == 0 ? tail : fl + i - 1), fl + i);
-                }
-                VP_HIP(hipGetLastError());
-                VP_HIP(hipMemcpyAsync(ctx->wsd.host, fl, kWsBatch * 4, hipMemcpyDeviceToHost, st));
-                VP_HIP(hipMemcpyAsync(ctx->wsd.host.p + kWsBatch, counters + kCntT, 4, hipMemcpyDeviceToHost, st));
-                VP_HIP(hipStreamSynchronize(st));
-                uint32_t i = 0;
-                while (i < kWsBatch && host[i]) ++i;
-                if (i < kWsBatch) { base = host[kWsBatch]; break; }  // a round that changed nothing: the level's fixed point
-            }
+            // rounds until one changes nothing: the level's fixed point; the largest T comes back with every batch of flags
+            VP_TRY(run_rounds(st, RoundRing{flags, kWsBatch, host}, nullptr, counters + kCntT, [&](uint32_t, const uint32_t* prev, uint32_t* cur) {
+                ProfScope p(ctx, VP_K_MD_NAIVE);
+                hipLaunchKernelGGL(naive, dim3(wgs), dim3(256), 0, st, d_mask, d_priority, K, n, lv, rank, base, prev, cur, counters + kCntT);
+            }));
+            base = host[kWsBatch];
         }
     }
     {
         ProfScope p(ctx, VP_K_MD_SPLIT);
-        if (conn == VP_CONN_6)
-            hipLaunchKernelGGL(ws_final<6>, dim3(wgs), dim3(256), 0, st, K, (uint32_t*)ctx->wsd.labels.ptr, (uint32_t*)ctx->wsd.cut.ptr, n, (unsigned long long*)counters);
-        else
-            hipLaunchKernelGGL(ws_final<26>, dim3(wgs), dim3(256), 0, st, K, (uint32_t*)ctx->wsd.labels.ptr, (uint32_t*)ctx->wsd.cut.ptr, n, (unsigned long long*)counters);
+        hipLaunchKernelGGL(conn == VP_CONN_6 ? ws_final<6> : ws_final<26>, dim3(wgs), dim3(256), 0, st, (const unsigned long long*)K, (uint32_t*)ctx->wsd.labels.ptr,
+                           (uint32_t*)ctx->wsd.cut.ptr, n, (unsigned long long*)counters);
     }
     VP_HIP(hipGetLastError());
     VP_HIP(hipMemcpyAsync(ctx->wsd.host, counters, kAuxHead, hipMemcpyDeviceToHost, st));

@@ -91,3 +91,12 @@ def test_fill_refuses_several_gpus(cli, tmp_path):
                        cwd=str(tmp_path))
     assert p.returncode != 0
     assert "--fill runs on one device" in p.stdout + p.stderr
+
+
+def test_flag_ring_index_arithmetic(tmp_path):
+    """tests/cpp/round_ring_check.cpp: where a round's flag lives and which flag it reads (csrc/round_ring.h), as a plain host program"""
+    exe = str(tmp_path / "round_ring_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", build.CSRC,
+                           os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "round_ring_check.cpp"), "-o", exe])
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0 and p.stdout.strip() == "ok", p.stdout[-2000:] + p.stderr[-2000:]

@@ -84,6 +84,15 @@ def test_maze(engine, n):
     assert rounds > _batch(), rounds                        # more than one batch ran: the batch and early-exit logic was exercised
 
 
+def test_maze_runs_three_batches(engine):
+    """the smallest maze whose rounds fill more than two batches: both halves of the flag ring (csrc/round_ring.h) are reused"""
+    n = 32
+    words, _ = maze(n, seed=n)
+    got, rounds = _fill(engine, n, words)
+    assert np.array_equal(got, fill_numpy(words, n)), int(np.count_nonzero(got != fill_numpy(words, n)))
+    assert rounds > 2 * _batch(), rounds
+
+
 def _convex(xyz, tri):
     v = xyz.astype(np.float64)
     t = tri.astype(np.int64)

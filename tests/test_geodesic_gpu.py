@@ -277,6 +277,20 @@ def test_timing_keys(engine):
     assert list(capi.EVERY_PROF_KEY) == every and capi.lib().vp_abi_version() == 6
 
 
+def test_naive_rounds_cross_the_flag_ring_twice(engine):
+    """NAIVE with face steps on the serpentine at n = 32: against the y order of the launch a front gains about a voxel per round, so the
+    rounds fill at least three batches of eight (csrc/round_ring.h) -- both halves of the flag ring are reused; the result is the reference's"""
+    ctx = engine.ctx
+    ctx.prof_reset()
+    ctx.prof_enable(True)
+    try:
+        _check(engine, "serpentine 32", R.GEO_6, ALGO_NAIVE)
+    finally:
+        ctx.prof_enable(False)
+    launches = ctx.prof()["md_naive"]["launches"]
+    assert launches >= 3 * 8 and launches % 8 == 0, launches
+
+
 # ---- 10: the CLI ------------------------------------------------------------------------------------------------------------------------------------
 def test_cli_device_equals_host(tmp_path):
     cli = build.build_cli()

@@ -228,6 +228,26 @@ def test_timing_keys(engine):
     assert list(capi.EVERY_PROF_KEY) == every and capi.lib().vp_abi_version() == 6
 
 
+def test_naive_rounds_cross_the_flag_ring_twice(engine):
+    """NAIVE, conn 6, one level: the serpentine of tests/geodesic_ref.py at n = 32 as an influence-zone mask with a single marker at its
+    start.  The rounds of the level fill at least three batches of eight (csrc/round_ring.h) -- both halves of the flag ring are reused"""
+    import geodesic_ref as G
+    mask, start = G.case("serpentine 32")
+    markers = start.astype(np.uint32)
+    exp, cut, stats = R.watershed(mask, markers, None, R.DESCENDING, 1, 6)
+    assert stats[2] == 1 and np.array_equal(exp != 0, mask)
+    ctx = engine.ctx
+    ctx.prof_reset()
+    ctx.prof_enable(True)
+    try:
+        w, c, s = _run(engine, mask, markers, None, R.DESCENDING, 1, 6, ALGO_NAIVE)
+    finally:
+        ctx.prof_enable(False)
+    assert np.array_equal(w, exp.reshape(-1)) and np.array_equal(c, R.bool_to_words(cut)) and s == stats
+    launches = ctx.prof()["md_naive"]["launches"]
+    assert launches >= 3 * 8 and launches % 8 == 0, launches
+
+
 # ---- 5: vp_watershed_host and the engine ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("conn", R.CONNS)
 def test_host_entry_point(engine, conn):
