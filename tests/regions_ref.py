@@ -196,6 +196,7 @@ def case(name):
         "blobs": lambda: (_blobs(64, 4), 7),
         "blobs96": lambda: (_blobs(96, 5), 7),
         "whole96": lambda: (np.ones((96, 96, 96), np.uint32), 1),
+        "whole128": lambda: (np.ones((128, 128, 128), np.uint32), 1),   # the smallest side whose sum x^2 and sum xy pass 2^32
         "above": lambda: (_random(32, 8, 6) + np.uint32(10), 9),  # every label above K
         "empty": lambda: (np.zeros((32, 32, 32), np.uint32), 4),
         "count0": lambda: (_random(32, 3, 7), 0),
@@ -206,15 +207,15 @@ def case(name):
 
 
 CASES = ("voxel", "corner_voxel", "far_corner_voxel", "ball", "shell", "torus", "halves", "seams", "faces", "faces64", "random5", "random4000",
-         "sparse300", "blobs", "blobs96", "whole96", "above", "empty", "count0")
+         "sparse300", "blobs", "blobs96", "whole96", "whole128", "above", "empty", "count0")
 
 
 @functools.lru_cache(maxsize=None)
 def values_of(name):
-    """the value field of a case: whole96 -- every value 0xFFFFFFFF (the sum needs 64 bits); the others -- random over the full uint32
-    range with 0 and 0xFFFFFFFF forced in"""
+    """the value field of a case: whole96 and whole128 -- every value 0xFFFFFFFF (the sum needs 64 bits); the others -- random over the full
+    uint32 range with 0 and 0xFFFFFFFF forced in"""
     W, _ = case(name)
-    if name == "whole96":
+    if name in ("whole96", "whole128"):
         v = np.full(W.shape, 0xFFFFFFFF, np.uint32)
     else:
         rng = np.random.default_rng(len(name) * 31 + W.shape[0])

@@ -1,9 +1,10 @@
 """Region analysis on the GPU (vp_regions*, csrc/regions.hip) against the numpy restatement of tests/regions_ref.py, table and statistics
 byte for byte, NAIVE and TILED, with and without a value field: the hand cases, a label over every kind of block seam and a block corner,
 voxels on all six grid faces, random labels (K = 5 with ignored labels; K = 4000 where the label slots of a block overflow), values over the
-full uint32 range, one label over the whole 96^3 grid with every value 0xFFFFFFFF, count = 0, every label above K, an empty volume;
-agreement with vp_components_*, vp_skeleton and vp_watershed; what a context keeps between calls, refusals, timing keys, vp_regions_host,
-Engine.regions and `vpcli --regions`.  Sides 32, 64 and 96 only.
+full uint32 range, one label over the whole 96^3 and 128^3 grids with every value 0xFFFFFFFF (at 128 sum x^2 and sum xy pass 2^32), count = 0,
+every label above K, an empty volume; agreement with vp_components_*, vp_skeleton and vp_watershed; what a context keeps between calls,
+refusals, timing keys, vp_regions_host, Engine.regions and `vpcli --regions`.  Sides 32, 64, 96 and 128; side 1024 is in
+tests/test_largest_side_gpu.py, every kind of seam at every phase in tests/test_phases_gpu.py.
 
 The issue asks, for W of the watershed's "equal balls" case, for equal V and equal contact of both labels.  The contact counts are equal; the
 volumes cannot be: vp_watershed gives the voxels ON the symmetry plane x = 32 to label 1 (tests/test_watershed_gpu.py pins that), so
@@ -94,6 +95,8 @@ def test_cases(engine, name, with_values, algo):
         assert stats[1] > 3900                                      # thousands of labels in every block: the 16 slots cannot hold them
     elif name == "whole96":
         assert stats == (96 ** 3, 1, 0, 0) and (not with_values or int(T[0, 22]) == 96 ** 3 * 0xFFFFFFFF)
+    elif name == "whole128":                                        # the smallest side whose sums pass 2^32: every block's share must carry
+        assert stats == (128 ** 3, 1, 0, 0) and [int(t) for t in T[0, 10:16]] == [11319377920] * 3 + [8456241152] * 3
     elif name == "above":
         assert stats == (0, 0, 32 ** 3, 0) and not T.any()
     elif name == "empty":

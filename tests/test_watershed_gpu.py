@@ -3,7 +3,7 @@ tests/watershed_ref.py, byte for byte (labels, cut grid) and statistics included
 cases, markers on every kind of block seam, interfaces along a seam plane and across a block corner, the snake, the diagonal chain,
 random masks with ties everywhere and basins without markers (both quanta, both orders), the extreme labels, an empty mask, no markers,
 markers that cover the mask, a side that is no power of two; what a context keeps between calls, refusals, timing keys,
-vp_watershed_host and Engine.watershed.  Sides 32, 64 and 96 only."""
+vp_watershed_host and Engine.watershed.  Sides 32, 64 and 96; side 1024 is in tests/test_largest_side_gpu.py."""
 import ctypes
 import os
 import sys
