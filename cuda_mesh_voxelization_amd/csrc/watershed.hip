@@ -39,7 +39,7 @@ namespace vp {
 
 namespace {
 
-constexpr uint32_t kWsSweeps = 64;   // TILED: sweeps over a block per launch at most
+constexpr uint32_t kWsSweeps = 64;   // TILED: sweeps over a block per launch at most (the tests read this line: their comb must outlast it)
 constexpr uint32_t kWsBatch = 8;     // NAIVE: rounds enqueued between two read-backs of their flags
 constexpr uint32_t kLabelBits = 20, kRankBits = 14, kTShift = kLabelBits + kRankBits;
 constexpr uint32_t kLabelMask = VP_WS_LABEL_MAX, kBitmapWords = VP_WS_MAX_SPAN / 32;
@@ -338,8 +338,8 @@ int launch_watershed(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const 
     if (top > VP_WS_LABEL_MAX) return set_error(VP_ERR_INVALID, "vp_watershed: marker label %u above VP_WS_LABEL_MAX = %u", top, (uint32_t)VP_WS_LABEL_MAX);
     const uint32_t first = empty ? 0u : pmin / q, last = empty ? 0u : pmax / q;
     if (last - first >= VP_WS_MAX_SPAN)
-        return set_error(VP_ERR_INVALID, "vp_watershed: the levels span %u, VP_WS_MAX_SPAN = %u: the smallest quantum that fits is %u", last - first + 1u,
-                         (uint32_t)VP_WS_MAX_SPAN, fitting_quantum(pmin, pmax, q));
+        return set_error(VP_ERR_INVALID, "vp_watershed: the levels span %llu, VP_WS_MAX_SPAN = %u: the smallest quantum that fits is %u",
+                         (unsigned long long)(last - first) + 1ull, (uint32_t)VP_WS_MAX_SPAN, fitting_quantum(pmin, pmax, q));   // 2^32 levels at most
     std::vector<uint32_t> levels;                                  // the present levels in flood order
     if (!empty)
         for (uint32_t l = first;; ++l) {

@@ -1,5 +1,7 @@
 """Seeded watershed without a GPU: the numpy restatement of tests/watershed_ref.py against its literal form, against the geodesic
-reference (zones), against the component labels, on the two-ball cases of the issue and on hand-made flood orders; the cut grid; the
+reference (zones), against the component labels, on the two-ball cases of the issue and on hand-made flood orders; what the cases at the
+limits of the key reach (priorities up to 2^32 - 1, rank 16383, the extreme labels, gates on block seams, the comb past the sweep cap
+of watershed.hip); the cut grid; the
 host restatement of vplib/src/watershed.cpp through the C++ API on both word types, on every case of the GPU tests, byte for byte and
 statistics included, and its refusals; `vpcli --watershed`; the header's prototypes."""
 import os
@@ -27,11 +29,122 @@ def test_reference_equals_its_literal_form(conn):
     """the index-list form starts a level from the neighbours of the voxels whose level it is: the same bytes as the definition"""
     for name in R.CASES:
         m, L, P, order, q = R.case(name)
-        if m.shape[0] != 32:
+        if not R.has_literal(name):                                 # a side above 32, or thousands of levels: minutes
             continue
         W, cut, stats = R.watershed_literal(m, L, P, order, q, conn)
         e = R.expected(name, conn)
         assert np.array_equal(W, e[0]) and np.array_equal(cut, e[1]) and stats == e[2], (name, conn)
+    # every gate, quantum and comb, and the four wide cases of 256 levels
+    assert all(R.has_literal(name) for name in R.GATE_CASES + R.QUANTA + R.COMBS)
+    assert [name for name in R.WIDES if R.has_literal(name)] == [R.wide_name(q, R.TOP, 256, o) for q in (1, 3) for o in R.ORDERS]
+
+
+# ---- the limits of the key ---------------------------------------------------------------------------------------------------------------
+def levels_of(name):
+    """(first level, last level, q) over M"""
+    m, _, P, _, q = R.case(name)
+    level = P.astype(np.int64)[m] // q
+    return int(level.min()), int(level.max()), q
+
+
+def test_limit_cases_reach_the_limits():
+    """what the wide cases are for, as caps on the cases and not as measurements"""
+    wraps = beyond = 0
+    for name in R.WIDES + R.QUANTA:
+        m, L, P, order, q = R.case(name)
+        first, last, _ = levels_of(name)
+        wraps += first % R.MAX_SPAN + (last - first) >= R.MAX_SPAN  # the index into the presence bitmap wraps
+        beyond += last * q + q - 1 >= 1 << 32                       # the top of the last level's range of P lies beyond uint32
+        rank, levels = R.ranks(m, P, order, q)
+        for conn in R.CONNS:
+            W, _, stats = R.expected(name, conn)
+            assert stats[0] == 12 and stats[1] > 20000 and stats[2] == levels, (name, conn, stats)   # far more labelled than markers
+            assert set(np.unique(W[m]).tolist()) - {0} == set(R.EXTREME_LABELS), (name, conn)
+        assert set(np.unique(L[m]).tolist()) == {0} | set(R.EXTREME_LABELS)
+        if name in R.WIDES:
+            assert last - first == R.MAX_SPAN - 1 and {0, R.MAX_SPAN - 1} <= set(rank[m].tolist()), name
+            assert last == int(name.split()[2][3:]) // q, name
+        else:
+            assert (first, last, levels) == (0, 1, 2) and int(P[m].max()) == R.TOP and int(P[m].min()) == 0, name
+    assert wraps >= 6 and beyond >= 8, (wraps, beyond)
+    # every rank value: the case that asks for all 16384 levels holds as many as the mask lets it, far above 2^13
+    most = R.expected(R.wide_name(1, R.TOP, R.MAX_SPAN, R.ASCENDING), 6)[2][2]
+    assert most > 12000, most
+    assert [levels_of(R.wide_name(3, R.TOP, 256, o))[0] for o in R.ORDERS] == [0x55555555 - (R.MAX_SPAN - 1)] * 2
+    assert R.fitting_quantum(np.array([0, R.TOP], np.uint32), np.ones(2, bool), 1) == 1 << 18
+
+
+def test_a_short_rank_field_cannot_pass():
+    """the reference with the rank cut to 13 bits differs from the true one on thousands of voxels of a wide case"""
+    name = R.wide_name(1, R.TOP, 256, R.DESCENDING)
+    m, L, P, order, q = R.case(name)
+    first, last, _ = levels_of(name)
+    cut_rank = (first + ((last - P.astype(np.int64)) & 0x1FFF)).astype(np.uint32)   # ascending over the cut ranks = descending with 13 bits
+    W = R.watershed(m, L, cut_rank, R.ASCENDING, 1, 6)[0]
+    assert int((W != R.expected(name, 6)[0]).sum()) > 1000
+
+
+@pytest.mark.parametrize("conn", R.CONNS)
+def test_adding_a_constant_to_the_field_changes_nothing(conn):
+    """the wrap far from the top equals its copy moved down to first = 0"""
+    for order in R.ORDERS:
+        name = R.wide_name(1, R.SECOND_WRAP + R.MAX_SPAN - 1, 4096, order)
+        m, L, P, _, q = R.case(name)
+        moved = R.watershed(m, L, P - np.uint32(R.SECOND_WRAP), order, q, conn)
+        e = R.expected(name, conn)
+        assert int(P[m].min()) == R.SECOND_WRAP and np.array_equal(moved[0], e[0]) and np.array_equal(moved[1], e[1]) and moved[2] == e[2]
+
+
+def in_block(W, b):
+    return W[R.block_box(b)]
+
+
+@pytest.mark.parametrize("conn", R.CONNS)
+def test_gates_flood_a_block_at_a_level_it_does_not_hold(conn):
+    for name in R.GATE_CASES:
+        m, L, P, order, q = R.case(name)
+        W, cut, stats = R.expected(name, conn)
+        if name.startswith("two fronts"):
+            a, b, c = R.TWO_FRONTS[name.split()[2]]
+            assert (in_block(W, a) == 9).sum() > 7000 and (in_block(W, c) == 4).sum() > 7000 and stats[:3] == (2, 24576, 2) and stats[3] > 0
+            both = np.unique(in_block(W, b), return_counts=True)
+            assert both[0].tolist() == [4, 9] and both[1].min() > 2000, (name, both)   # B is split between the two fronts
+            continue
+        b = R.GATES[" ".join(name.split()[1:-1])]
+        steps = sum(abs(u - v) for u, v in zip(R.GATE_A, b))
+        assert (in_block(W, R.GATE_A) == 9).all()
+        lo, hi = int(in_block(P, b).min()), int(in_block(P, R.GATE_A).min())
+        assert lo == int(in_block(P, b).max()) and (lo < hi if order == R.ASCENDING else lo > hi)   # B's own level runs first, without a source
+        if steps == 1 or conn == 26:
+            assert stats == (1, 16384, 2, 0) and (in_block(W, b) == 9).all(), (name, conn, stats)
+        else:
+            assert stats == (1, 8192, 2, 0) and not in_block(W, b).any(), (name, conn, stats)
+    assert sorted(sum(abs(u - v) for u, v in zip(R.GATE_A, b)) for b in R.GATES.values()) == [1] * 5 + [2] * 3 + [3] * 2
+
+
+def comb_past_the_sweep_cap():
+    """(mask, start, the sweeps the comb needs, kWsSweeps of watershed.hip), after the check that the first exceeds the second; shared with
+    tests/test_watershed_gpu.py"""
+    with open(os.path.join(os.path.dirname(capi.LIB_PATH), "csrc", "watershed.hip")) as f:
+        cap = int(re.search(r"^constexpr uint32_t kWsSweeps = (\d+);", f.read(), re.M).group(1))
+    mask, start, steps = geodesic_ref.comb()
+    assert steps == 270 and int(mask.sum()) == 271
+    # the 30 steps along x between two corridors cost no sweep of their own (a sweep walks a whole x row): count the 240 along y only
+    assert steps - 30 > cap, "kWsSweeps has caught up with the comb: build a longer maze inside one block for the comb cases"
+    return mask, start, steps - 30, cap
+
+
+def test_the_comb_outlasts_the_sweep_cap():
+    """the comb lies inside one block and a sweep of ws_relax carries a key one row on: its face steps must exceed the sweeps of one launch,
+    so that the block stops at the cap and re-lists itself"""
+    mask, start, _, _ = comb_past_the_sweep_cap()
+    idx = np.argwhere(mask)
+    assert idx[:, 2].max() < 32 and idx[:, 1].max() < 16 and idx[:, 0].max() < 16   # one block
+    for conn in R.CONNS:
+        assert R.expected("comb zones", conn)[2] == (1, 271, 1, 0) and R.expected("comb flood", conn)[2] == (1, 271, 3, 0)
+    P = R.case("comb flood")[2]
+    d = geodesic_ref.geodesic(mask, start, geodesic_ref.GEO_6)[0]
+    assert sorted(set(P[mask].tolist())) == [0, 1, 2] and int(P[mask][np.argsort(d[mask])][-1]) == 2   # 0, 1, 2 along the path: every level ends in the block that is still re-listing itself
 
 
 @pytest.mark.parametrize("conn", R.CONNS)
@@ -199,12 +312,13 @@ def test_host_form_equals_numpy(check_exe, tmp_path, conn):
     for k, name in enumerate(R.CASES):
         mask, markers, P, order, q = R.case(name)
         W, cut, stats = R.expected(name, conn)
-        p, got = run_check(check_exe, mask, markers, P, order, q, conn, 64 if k % 2 else 32, "so", prefix)
-        assert p.returncode == 0, (name, p.stdout[-500:] + p.stderr[-500:])
-        for tag in ("seq", "omp"):
-            assert np.array_equal(got[tag][0], W.reshape(-1)), (name, tag)
-            assert np.array_equal(got[tag][1], R.bool_to_words(cut)), (name, tag)
-            assert got[tag][2] == stats, (name, tag, got[tag][2], stats)
+        for bits in ((32, 64) if name in R.LIMITS else (64 if k % 2 else 32,)):   # the cases at the limits of the key on both word types
+            p, got = run_check(check_exe, mask, markers, P, order, q, conn, bits, "so", prefix)
+            assert p.returncode == 0, (name, bits, p.stdout[-500:] + p.stderr[-500:])
+            for tag in ("seq", "omp"):
+                assert np.array_equal(got[tag][0], W.reshape(-1)), (name, bits, tag)
+                assert np.array_equal(got[tag][1], R.bool_to_words(cut)), (name, bits, tag)
+                assert got[tag][2] == stats, (name, bits, tag, got[tag][2], stats)
 
 
 def test_host_form_on_the_hand_made_orders(check_exe, tmp_path):

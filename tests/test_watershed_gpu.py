@@ -2,10 +2,13 @@
 tests/watershed_ref.py, byte for byte (labels, cut grid) and statistics included, NAIVE and TILED x both connectivities: the two-ball
 cases, markers on every kind of block seam, interfaces along a seam plane and across a block corner, the snake, the diagonal chain,
 random masks with ties everywhere and basins without markers (both quanta, both orders), the extreme labels, an empty mask, no markers,
-markers that cover the mask, a side that is no power of two; what a context keeps between calls, refusals, timing keys,
+markers that cover the mask, a side that is no power of two; the limits of the key (P up to 2^32 - 1, a span of 16383, quanta up to
+2^32 - 1, the extreme labels, all at once), blocks flooded only through a seam, the comb that outlasts the sweep cap; what a context
+keeps between calls, refusals (the quantum they name against the reference), timing keys,
 vp_watershed_host and Engine.watershed.  Sides 32, 64 and 96; side 1024 is in tests/test_largest_side_gpu.py."""
 import ctypes
 import os
+import re
 import sys
 
 import numpy as np
@@ -17,7 +20,7 @@ from cuda_mesh_voxelization_amd.capi import ALGO_NAIVE, ALGO_TILED, Frame
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import watershed_ref as R  # noqa: E402
-from test_watershed_cpu import cli_expected, cli_run  # noqa: E402
+from test_watershed_cpu import cli_expected, cli_run, comb_past_the_sweep_cap  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ALGOS = (ALGO_NAIVE, ALGO_TILED)
@@ -105,14 +108,92 @@ def test_random_masks(engine, name, conn, algo):
     assert " 0.7 " in name or stats[1] < int(mask.sum())             # the sparse masks have components that no marker reaches
 
 
+# ---- 1b: the limits of the key, gates on block seams, the sweep cap --------------------------------------------------------------------------
+@pytest.mark.parametrize("algo", ALGOS)
+@pytest.mark.parametrize("conn", R.CONNS)
+@pytest.mark.parametrize("name", R.WIDES + R.QUANTA)
+def test_priorities_ranks_and_labels_at_their_limits(engine, name, conn, algo):
+    """P up to 2^32 - 1, a level span of exactly 16383 with both ends in M (or a quantum of 2^31 and more), labels 1, 2, 2^20 - 2 and
+    2^20 - 1 flooding at once: every field of the key full at the same time.  What each case reaches is asserted without a GPU in
+    tests/test_watershed_cpu.py::test_limit_cases_reach_the_limits"""
+    mask, markers, P, order, q = R.case(name)
+    exp, _, stats = _check(engine, name, conn, algo)
+    level = P.astype(np.int64)[mask] // q
+    assert int(level.max()) - int(level.min()) == (R.MAX_SPAN - 1 if name in R.WIDES else 1)
+    assert stats[0] == 12 and stats[1] > 20000 and stats[2] == len(np.unique(level))
+    assert set(np.unique(exp[mask]).tolist()) - {0} == set(R.EXTREME_LABELS)
+
+
+@pytest.mark.parametrize("algo", ALGOS)
+@pytest.mark.parametrize("conn", R.CONNS)
+@pytest.mark.parametrize("order", R.ORDERS)
+def test_adding_a_constant_to_the_field_changes_nothing(engine, order, conn, algo):
+    """the case whose presence bits wrap in the middle of the bitmap against its copy moved down to first = 0, which does not wrap"""
+    name = R.wide_name(1, R.SECOND_WRAP + R.MAX_SPAN - 1, 4096, order)
+    mask, markers, P, _, q = R.case(name)
+    exp, cut, stats = R.expected(name, conn)
+    w, c, s = _run(engine, mask, markers, P - np.uint32(R.SECOND_WRAP), order, q, conn, algo)
+    assert np.array_equal(w, exp.reshape(-1)) and np.array_equal(c, R.bool_to_words(cut)) and s == stats
+
+
+@pytest.mark.parametrize("algo", ALGOS)
+@pytest.mark.parametrize("conn", R.CONNS)
+@pytest.mark.parametrize("name", R.GATE_CASES)
+def test_gates_on_block_seams(engine, name, conn, algo):
+    """a full block B whose own level ran before any source touched it, next to a block A (and C) flooded at a level that no voxel of B
+    has: B is on no first list of ws_first, TILED reaches it only through the flags that A's changed seam voxels raise.  With two fronts
+    the reference decides where B is split, so the arrival times behind the seam count, not only that the flood came through"""
+    mask, markers, P, order, q = R.case(name)
+    exp, _, stats = _check(engine, name, conn, algo)
+    if name.startswith("two fronts"):
+        b = R.TWO_FRONTS[name.split()[2]][1]
+        labels, counts = np.unique(exp[R.block_box(b)], return_counts=True)
+        assert labels.tolist() == [4, 9] and counts.min() > 2000 and stats[:3] == (2, 24576, 2) and stats[3] > 0
+        return
+    b = R.GATES[" ".join(name.split()[1:-1])]
+    lo, hi = np.unique(P[R.block_box(b)]), np.unique(P[R.block_box(R.GATE_A)])
+    assert len(lo) == len(hi) == 1 and (lo[0] < hi[0] if order == R.ASCENDING else lo[0] > hi[0])   # [lo, hi] of B never meets A's level
+    if sum(abs(u - v) for u, v in zip(R.GATE_A, b)) == 1 or conn == 26:
+        assert stats == (1, 16384, 2, 0) and (exp[R.block_box(b)] == 9).all()
+    else:
+        assert stats == (1, 8192, 2, 0) and not exp[R.block_box(b)].any()   # no face step leads across an edge or a corner
+
+
+@pytest.mark.parametrize("algo", ALGOS)
+@pytest.mark.parametrize("conn", R.CONNS)
+@pytest.mark.parametrize("name", R.COMBS)
+def test_comb_inside_one_block_exceeds_the_sweep_cap(engine, name, conn, algo):
+    """270 face steps inside one block, 240 of them across x rows -- one sweep each: ws_relax stops at kWsSweeps and the block re-lists
+    itself several times per level; in the flood, three levels end while it does"""
+    mask, start, sweeps, cap = comb_past_the_sweep_cap()            # fails with the advice to build a longer maze once the cap has caught up
+    assert np.array_equal(mask, R.case(name)[0]) and _block_count(mask) == 1
+    exp, _, stats = _check(engine, name, conn, algo)
+    assert stats == (1, 271, 3 if name == "comb flood" else 1, 0) and (exp[mask] == 7).all()
+    if algo == ALGO_TILED and conn == 6 and name == "comb zones":   # a sweep carries a key one x row on: the block ran ceil(240 / cap) times at least
+        ctx = engine.ctx
+        ctx.prof_reset()
+        ctx.prof_enable(True)
+        try:
+            _run(engine, *R.case(name), conn, algo)
+        finally:
+            ctx.prof_enable(False)
+        assert ctx.prof()["md_brick"]["launches"] >= -(-sweeps // cap) > 2
+
+
+def _block_count(mask):
+    idx = np.argwhere(mask)
+    return len(set(map(tuple, np.stack([idx[:, 2] // 32, idx[:, 1] // 16, idx[:, 0] // 16], axis=1).tolist())))
+
+
 # ---- 2: what a context keeps ------------------------------------------------------------------------------------------------------------------
 def test_context_history_and_release(engine):
     runs = (("seams flood", 26, ALGO_TILED), ("snake flood", 6, ALGO_NAIVE), ("not a power of two", 6, ALGO_TILED),
-            ("interface along a seam", 26, ALGO_TILED), ("unequal balls", 6, ALGO_NAIVE), ("empty mask", 6, ALGO_TILED))
+            ("interface along a seam", 26, ALGO_TILED), (R.wide_name(3, R.TOP, 256, R.DESCENDING), 26, ALGO_TILED), ("unequal balls", 6, ALGO_NAIVE),
+            ("empty mask", 6, ALGO_TILED), (R.wide_name(1 << 18, R.TOP, 4096, R.ASCENDING), 6, ALGO_NAIVE), ("gate edge xy asc", 26, ALGO_TILED))
     ctx = capi.Context(0)
     try:
         assert ctx.watershed_result() == (0, 0, (0, 0, 0, 0), 0)
-        for name, conn, algo in runs:                               # n = 64, 32, 96, 32, 64, 32 on one context: a smaller side after a larger
+        for name, conn, algo in runs:                               # n = 64, 32, 96, 32, 32, 64, 32, 32, 64 on one context: a smaller side after a larger
             _check(engine, name, conn, algo, ctx)
         ctx.release()
         assert ctx.watershed_result() == (0, 0, (0, 0, 0, 0), 0)
@@ -173,6 +254,20 @@ def test_refusals_leave_the_previous_result_untouched(engine):
         assert "quantum that fits is 2" in _last_error()
         refused(fr, full.data_ptr(), ok_markers.data_ptr(), wide3.data_ptr(), D, 3, 6, algo, 10001)
         assert "quantum that fits is 4" in _last_error()
+    # the whole range of uint32 in M, and more (lowest P, highest P, quantum): the quantum named is the one the reference finds
+    everything = np.ones(n ** 3, bool)
+    assert R.fitting_quantum(np.array([0, R.TOP], np.uint32), np.ones(2, bool), 1) == 262144
+    for k, (lo, hi, q) in enumerate(((0, R.TOP, 1), (0, R.TOP, 262143), (1000, 1000 + 5 * R.MAX_SPAN + 3, 2), (7, 0xFFFFFFF0, 1000),
+                                     (1 << 31, R.TOP, 1), (R.TOP - 3 * R.MAX_SPAN, R.TOP, 2), (16383, 2 * 16384, 1), (3, R.TOP - 1, 262143))):
+        Q = np.full(n ** 3, lo, np.uint32)
+        Q[(7 * k + 3) % 50::50] = hi
+        fits = R.fitting_quantum(Q, everything, q)
+        assert fits > q and (hi // fits - lo // fits) < R.MAX_SPAN <= (hi // (fits - 1) - lo // (fits - 1))
+        field = _dev(engine, Q)
+        for algo, order in ((T, A), (N, D)):
+            refused(fr, full.data_ptr(), ok_markers.data_ptr(), field.data_ptr(), order, q, 26 if k % 2 else 6, algo, 10001)
+            found = re.search(r"the levels span (\d+), VP_WS_MAX_SPAN = 16384: the smallest quantum that fits is (\d+)$", _last_error())
+            assert found and int(found.group(2)) == fits and int(found.group(1)) == hi // q - lo // q + 1, (lo, hi, q, fits, _last_error())
     # ... outside the mask neither counts
     hole = np.full(fr.words, 0xFFFFFFFF, np.uint32)
     hole[77 // 32] &= ~np.uint32(1 << (77 % 32))
@@ -184,11 +279,14 @@ def test_refusals_leave_the_previous_result_untouched(engine):
     # the bounds themselves are served: label 2^20 - 1, span 16383
     P[100] = R.MAX_SPAN - 1
     widest = _dev(engine, P)
-    for algo in ALGOS:
-        s = engine.ctx.watershed(fr, full.data_ptr(), ok_markers.data_ptr(), widest.data_ptr(), D, 1, 6, algo)
-        assert s[:3] == (2, n ** 3, 2)
-        w, _, _ = _fetch(engine.ctx, n)
-        assert w[77] == R.LABEL_MAX and w[100] in (1, R.LABEL_MAX) and w[5] == 1
+    served = np.where(L > R.LABEL_MAX, R.LABEL_MAX, L).reshape(n, n, n), P.reshape(n, n, n)
+    for order, conn in ((D, 6), (A, 26)):
+        W, cut, stats = R.watershed(np.ones((n,) * 3, bool), served[0], served[1], order, 1, conn)
+        assert stats[:3] == (2, n ** 3, 2) and set(np.unique(W).tolist()) == {1, R.LABEL_MAX}
+        for algo in ALGOS:
+            s = engine.ctx.watershed(fr, full.data_ptr(), ok_markers.data_ptr(), widest.data_ptr(), order, 1, conn, algo)
+            w, c, rs = _fetch(engine.ctx, n)
+            assert np.array_equal(w, W.reshape(-1)) and np.array_equal(c, R.bool_to_words(cut)) and s == rs == stats, (order, conn, algo, s, stats)
     h = np.zeros(fr.words, np.uint32)
     hv = np.zeros(fr.voxels, np.uint32)
     for frame, order, q, conn, algo, code in ((slab, A, 1, 6, T, 10002), (fr, 5, 1, 6, T, 10001), (fr, A, 0, 6, T, 10001), (fr, A, 1, 7, T, 10001),
@@ -251,11 +349,14 @@ def test_naive_rounds_cross_the_flag_ring_twice(engine):
 # ---- 5: vp_watershed_host and the engine ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("conn", R.CONNS)
 def test_host_entry_point(engine, conn):
-    for name, algo in (("snake flood", ALGO_TILED), ("interface along a seam", ALGO_NAIVE)):
+    every = ((True, True, True), (False, True, True), (True, False, True), (True, True, False), (True, False, False), (False, False, True))
+    for name, algo, wants in (("snake flood", ALGO_TILED, every), ("interface along a seam", ALGO_NAIVE, every),
+                              (R.wide_name(3, R.TOP, 4096, R.DESCENDING), ALGO_TILED, every[:1]), ("quantum %d asc" % R.TOP, ALGO_NAIVE, every[:1]),
+                              ("gate corner ++ desc", ALGO_TILED, every[:1]), ("two fronts y asc", ALGO_NAIVE, every[:1])):
         mask, markers, P, order, q = R.case(name)
         exp, cut, stats = R.expected(name, conn)
-        for want in ((True, True, True), (False, True, True), (True, False, True), (True, True, False), (True, False, False), (False, False, True)):
-            w, c, s = engine.ctx.watershed_host(_frame(32), R.bool_to_words(mask), markers.reshape(-1), None if P is None else P.reshape(-1),
+        for want in wants:
+            w, c, s = engine.ctx.watershed_host(_frame(mask.shape[0]), R.bool_to_words(mask), markers.reshape(-1), None if P is None else P.reshape(-1),
                                                 order, q, conn, algo, want)
             assert (w is None) == (not want[0]) and (c is None) == (not want[1]) and (s is None) == (not want[2])
             assert w is None or np.array_equal(w, exp.reshape(-1))

@@ -8,7 +8,9 @@
                            labelled, so every path of level h passes a voxel of level h first.  test_watershed_cpu.py pins it to the
                            literal form.
   cut_of(W, conn)          the cut grid;  stats_of(...)  the four statistics
-and the solids: balls, seams, the snake, the diagonal chain, random masks."""
+and the solids: balls, seams, the snake, the diagonal chain, random masks; the limits of the key (LIMITS): priorities up to 2^32 - 1 with
+every rank up to 16383 and the extreme labels at once, quanta of 2^31 and more, blocks that are flooded only through a seam, and the comb
+maze that outlasts the sweep cap of the TILED kernel."""
 import functools
 
 import numpy as np
@@ -224,9 +226,113 @@ SEAM_MARKERS = [((31, 5, 5), 1), ((32, 40, 21), 2), ((5, 15, 40), 3), ((40, 16, 
                 ((31, 15, 47), 10), ((32, 48, 48), 11)]                                                                              # corners
 
 
+# ---- the limits of the key: priorities near 2^32, every rank up to 16383, the extreme labels at once -----------------------------------
+TOP = 0xFFFFFFFF
+EXTREME_LABELS = (1, 2, LABEL_MAX - 1, LABEL_MAX)
+
+
+def _limit_mask_and_markers(n, rng):
+    """a random mask of density 0.7 and 12 marker voxels inside it, three of each of EXTREME_LABELS"""
+    mask = rng.random((n, n, n)) < 0.7
+    L = np.zeros(n ** 3, np.uint32)
+    L[rng.choice(np.flatnonzero(mask), 12, replace=False)] = rng.permutation(np.repeat(EXTREME_LABELS, 3))
+    return mask, L.reshape(n, n, n)
+
+
+def wide(n, seed, q, top, present, span=MAX_SPAN - 1):
+    """(mask, markers, P): the levels of M are `present` distinct values (fewer where the mask has too few voxels) of first .. first + span
+    with both ends among them, first = top // q - span; P = level * q + a random remainder, clipped to top: the largest level of M is
+    exactly top // q, and with the default span the rank field takes both 0 and 16383"""
+    rng = np.random.default_rng([n, seed, q % (1 << 32), top, present, span])
+    mask, L = _limit_mask_and_markers(n, rng)
+    assert 2 <= present <= span + 1 and top // q >= span
+    inner = 1 + rng.choice(span - 1, present - 2, replace=False)
+    level = np.r_[0, span, inner][rng.integers(0, present, n ** 3)].astype(np.int64)
+    at = rng.choice(np.flatnonzero(mask), 2, replace=False)
+    level[at] = 0, span                                             # both ends are in M whatever the draw
+    first = top // q - span
+    P = np.minimum((first + level) * q + rng.integers(0, q, n ** 3), top)
+    assert int(P.min()) >= 0 and int(P.max()) <= TOP
+    return mask, L, P.astype(np.uint32).reshape(n, n, n)
+
+
+def huge_quantum(n, seed, q):
+    """(mask, markers, P): a quantum of 2^31 or more -- two levels -- with P from the values around 0, q and 2^32"""
+    rng = np.random.default_rng([n, seed, q % (1 << 32), q >> 32])
+    mask, L = _limit_mask_and_markers(n, rng)
+    values = np.array(sorted({0, 1, q - 1, q, min(q + 1, TOP), TOP - 1, TOP}), np.int64)
+    P = values[rng.integers(0, len(values), n ** 3)]
+    at = rng.choice(np.flatnonzero(mask), 2, replace=False)
+    P[at] = 0, TOP
+    return mask, L, P.astype(np.uint32).reshape(n, n, n)
+
+
+SECOND_WRAP = 5 * MAX_SPAN + 9000                                   # a first level whose bit lies in the middle of the presence bitmap
+# (q, top, present): P up to 2^32 - 1 at q = 1 (few levels: the literal form runs it; every level the mask can hold), at q = 3 (the first
+# level is 0x55555555 - 16383: the index into the presence bitmap wraps) and at q = 2^18 (P covers nearly all of uint32), and a wrap
+# far from the top
+WIDE = [(1, TOP, 256), (1, TOP, MAX_SPAN), (3, TOP, 256), (3, TOP, 4096), (1 << 18, TOP, 4096), (1, SECOND_WRAP + MAX_SPAN - 1, 4096)]
+HUGE_QUANTA = [1 << 31, (1 << 31) + 1, TOP]
+LITERAL_LEVELS = 256                                                # watershed_literal takes minutes on thousands of levels
+
+
+def wide_name(q, top, present, order):
+    return "wide q%d top%d p%d %s" % (q, top, present, "asc" if order == ASCENDING else "desc")
+
+
+# ---- gates: a full block that the flood enters through a seam at a level none of its own voxels has --------------------------------------
+GATE_A = (0, 1, 1)                                                  # the block (bx, by, bz) with the marker, of 32 x 16 x 16 voxels at n = 64
+GATES = {"+x": (1, 1, 1), "-y": (0, 0, 1), "+y": (0, 2, 1), "-z": (0, 1, 0), "+z": (0, 1, 2),                 # five faces
+         "edge xy": (1, 2, 1), "edge xz": (1, 1, 0), "edge yz": (0, 0, 2), "corner ++": (1, 2, 2), "corner --": (1, 0, 0)}
+TWO_FRONTS = {"y": ((0, 0, 1), (0, 1, 1), (0, 2, 1)), "z": ((0, 1, 0), (0, 1, 1), (0, 1, 2))}   # A, B between them, C
+
+
+def block_box(b):
+    """the (z, y, x) slices of block (bx, by, bz)"""
+    return slice(16 * b[2], 16 * b[2] + 16), slice(16 * b[1], 16 * b[1] + 16), slice(32 * b[0], 32 * b[0] + 32)
+
+
+def gate(blocks, markers, order):
+    """(mask, markers, P) at n = 64: blocks = [A, B] or [A, B, C], all full; A and C hold P = 5 (ascending) or 0xFFFFFFF0 (descending) and a
+    marker each, B holds 0 or 0xFFFFFFFF: B's own level runs first and floods nothing, and at the level of A no voxel of B has that level"""
+    m = np.zeros((64,) * 3, bool)
+    P = np.zeros((64,) * 3, np.uint32)
+    for k, b in enumerate(blocks):
+        m[block_box(b)] = True
+        P[block_box(b)] = (0 if order == ASCENDING else TOP) if k == 1 else (5 if order == ASCENDING else 0xFFFFFFF0)
+    voxels = []
+    for b, ((dx, dy, dz), label) in zip((blocks[0],) + tuple(blocks[2:]), markers):
+        voxels.append(((32 * b[0] + dx, 16 * b[1] + dy, 16 * b[2] + dz), label))
+    return m, marker_volume(64, voxels), P
+
+
+def comb_case(flood):
+    """the comb maze of geodesic_ref inside one block, 271 voxels and 270 face steps, with one marker at its start; the flood has three
+    levels that come back along the path"""
+    import geodesic_ref
+    m, start, _ = geodesic_ref.comb()
+    L = np.where(start, 7, 0).astype(np.uint32)
+    if not flood:
+        return m, L, None
+    d = geodesic_ref.geodesic(m, start, geodesic_ref.GEO_6)[0].astype(np.int64)
+    return m, L, np.where(m, (d // 100) % 3, 0).astype(np.uint32)
+
+
 def _case(name):
     """(mask, markers, priority or None, order, q) -- the connectivity is the caller's"""
     w = name.split()
+    order = ASCENDING if w[-1] == "asc" else DESCENDING
+    if w[0] == "wide":
+        q, top, present = int(w[1][1:]), int(w[2][3:]), int(w[3][1:])
+        return wide(32, 1, q, top, present) + (order, q)
+    if w[0] == "quantum":
+        return huge_quantum(32, 2, int(w[1])) + (order, int(w[1]))
+    if w[0] == "gate":
+        return gate([GATE_A, GATES[" ".join(w[1:-1])]], [((5, 3, 9), 9)], order) + (order, 1)
+    if name.startswith("two fronts"):
+        return gate(TWO_FRONTS[w[2]], [((5, 3, 9), 9), ((20, 11, 2), 4)], order) + (order, 1)
+    if w[0] == "comb":
+        return comb_case(w[1] == "flood") + (ASCENDING, 1)
     if name.startswith("equal balls"):
         m, L, P, _ = two_balls(EQUAL_BALLS)
         return m, L, P, DESCENDING, 1
@@ -293,8 +399,21 @@ HAND = ["equal balls", "unequal balls", "unequal balls swapped", "seams zones", 
 # meets every side, density and range of P
 RANDOMS = [random_name(n, d, pmax, seed, q, order) for k, (n, d, pmax, seed) in enumerate(RANDOM)
            for q, order in (((1, ASCENDING), (7, DESCENDING)) if (k + k // 3) % 2 == 0 else ((7, ASCENDING), (1, DESCENDING)))]
-CASES = HAND + RANDOMS
+ORDERS = (ASCENDING, DESCENDING)
+WIDES = [wide_name(q, top, present, order) for q, top, present in WIDE for order in ORDERS]
+QUANTA = ["quantum %d %s" % (q, o) for q in HUGE_QUANTA for o in ("asc", "desc")]
+GATE_CASES = ["gate %s %s" % (k, o) for k in GATES for o in ("asc", "desc")] + ["two fronts %s %s" % (k, o) for k in TWO_FRONTS for o in ("asc", "desc")]
+COMBS = ["comb zones", "comb flood"]
+LIMITS = WIDES + QUANTA + GATE_CASES + COMBS
+CASES = HAND + RANDOMS + LIMITS
 CONNS = (6, 26)
+
+
+def has_literal(name):
+    """whether watershed_literal is run on the case: side 32 and few levels, and the gates at side 64 (two levels, short paths)"""
+    if name.startswith("wide"):
+        return int(name.split()[3][1:]) <= LITERAL_LEVELS
+    return case(name)[0].shape[0] == 32 or name in GATE_CASES
 
 
 @functools.lru_cache(maxsize=None)
