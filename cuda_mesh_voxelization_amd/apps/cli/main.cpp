@@ -51,6 +51,11 @@
 //                            and -s act on the separated parts.  Prints "watershed: n N, markers K, marker voxels U, labelled L, levels
 //                            H, cut X"; with -e writes out/<mesh stem>_<type>_labels.raw (n^3 uint32, x fastest); -d PREFIX additionally
 //                            writes PREFIX.labels.u32 (the labels of the first grid).
+//         --watershed h:H[:Q[:C]]  (extension) the same with markers picked automatically: H = a depth in voxels, a decimal number 0 .. 1023,
+//                            h16 = floor(16 H + 1/2).  V = floor(16 sqrt(D2)) (vp_extrema, VP_EXT_SQRT16: the distance in sixteenths of a
+//                            voxel); markers = the components (C) of the extended maxima of V at depth h16 -- the maxima that rise more than
+//                            h16 above every pass to a higher one; priority = V, flooded from the high end in levels of Q (default 1).
+//                            Prints "extrema: n N, h16 X, maxima voxels E, markers K" in front of the watershed line (vox/reconstruct.h).
 //         --regions [C]      (extension) region analysis of the working grid after every grid operator (--morph, --fill, --watershed, CSG) and
 //                            before --thickness, --skeleton, --octree, --geodesic: its components (connectivity C = 6 | 26, default 26) are
 //                            labelled and measured (include/vphip.h, vp_regions; vox/regions.h) with the exact squared distance to the nearest
@@ -127,6 +132,7 @@
 #include "mesh/mesh_io.h"
 #include "proc_utils.h"
 #include "vox/geodesic.h"
+#include "vox/reconstruct.h"
 #include "vox/watershed.h"
 #include "vox/regions.h"
 #include "vox/octree.h"
@@ -164,8 +170,9 @@ struct Options {
     int skeleton = -1;                                      // --skeleton curve|kernel[:ITERS]: VOX::SkeletonMode, -1 = not asked for
     unsigned skeletonIters = 0;
     bool skeletonOnly = false;
-    bool watershed = false;                                 // --watershed R[:Q[:C]]
+    bool watershed = false;                                 // --watershed R[:Q[:C]] | h:H[:Q[:C]]
     unsigned wsRadius = 0, wsQuantum = 1;
+    int wsH16 = -1;                                         // >= 0: the h: form, markers from the extended maxima at this depth
     int wsConn = 6;
     bool regions = false;                                   // --regions [6|26]
     int regionsConn = 26;
@@ -282,6 +289,9 @@ const char* kUsage =
     "                        squared distance map, from its high end in levels of Q (default 1), and cut where they meet.  The cut grid\n"
     "                        replaces the working grid, so every later step and export acts on the separated parts; -e also writes\n"
     "                        out/<mesh>_<type>_labels.raw, -d PREFIX.labels.u32.  One device (extension)\n"
+    "                        arg = h:H[:Q[:C]] picks the markers automatically: the components of the extended maxima, at depth H voxels\n"
+    "                        (a decimal number 0..1023, taken in sixteenths), of the distance map in sixteenths of a voxel, which is then\n"
+    "                        the field that is flooded.  Prints an extrema line in front of the watershed line\n"
     "      --regions [arg]   Region analysis of the working grid after --morph, --fill, --watershed and the CSG: its components\n"
     "                        (connectivity arg = 6 or 26, default 26) are measured -- volume, box, centroid, ellipsoid, surface, contact,\n"
     "                        Euler number, and the squared radius of the largest inscribed ball from the exact distance map -- into\n"
@@ -433,15 +443,32 @@ Options Parse(int argc, char** argv)
                 break;
             }
             case 'Z': {
-                // R[:Q[:6|26]]: the erosion radius 1 .. 65535, the quantum 1 .. 2^32 - 1, the connectivity
+                // R[:Q[:6|26]]: the erosion radius 1 .. 65535, the quantum 1 .. 2^32 - 1, the connectivity; h:H[:Q[:6|26]]: the depth
+                // H = 0 .. 1023 voxels, a decimal number, in place of the radius
                 std::vector<std::string> fields;
-                for (size_t at = 0;;) {
+                const bool byDepth = value.rfind("h:", 0) == 0;
+                for (size_t at = byDepth ? 2 : 0;;) {
                     const size_t end = value.find(':', at);
                     fields.push_back(value.substr(at, end == std::string::npos ? end : end - at));
                     if (end == std::string::npos) break;
                     at = end + 1;
                 }
                 auto digits = [](const std::string& t, size_t most) { return !t.empty() && t.size() <= most && t.find_first_not_of("0123456789") == std::string::npos; };
+                if (byDepth) {
+                    const std::string& t = fields[0];
+                    const size_t dot = t.find('.');
+                    bool ok = fields.size() <= 3 && !t.empty() && t.size() <= 12 && t.find_first_not_of("0123456789.") == std::string::npos &&
+                              (dot == std::string::npos || t.find('.', dot + 1) == std::string::npos) && t.find_first_of("0123456789") != std::string::npos;
+                    ok = ok && std::stod(t) <= 1023.0;
+                    ok = ok && (fields.size() < 2 || (digits(fields[1], 10) && std::stoull(fields[1]) >= 1 && std::stoull(fields[1]) <= 0xFFFFFFFFull));
+                    ok = ok && (fields.size() < 3 || fields[2] == "6" || fields[2] == "26");
+                    cpuAssert(ok, "--watershed: '" + value + "' is not h:H[:Q[:C]] with H in 0..1023 voxels (a decimal number), a quantum Q >= 1 and C = 6 or 26\n");
+                    o.watershed = true;
+                    o.wsH16 = static_cast<int>(std::stod(t) * 16.0 + 0.5);
+                    o.wsQuantum = fields.size() >= 2 ? static_cast<unsigned>(std::stoull(fields[1])) : 1u;
+                    o.wsConn = fields.size() >= 3 ? std::stoi(fields[2]) : 6;
+                    break;
+                }
                 bool ok = fields.size() >= 1 && fields.size() <= 3 && digits(fields[0], 5) && std::stoul(fields[0]) >= 1 && std::stoul(fields[0]) <= 65535;
                 ok = ok && (fields.size() < 2 || (digits(fields[1], 10) && std::stoull(fields[1]) >= 1 && std::stoull(fields[1]) <= 0xFFFFFFFFull));
                 ok = ok && (fields.size() < 3 || fields[2] == "6" || fields[2] == "26");
@@ -590,11 +617,36 @@ void OctreeOut(const HostVoxelsGrid<gridType>& grid, const std::string& path)
 }
 
 // --watershed: `grid` is replaced by the cut grid of its watershed -- markers = the components of the grid eroded by `radius`, priority =
-// the squared distance to the nearest unset voxel, flooded from the high end; `labels` gets the label volume; prints what the flag promises
+// the squared distance to the nearest unset voxel, flooded from the high end; `labels` gets the label volume; prints what the flag promises.
+// h16 >= 0 (the h: form): markers = the components of the extended maxima at depth h16 of the distance in sixteenths of a voxel, which is
+// also the priority
 template <Types T>
-void WatershedSplit(unsigned radius, unsigned quantum, int conn, HostVoxelsGrid<gridType>& grid, HostGrid<uint32_t>& labels)
+void WatershedSplit(unsigned radius, int h16, unsigned quantum, int conn, HostVoxelsGrid<gridType>& grid, HostGrid<uint32_t>& labels)
 {
     const size_t n = grid.View().VoxelsPerSide();
+    if (h16 >= 0) {
+        HostGrid<uint32_t> markers, dist, scaled, flat;
+        HostVoxelsGrid<gridType> maxima, cut;
+        VOX::DistanceTransform<T>(grid, dist, VOX::EdtSeeds::UNSET);
+        const VOX::ExtremaStats es = VOX::Extrema<T>(grid, false, dist, VOX::EXTREMA_MAXIMA, VOX::EXTREMA_SQRT16, static_cast<uint32_t>(h16), conn, scaled,
+                                                     flat, maxima);
+        const uint32_t count = VOX::LabelComponents<T>(maxima, markers, conn);
+        cpuAssert(count <= VOX::WATERSHED_LABEL_MAX, "--watershed: more than 2^20 - 1 markers: give a larger H\n");
+        const uint32_t* v = scaled.View().Data();
+        uint32_t lo = 0xFFFFFFFFu, hi = 0;
+        const uint32_t* bits = reinterpret_cast<const uint32_t*>(grid.View().Data());
+        for (size_t i = 0; i < n * n * n; ++i)
+            if ((bits[i >> 5] >> (i & 31)) & 1u) { lo = std::min(lo, v[i]); hi = std::max(hi, v[i]); }
+        cpuAssert(lo > hi || hi / quantum - lo / quantum < VOX::WATERSHED_MAX_SPAN,
+                  "--watershed: the distance map spans 16384 levels or more at this quantum: give a larger Q\n");
+        const VOX::WatershedStats st = VOX::Watershed<T>(grid, markers, &scaled, VOX::WATERSHED_DESCENDING, quantum, conn, labels, &cut);
+        std::memcpy(grid.View().Data(), cut.View().Data(), grid.View().StorageSize() * sizeof(gridType));
+        std::printf("extrema: n %zu, h16 %d, maxima voxels %llu, markers %u\n", n, h16, static_cast<unsigned long long>(es.extrema), count);
+        std::printf("watershed: n %zu, markers %u, marker voxels %llu, labelled %llu, levels %llu, cut %llu\n", n, count,
+                    static_cast<unsigned long long>(st.markers), static_cast<unsigned long long>(st.labelled), static_cast<unsigned long long>(st.levels),
+                    static_cast<unsigned long long>(st.cutVoxels));
+        return;
+    }
     HostVoxelsGrid<gridType> cores(n, grid.View().VoxelSize());
     cores.View().SetOrigin(grid.View().OriginX(), grid.View().OriginY(), grid.View().OriginZ());
     std::memcpy(cores.View().Data(), grid.View().Data(), grid.View().StorageSize() * sizeof(gridType));
@@ -856,10 +908,10 @@ int main(int argc, char** argv)
             }
             if (opt.watershed) {
                 switch (TYPE) {
-                    case Types::SEQUENTIAL: WatershedSplit<Types::SEQUENTIAL>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
-                    case Types::OPENMP:     WatershedSplit<Types::OPENMP>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
-                    case Types::NAIVE:      WatershedSplit<Types::NAIVE>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
-                    case Types::TILED:      WatershedSplit<Types::TILED>(opt.wsRadius, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                    case Types::SEQUENTIAL: WatershedSplit<Types::SEQUENTIAL>(opt.wsRadius, opt.wsH16, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                    case Types::OPENMP:     WatershedSplit<Types::OPENMP>(opt.wsRadius, opt.wsH16, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                    case Types::NAIVE:      WatershedSplit<Types::NAIVE>(opt.wsRadius, opt.wsH16, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
+                    case Types::TILED:      WatershedSplit<Types::TILED>(opt.wsRadius, opt.wsH16, opt.wsQuantum, opt.wsConn, grid, wsLabels); break;
                 }
                 if (EXPORT)
                     WriteRaw("out/" + std::filesystem::path(GetFilename(opt.filenames[i])).stem().string() + "_" + typeName + "_labels.raw",

@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvphip.so")
 CLI = os.path.join(PKG, "vpcli")
 
-HIP_SOURCES = ["capi.hip", "vox.hip", "csg.hip", "jfa_seed.hip", "jfa_first_two.hip", "jfa_dense.hip", "extract.hip", "multi.hip", "cvox.hip", "fill.hip", "morph.hip", "components.hip", "surfnets.hip", "edt.hip", "meshdist.hip", "isonets.hip", "winding.hip", "thickness.hip", "octree.hip", "skeleton.hip", "geodesic.hip", "watershed.hip", "regions.hip"]
+HIP_SOURCES = ["capi.hip", "vox.hip", "csg.hip", "jfa_seed.hip", "jfa_first_two.hip", "jfa_dense.hip", "extract.hip", "multi.hip", "cvox.hip", "fill.hip", "morph.hip", "components.hip", "surfnets.hip", "edt.hip", "meshdist.hip", "isonets.hip", "winding.hip", "thickness.hip", "octree.hip", "skeleton.hip", "geodesic.hip", "watershed.hip", "regions.hip", "reconstruct.hip"]
 DENSE_PARTS = 10                 # jfa_dense.hip is compiled once per id format and pass kind, side by side (-DVP_DENSE_PART=1..10, see the end of the file)
 HOOK_SOURCES = ["vox.hip", "multi.hip", "cvox.hip", "meshdist.hip"]     # the sources that read test hooks from the environment under -DVP_TEST_HOOKS (libvphip_hooks.so)
 HOOKS_LIB = os.path.join(PKG, "libvphip_hooks.so")

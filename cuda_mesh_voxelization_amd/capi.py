@@ -21,6 +21,9 @@ ISO_LINEAR, ISO_SIGNED_SQUARE = 0, 1                                # vp_isonets
 CONN_6, CONN_26 = 6, 26                                             # vp_components_*: face / face + edge + corner neighbours
 SKEL_KERNEL, SKEL_CURVE = 0, 1                                      # vp_skeleton: the homotopy kernel / the centre line (line ends stay)
 GEO_6, GEO_26, GEO_CHAMFER = 0, 1, 2                                # vp_geodesic: face steps / all 26 steps at cost 1 / at cost 3, 4, 5
+REC_DILATION, REC_EROSION = 0, 1                                    # vp_reconstruct: by dilation (raise the marker under the mask) / by erosion
+EXT_MAXIMA, EXT_MINIMA = 0, 1                                       # vp_extrema: h-maxima / h-minima
+EXT_LINEAR, EXT_SQRT16 = 0, 1                                       # vp_extrema: the values as they are / floor(sqrt(256 v))
 WS_ASCENDING, WS_DESCENDING = 0, 1                                  # vp_watershed: flood from low / from high priority
 WS_LABEL_MAX, WS_MAX_SPAN = 0xFFFFF, 16384                          # vp_watershed: the largest marker label, the bound of the level span
 REGION_WORDS, REGIONS_MAX = 26, 0xFFFFF                             # vp_regions: uint64 words per record, the largest label count
@@ -80,6 +83,8 @@ SYMBOLS = [
     "vp_geodesic", "vp_geodesic_result", "vp_geodesic_host",
     "vp_watershed", "vp_watershed_result", "vp_watershed_host",
     "vp_regions", "vp_regions_result", "vp_regions_host",
+    "vp_reconstruct", "vp_reconstruct_result", "vp_reconstruct_host",
+    "vp_extrema", "vp_extrema_result", "vp_extrema_host",
 ]
 
 
@@ -235,6 +240,12 @@ def lib():
         "vp_geodesic": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
         "vp_geodesic_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
         "vp_geodesic_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+        "vp_reconstruct": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+        "vp_reconstruct_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_reconstruct_host": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+        "vp_extrema": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp]),
+        "vp_extrema_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "vp_extrema_host": (ctypes.c_int, [_vp, fp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
         "vp_watershed": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp]),
         "vp_watershed_result": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_uint32)]),
         "vp_watershed_host": (ctypes.c_int, [_vp, fp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
@@ -744,6 +755,39 @@ class Context:
         check(lib().vp_watershed_result(self._h, ctypes.byref(d), ctypes.byref(r), s, ctypes.byref(n)))
         return d.value or 0, r.value or 0, tuple(int(v) for v in s), int(n.value)
 
+    def reconstruct(self, frame: Frame, d_marker: int, d_mask: int, d_domain: int = 0, mode: int = REC_DILATION, connectivity: int = CONN_6,
+                    algo: int = ALGO_TILED):
+        """Grayscale reconstruction of the marker field under the mask field (uint32 per voxel) on the domain (a bit grid; 0: every voxel)
+        of a whole grid (n <= 1024) into a buffer the context owns; reconstruct_result() hands it out.  Blocks (convergence is read back)
+        and returns (domain voxels, voxels that changed, sum of R, largest R -- REC_EROSION: the smallest)."""
+        s = (ctypes.c_uint64 * 4)()
+        check(lib().vp_reconstruct(self._h, ctypes.byref(frame), _vp(d_domain or None), _vp(d_marker or None), _vp(d_mask or None), mode,
+                                   connectivity, algo, s))
+        return tuple(int(v) for v in s)
+
+    def reconstruct_result(self):
+        """(d_field, stats, n) of the last reconstruct(): the device pointer as an int (0 where there is none), the four statistics and
+        the side they are for.  Valid until the next reconstruct(), release() or close()."""
+        d, s, n = _vp(), (ctypes.c_uint64 * 4)(), ctypes.c_uint32()
+        check(lib().vp_reconstruct_result(self._h, ctypes.byref(d), s, ctypes.byref(n)))
+        return d.value or 0, tuple(int(v) for v in s), int(n.value)
+
+    def extrema(self, frame: Frame, d_values: int, d_domain: int = 0, kind: int = EXT_MAXIMA, scale: int = EXT_LINEAR, h: int = 0,
+                connectivity: int = CONN_6, algo: int = ALGO_TILED):
+        """h-maxima / h-minima and the extended extrema of a value field (uint32 per voxel) on the domain (a bit grid; 0: every voxel) of a
+        whole grid (n <= 1024) into buffers the context owns; extrema_result() hands them out.  Blocks and returns (domain voxels, extrema
+        voxels, largest H -- EXT_MINIMA: the smallest --, voxels with H != V)."""
+        s = (ctypes.c_uint64 * 4)()
+        check(lib().vp_extrema(self._h, ctypes.byref(frame), _vp(d_domain or None), _vp(d_values or None), kind, scale, h, connectivity, algo, s))
+        return tuple(int(v) for v in s)
+
+    def extrema_result(self):
+        """(d_scaled, d_flat, d_extrema, stats, n) of the last extrema(): the device pointers as ints (0 where there is none), the four
+        statistics and the side they are for.  Valid until the next extrema(), release() or close()."""
+        v, f, e, s, n = _vp(), _vp(), _vp(), (ctypes.c_uint64 * 4)(), ctypes.c_uint32()
+        check(lib().vp_extrema_result(self._h, ctypes.byref(v), ctypes.byref(f), ctypes.byref(e), s, ctypes.byref(n)))
+        return v.value or 0, f.value or 0, e.value or 0, tuple(int(x) for x in s), int(n.value)
+
     def regions(self, frame: Frame, d_labels: int, count: int, d_values: int = 0, algo: int = ALGO_TILED):
         """Region analysis of a label volume (uint32 per voxel; labels 1 .. count, anything above is ignored) of a whole grid (n <= 1024),
         with an optional value field (uint32 per voxel; 0: none), into a table the context owns: count records of REGION_WORDS uint64
@@ -771,6 +815,32 @@ class Context:
                                     None if h_values is None else h_values.ctypes.data_as(_vp), algo,
                                     None if t is None else t.ctypes.data_as(_vp), s))
         return t, None if s is None else tuple(int(v) for v in s)
+
+    def reconstruct_host(self, frame: Frame, h_marker, h_mask, h_domain=None, mode: int = REC_DILATION, connectivity: int = CONN_6,
+                         algo: int = ALGO_TILED, want=(True, True)):
+        """numpy in, numpy out: (field uint32[n^3], statistics); want = which of the two are asked for (the other goes in as NULL and comes
+        back as None)."""
+        np = __import__("numpy")
+        r = np.empty(frame.voxels, np.uint32) if want[0] else None
+        s = (ctypes.c_uint64 * 4)() if want[1] else None
+        check(lib().vp_reconstruct_host(self._h, ctypes.byref(frame), None if h_domain is None else h_domain.ctypes.data_as(_vp),
+                                        h_marker.ctypes.data_as(_vp), h_mask.ctypes.data_as(_vp), mode, connectivity, algo,
+                                        None if r is None else r.ctypes.data_as(_vp), s))
+        return r, None if s is None else tuple(int(v) for v in s)
+
+    def extrema_host(self, frame: Frame, h_values, h_domain=None, kind: int = EXT_MAXIMA, scale: int = EXT_LINEAR, h: int = 0,
+                     connectivity: int = CONN_6, algo: int = ALGO_TILED, want=(True, True, True, True)):
+        """numpy in, numpy out: (scaled uint32[n^3], flat uint32[n^3], extrema words uint32[n^3 / 32], statistics); want = which of the four
+        are asked for (the others go in as NULL and come back as None)."""
+        np = __import__("numpy")
+        v = np.empty(frame.voxels, np.uint32) if want[0] else None
+        f = np.empty(frame.voxels, np.uint32) if want[1] else None
+        e = np.empty(frame.voxels // 32, np.uint32) if want[2] else None
+        s = (ctypes.c_uint64 * 4)() if want[3] else None
+        p = lambda a: None if a is None else a.ctypes.data_as(_vp)
+        check(lib().vp_extrema_host(self._h, ctypes.byref(frame), p(h_domain), h_values.ctypes.data_as(_vp), kind, scale, h, connectivity, algo,
+                                    p(v), p(f), p(e), s))
+        return v, f, e, None if s is None else tuple(int(x) for x in s)
 
     def watershed_host(self, frame: Frame, h_mask, h_markers, h_priority=None, order: int = WS_DESCENDING, quantum: int = 1,
                        connectivity: int = CONN_6, algo: int = ALGO_TILED, want=(True, True, True)):

@@ -177,7 +177,7 @@ static int host_round_trip(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_wor
 }
 
 // One path for the calls that build a result the context owns (vp_isonets, vp_winding, vp_thickness, vp_octree, vp_octree_expand,
-// vp_skeleton, vp_geodesic, vp_watershed, vp_regions): `ft` is the feature that is built, `also` what the call writes besides that feature's buffers, launch() the
+// vp_skeleton, vp_geodesic, vp_watershed, vp_regions, vp_reconstruct, vp_extrema): `ft` is the feature that is built, `also` what the call writes besides that feature's buffers, launch() the
 // work.  The inputs are read while every one of those buffers is written: an input that lies in one is refused (the last result has to be
 // copied before it goes back in); `inputs` is empty for the calls that have never refused it.  The context's own buffers are outputs
 // like any other: whatever was recorded about their bytes is gone -- about the bytes they hold now (a buffer that has to grow is freed
@@ -1376,6 +1376,80 @@ int vp_watershed_result(vp_ctx* ctx, uint32_t** d_labels, uint32_t** d_cut, uint
     return 0;
 }
 
+// ---- grayscale reconstruction and h-extrema -------------------------------------------------------------
+// what vp_reconstruct, vp_extrema and their host forms share: whole grids up to n = 1024, the algo, the connectivity
+static int check_reconstruct(const vp_frame* f, const char* who, int conn, int algo)
+{
+    VP_TRY(check_grid_1024(f, who, algo));
+    if (conn != VP_CONN_6 && conn != VP_CONN_26) return set_error(VP_ERR_INVALID, "%s: unknown connectivity %d", who, conn);
+    return 0;
+}
+static int check_rec_mode(const char* who, int mode)
+{
+    if (mode != VP_REC_DILATION && mode != VP_REC_EROSION) return set_error(VP_ERR_INVALID, "%s: unknown mode %d", who, mode);
+    return 0;
+}
+static int check_extrema(const char* who, int kind, int scale)
+{
+    if (kind != VP_EXT_MAXIMA && kind != VP_EXT_MINIMA) return set_error(VP_ERR_INVALID, "%s: unknown kind %d", who, kind);
+    if (scale != VP_EXT_LINEAR && scale != VP_EXT_SQRT16) return set_error(VP_ERR_INVALID, "%s: unknown scale %d", who, scale);
+    return 0;
+}
+
+int vp_reconstruct(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_domain, const uint32_t* d_marker, const uint32_t* d_mask, int mode,
+                   int connectivity, int algo, uint64_t* h_stats)
+{
+    const char* who = "vp_reconstruct";
+    if (!ctx || !f || !d_marker || !d_mask) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_reconstruct(f, who, connectivity, algo));
+    VP_TRY(check_rec_mode(who, mode));
+    VP_TRY(check_aligned(who, {d_domain, d_marker, d_mask}));
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;   // (a null domain overlaps nothing)
+    return build_owned(ctx, who, ctx->rc, {}, {{d_domain, wb}, {d_marker, vb}, {d_mask, vb}}, [&] {
+        return launch_reconstruct(ctx, make_frame(f), d_domain, d_marker, d_mask, mode, connectivity, algo, h_stats);
+    });
+}
+
+int vp_reconstruct_result(vp_ctx* ctx, uint32_t** d_field, uint64_t* h_stats, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_reconstruct_result: null ctx");
+    const bool any = ctx->rc.n != 0;
+    if (d_field) *d_field = any ? (uint32_t*)ctx->rc.field.ptr : nullptr;
+    if (h_stats)
+        for (int i = 0; i < 4; ++i) h_stats[i] = any ? ctx->rc.stats[i] : 0;
+    if (h_n) *h_n = ctx->rc.n;
+    return 0;
+}
+
+int vp_extrema(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_domain, const uint32_t* d_values, int kind, int scale, uint32_t h,
+               int connectivity, int algo, uint64_t* h_stats)
+{
+    const char* who = "vp_extrema";
+    if (!ctx || !f || !d_values) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(bind_device(ctx));
+    VP_TRY(check_reconstruct(f, who, connectivity, algo));
+    VP_TRY(check_extrema(who, kind, scale));
+    VP_TRY(check_aligned(who, {d_domain, d_values}));
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    return build_owned(ctx, who, ctx->ex, {}, {{d_domain, wb}, {d_values, vb}}, [&] {
+        return launch_extrema(ctx, make_frame(f), d_domain, d_values, kind, scale, h, connectivity, algo, h_stats);
+    });
+}
+
+int vp_extrema_result(vp_ctx* ctx, uint32_t** d_scaled, uint32_t** d_flat, uint32_t** d_extrema, uint64_t* h_stats, uint32_t* h_n)
+{
+    if (!ctx) return set_error(VP_ERR_INVALID, "vp_extrema_result: null ctx");
+    const bool any = ctx->ex.n != 0;
+    if (d_scaled) *d_scaled = any ? (uint32_t*)ctx->ex.scaled.ptr : nullptr;
+    if (d_flat) *d_flat = any ? (uint32_t*)ctx->ex.flat.ptr : nullptr;
+    if (d_extrema) *d_extrema = any ? (uint32_t*)ctx->ex.extrema.ptr : nullptr;
+    if (h_stats)
+        for (int i = 0; i < 4; ++i) h_stats[i] = any ? ctx->ex.stats[i] : 0;
+    if (h_n) *h_n = ctx->ex.n;
+    return 0;
+}
+
 // ---- region analysis ----------------------------------------------------------------------------------
 // what vp_regions and its host form share: whole grids up to n = 1024, the algo, the bound of the label count
 static int check_regions(const vp_frame* f, const char* who, uint32_t count, int algo)
@@ -1609,6 +1683,39 @@ int vp_watershed_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, co
     VP_TRY(vp_watershed(ctx, f, (const uint32_t*)dm, (const uint32_t*)dl, (const uint32_t*)dp, order, quantum, connectivity, algo, h_stats));
     if (h_labels) VP_TRY(vp_download(ctx, h_labels, ctx->wsd.labels.ptr, vb));
     return h_cut ? vp_download(ctx, h_cut, ctx->wsd.cut.ptr, wb) : 0;
+}
+
+int vp_reconstruct_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_domain, const uint32_t* h_marker, const uint32_t* h_mask, int mode,
+                        int connectivity, int algo, uint32_t* h_field, uint64_t* h_stats)
+{
+    const char* who = "vp_reconstruct_host";
+    if (!ctx || !f || !h_marker || !h_mask || (!h_field && !h_stats)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_reconstruct(f, who, connectivity, algo));
+    VP_TRY(check_rec_mode(who, mode));
+    void *dd = nullptr, *df = nullptr, *dg = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    if (h_domain) VP_TRY(stage(ctx, SLOT_GRID_A, h_domain, wb, &dd));
+    VP_TRY(stage(ctx, SLOT_SDF, h_marker, vb, &df));
+    VP_TRY(stage(ctx, SLOT_NEAREST, h_mask, vb, &dg));
+    VP_TRY(vp_reconstruct(ctx, f, (const uint32_t*)dd, (const uint32_t*)df, (const uint32_t*)dg, mode, connectivity, algo, h_stats));
+    return h_field ? vp_download(ctx, h_field, ctx->rc.field.ptr, vb) : 0;
+}
+
+int vp_extrema_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_domain, const uint32_t* h_values, int kind, int scale, uint32_t h,
+                    int connectivity, int algo, uint32_t* h_scaled, uint32_t* h_flat, uint32_t* h_extrema, uint64_t* h_stats)
+{
+    const char* who = "vp_extrema_host";
+    if (!ctx || !f || !h_values || (!h_scaled && !h_flat && !h_extrema && !h_stats)) return set_error(VP_ERR_INVALID, "%s: null argument", who);
+    VP_TRY(check_reconstruct(f, who, connectivity, algo));
+    VP_TRY(check_extrema(who, kind, scale));
+    void *dd = nullptr, *dv = nullptr;
+    const size_t wb = vp_grid_words(f) * 4, vb = vp_grid_voxels(f) * 4;
+    if (h_domain) VP_TRY(stage(ctx, SLOT_GRID_A, h_domain, wb, &dd));
+    VP_TRY(stage(ctx, SLOT_SDF, h_values, vb, &dv));
+    VP_TRY(vp_extrema(ctx, f, (const uint32_t*)dd, (const uint32_t*)dv, kind, scale, h, connectivity, algo, h_stats));
+    if (h_scaled) VP_TRY(vp_download(ctx, h_scaled, ctx->ex.scaled.ptr, vb));
+    if (h_flat) VP_TRY(vp_download(ctx, h_flat, ctx->ex.flat.ptr, vb));
+    return h_extrema ? vp_download(ctx, h_extrema, ctx->ex.extrema.ptr, wb) : 0;
 }
 
 int vp_regions_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_labels, uint32_t count, const uint32_t* h_values, int algo, uint64_t* h_table,

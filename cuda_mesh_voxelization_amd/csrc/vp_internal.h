@@ -255,6 +255,22 @@ struct vp_ctx {
         uint64_t stats[4] = {};
         void forget() { OwnedResult::forget(); count = 0; }
     } rg;
+    // grayscale reconstruction (reconstruct.hip): R (4 n^3 bytes) of the last vp_reconstruct, which the context owns and
+    // vp_reconstruct_result hands out, and its four statistics; the counters with TILED's block flags and list of active blocks
+    // (block_list.h) or NAIVE's ring of round flags; the pinned host words they come back through
+    struct Rc : vp::OwnedResult {
+        VP_BUFFERS(released, field, aux)
+        vp::HostWords<uint64_t> host;
+        uint64_t stats[4] = {};
+    } rc;
+    // h-extrema (reconstruct.hip): the scaled field V, the flattened field H (4 n^3 bytes each) and the grid E of the extended extrema
+    // (n^3 / 8 bytes) of the last vp_extrema, which the context owns and vp_extrema_result hands out, and its four statistics; the field of
+    // the second reconstruction (4 n^3 bytes of scratch) and counters, flags and host words of its own, like Rc's
+    struct Ex : vp::OwnedResult {
+        VP_BUFFERS(released, scaled, flat, extrema, tmp, aux)
+        vp::HostWords<uint64_t> host;
+        uint64_t stats[4] = {};
+    } ex;
     // vp_extract_*: block counts / offsets of the last count call and what it was for (words = nullptr: nothing)
     struct Ext : vp::Feature {
         VP_BUFFERS(kept, cnt, off)
@@ -286,7 +302,7 @@ struct vp_ctx {
     // f(feature) for every feature of the context: how vp_ctx_release and vp_ctx_destroy find every buffer
     template <typename F> void each_feature(F f)
     {
-        f(ws); f(vox); f(cvox); f(fill); f(morph); f(comp); f(sn); f(edt); f(md); f(iso); f(wn); f(th); f(oc); f(ocx); f(sk); f(gd); f(wsd); f(rg); f(ext); f(jfa);
+        f(ws); f(vox); f(cvox); f(fill); f(morph); f(comp); f(sn); f(edt); f(md); f(iso); f(wn); f(th); f(oc); f(ocx); f(sk); f(gd); f(wsd); f(rg); f(rc); f(ex); f(ext); f(jfa);
     }
 };
 
@@ -365,6 +381,13 @@ int launch_watershed(vp_ctx* ctx, const Frame& f, const uint32_t* d_mask, const 
 // regions.hip: the per-label records of a label volume (volume, box, moments, faces, lattice points and edges, values) into the context's own
 // table (blocks once: the four totals are read back); d_values may be null
 int launch_regions(vp_ctx* ctx, const Frame& f, const uint32_t* d_labels, uint32_t count, const uint32_t* d_values, int algo, uint64_t* h_stats);
+// reconstruct.hip: grayscale reconstruction of a marker field under a mask field, and the scaled field, the flattened field and the grid of
+// the extended extrema of a value field, into the context's own buffers (block: the round flags or the length of the block list are
+// read back); d_domain may be null
+int launch_reconstruct(vp_ctx* ctx, const Frame& f, const uint32_t* d_domain, const uint32_t* d_marker, const uint32_t* d_mask, int mode, int conn,
+                       int algo, uint64_t* h_stats);
+int launch_extrema(vp_ctx* ctx, const Frame& f, const uint32_t* d_domain, const uint32_t* d_values, int kind, int scale, uint32_t h, int conn,
+                   int algo, uint64_t* h_stats);
 // meshdist.hip: narrow-band squared distance to the triangles of a mesh and the nearest face of a whole grid (TILED blocks once: it reads
 // the list lengths back)
 int launch_mesh_distance(vp_ctx* ctx, const Frame& f, const float* d_xyz, size_t nverts, const uint32_t* d_tri, size_t ntris,

@@ -214,6 +214,32 @@ class Engine:
         dg, _, _ = self.ctx.skeleton_result()
         return torch.as_tensor(_DeviceView(dg, frame.voxels // 32, "<i4", self), device=self.device), stats
 
+    def reconstruct(self, frame: Frame, marker, mask, domain=None, mode: int = capi.REC_DILATION, connectivity: int = capi.CONN_6,
+                    algo: int = ALGO_TILED):
+        """Grayscale reconstruction of a grid (n <= 1024): returns (field, stats) -- a tensor of n^3 values, x fastest: the marker field
+        raised under the mask field along paths inside `domain` (a bit grid in the library's layout; None: every voxel) for
+        capi.REC_DILATION, lowered above it for capi.REC_EROSION; off the domain it reads 0 / -1 in the int32 view -- and (domain voxels,
+        voxels that changed, sum of the field over the domain, its largest value -- erosion: the smallest).  The tensor is a VIEW of a
+        buffer the context owns: it is overwritten by the next reconstruct() and dies with release() / close() -- clone() what has to
+        live longer (also before it goes back in as `marker` or `mask`).  Blocking."""
+        stats = self.ctx.reconstruct(frame, marker.data_ptr(), mask.data_ptr(), 0 if domain is None else domain.data_ptr(), mode, connectivity, algo)
+        dr, _, _ = self.ctx.reconstruct_result()
+        return torch.as_tensor(_DeviceView(dr, frame.voxels, "<i4", self), device=self.device), stats
+
+    def extrema(self, frame: Frame, values, domain=None, kind: int = capi.EXT_MAXIMA, scale: int = capi.EXT_LINEAR, h: int = 0,
+                connectivity: int = capi.CONN_6, algo: int = ALGO_TILED):
+        """h-extrema of a value field of a grid (n <= 1024): returns (scaled, flat, extrema, stats) -- the scaled field V (the values, or
+        floor(sqrt(256 v)) for capi.EXT_SQRT16: a squared distance in sixteenths of a voxel), the field H with every maximum (minimum)
+        of depth below h flattened, the grid of the extended maxima (minima) in the library's bit layout -- label it with components()
+        for the markers of watershed(), and flood V -- and (domain voxels, extrema voxels, largest H -- minima: the smallest --, voxels
+        with H != V).  The three tensors are VIEWS of buffers the context owns: they are overwritten by the next extrema() and die with
+        release() / close() -- clone() what has to live longer (also before one goes back in).  Blocking."""
+        stats = self.ctx.extrema(frame, values.data_ptr(), 0 if domain is None else domain.data_ptr(), kind, scale, h, connectivity, algo)
+        dv, df, de, _, _ = self.ctx.extrema_result()
+        return (torch.as_tensor(_DeviceView(dv, frame.voxels, "<i4", self), device=self.device),
+                torch.as_tensor(_DeviceView(df, frame.voxels, "<i4", self), device=self.device),
+                torch.as_tensor(_DeviceView(de, frame.voxels // 32, "<i4", self), device=self.device), stats)
+
     def geodesic(self, frame: Frame, mask, seeds, metric: int = capi.GEO_CHAMFER, algo: int = ALGO_TILED):
         """Geodesic distance of a grid (n <= 1024): returns (dist, reach, stats) -- a tensor of n^3 values, x fastest, the length of the
         shortest path from a seed voxel that stays inside `mask` (0 at the seeds inside the mask; capi.GEO_NONE, which reads -1 in the

@@ -773,6 +773,74 @@ int vp_watershed_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_mask, co
                       int order, uint32_t quantum, int connectivity, int algo, uint32_t* h_labels, uint32_t* h_cut,
                       uint64_t* h_stats /* any two may be NULL, not all three */);
 
+/* ---- grayscale reconstruction and h-extrema: automatic watershed markers (no reference counterpart) ------------------
+ * vp_watershed floods from one marker per object, and the only marker source above is vp_components_label of one erosion radius for the
+ * whole grid.  This is what MorphoLibJ's "Distance Transform Watershed 3D" picks its markers with (its "dynamic" parameter): the extended
+ * maxima of the distance map, through grayscale morphological reconstruction -- which also fills holes, removes peaks and gives h-domes.
+ *   inputs      a whole-grid frame, n % 32 == 0, n <= 1024; a marker field F and a mask field G, one uint32 per voxel, x fastest, in
+ *               vp_edt's layout; a domain M, a bit grid, NULL = every voxel.  OUTSIDE THE GRID COUNTS AS NOT IN M.
+ *   work values u(v) = v for VP_REC_DILATION, u(v) = ~v for VP_REC_EROSION; off M the work value of both fields is 0.
+ *   dilation    R is the unique field with R(p) = min(G(p), max(R0(p), max over the neighbours q of p in M of R(q))), R0 = min(F, G):
+ *               R(p) is the maximum over paths q .. p inside M of min(R0(q), min of G along the path).  Neighbours under `connectivity`
+ *               (VP_CONN_6 / VP_CONN_26; a diagonal step needs no other voxel set).
+ *   erosion     the same on the complemented values, the result complemented back: rec_erosion(F, G) = ~rec_dilation(~F, ~G).
+ *   output R    one uint32 per voxel (4 n^3 bytes); off M it reads 0 for dilation and 0xFFFFFFFF for erosion.
+ *   walls       A WORK VALUE OF 0 INSIDE M BEHAVES EXACTLY LIKE "NOT IN M": the voxel stays at 0 and nothing passes through it (G = 0 for
+ *               dilation, G = 0xFFFFFFFF for erosion).
+ *   h_stats     { |M|, voxels of M with R != R0, the sum of R over M (exact in 64 bits), the largest R over M (erosion: the smallest; 0
+ *               for an empty M) }.  Nothing that depends on the number of rounds is reported.
+ * Integers and a monotone fixed point that is unique: numpy, the C++ host form, VP_ALGO_NAIVE and VP_ALGO_TILED give the same bytes and
+ * statistics whatever the order of execution (the argument is in csrc/reconstruct.hip and DESIGN.md section 25).
+ *   vp_reconstruct         builds R into a grow-only buffer that the CONTEXT owns; vp_ctx_release frees it.  BLOCKS: convergence is read
+ *                          back -- a batch of round flags at a time (NAIVE), the length of the list of active blocks once per round (TILED).
+ *   vp_reconstruct_result  pointer to the last R, the statistics and the side they are for; any argument may be NULL.  Before a build and
+ *                          after a release: NULL, zeros and side 0.
+ *   vp_reconstruct_host    host in, host out (staged through workspace slots); h_domain may be NULL; h_field or h_stats may be NULL, not both.
+ * vp_extrema composes it: h-maxima / h-minima and the extended extrema of a value field.
+ *   V scaled    VP_EXT_LINEAR: the values as they are.  VP_EXT_SQRT16: floor(sqrt(256 v)) in exact 64-bit integer arithmetic, for every
+ *               uint32 -- a squared distance such as vp_edt's becomes a distance in sixteenths of a voxel, a fixed h means the same depth
+ *               at every size, and vp_watershed can flood V at quantum 1 where D^2 is refused.
+ *   H flattened VP_EXT_MAXIMA: H = rec_dilation(V - h, V), the subtraction saturating at 0.  VP_EXT_MINIMA: H = rec_erosion(V + h, V), the
+ *               addition saturating at 0xFFFFFFFF.  Both on the domain; off it H reads as R does.  h = 0 gives H = V on M.
+ *   E extrema   a bit grid: for maxima p is in E iff H(p) > 0 and the plateau of p -- the connected set in M of equal H -- has no neighbour
+ *               in M with a larger H; equivalently H(p) > rec_dilation(H - 1, H)(p), which is how it is built.  Minima are the dual.  A
+ *               voxel whose work value is 0 is never an extremum (for D^2: the voxels outside the solid).  The markers of vp_watershed are
+ *               vp_components_label(E, connectivity): the caller chains it.
+ *   h_stats     { |M|, |E|, the largest H over M (minima: the smallest; 0 for an empty M), voxels of M with H != V }.
+ *   vp_extrema / _result / _host   as above: V, H and E live in grow-only buffers of the context (4 n^3 + 4 n^3 + n^3 / 8 bytes) in a feature
+ *               of their own, the second reconstruction in 4 n^3 bytes of scratch; all are freed by vp_ctx_release.  A vp_extrema call
+ *               leaves vp_reconstruct_result as it was, and the other way round.  _host: any three of h_scaled / h_flat / h_extrema /
+ *               h_stats may be NULL, not all four.
+ * A slab frame and n > 1024: VP_ERR_UNSUPPORTED.  Null ctx / f / marker / mask / values, a buffer that is not 16-byte aligned, an input
+ * overlapping a buffer the context writes in this call (the last result among them: copy it first), an unknown mode / kind / scale /
+ * connectivity / algo: VP_ERR_INVALID.  A refusal is decided before anything is touched and leaves the previous result as it was.
+ *   algo: VP_ALGO_NAIVE -- one lane per voxel with room (R < G) pulls the maximum over its neighbours from global memory, in place;
+ *   whole-grid launches repeat until one changes nothing.  VP_ALGO_TILED -- one workgroup per active block of 32 x 16 x 16 voxels, R and a
+ *   one-voxel halo staged in LDS (45 KB), the lane's row of G in registers, swept until nothing rises or a fixed number of sweeps have
+ *   run, changed values written back; neighbour blocks are flagged as in vp_geodesic; the first list is the blocks that hold a voxel with
+ *   R0 < G (only such a voxel can ever change), the loop ends with the first empty list.  No atomics on R; kernel boundaries are the only
+ *   synchronisation between workgroups.  Scratch of the context (grow-only, freed by vp_ctx_release): 8 bytes per block.
+ *   Timing books under existing keys: the launches that write R0 and the scaled / shifted fields under VP_K_MD_FILL, the final launches
+ *   (statistics, un-complementing, the extrema ballot) under VP_K_MD_SPLIT, the block list under VP_K_MD_SCAN, the TILED rounds under
+ *   VP_K_MD_BRICK, the NAIVE rounds under VP_K_MD_NAIVE. */
+enum { VP_REC_DILATION = 0, VP_REC_EROSION = 1 };
+enum { VP_EXT_MAXIMA = 0, VP_EXT_MINIMA = 1 };
+enum { VP_EXT_LINEAR = 0, VP_EXT_SQRT16 = 1 };
+int vp_reconstruct(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_domain /* bit grid, may be NULL: the whole grid */,
+                   const uint32_t* d_marker, const uint32_t* d_mask, int mode, int connectivity, int algo,
+                   uint64_t* h_stats /* 4, may be NULL: |M|, voxels with R != R0, sum of R, largest (erosion: smallest) R */);
+int vp_reconstruct_result(vp_ctx* ctx, uint32_t** d_field, uint64_t* h_stats /* 4 */, uint32_t* h_n);
+int vp_reconstruct_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_domain /* may be NULL */, const uint32_t* h_marker,
+                        const uint32_t* h_mask, int mode, int connectivity, int algo, uint32_t* h_field,
+                        uint64_t* h_stats /* either may be NULL, not both */);
+int vp_extrema(vp_ctx* ctx, const vp_frame* f, const uint32_t* d_domain /* may be NULL */, const uint32_t* d_values, int kind, int scale,
+               uint32_t h, int connectivity, int algo,
+               uint64_t* h_stats /* 4, may be NULL: |M|, |E|, largest (minima: smallest) H, voxels with H != V */);
+int vp_extrema_result(vp_ctx* ctx, uint32_t** d_scaled, uint32_t** d_flat, uint32_t** d_extrema, uint64_t* h_stats /* 4 */, uint32_t* h_n);
+int vp_extrema_host(vp_ctx* ctx, const vp_frame* f, const uint32_t* h_domain /* may be NULL */, const uint32_t* h_values, int kind, int scale,
+                    uint32_t h, int connectivity, int algo, uint32_t* h_scaled, uint32_t* h_flat, uint32_t* h_extrema,
+                    uint64_t* h_stats /* any three may be NULL, not all */);
+
 /* ---- region analysis: per-label volume, moments, surface, Euler number (no reference counterpart) -------------------
  * The last step of voxelize -> repair -> split -> measure: what MorphoLibJ calls "Analyze Regions 3D".  vp_components_sizes stops at one
  * voxel count per label; this gives, per label of a label volume, everything that is an integer sum, minimum or maximum over voxels.
